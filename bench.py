@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the per-frame surfel-fusion hot path (BASELINE.json: depth frames fused/sec @ 1226x370).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--frames-per-step F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--frames-per-step F] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (config.workload): BASELINE configs[1] -- synthetic KITTI-shaped replay, 1226x370, one frame
@@ -222,6 +222,50 @@ def canon_bytes(a: np.ndarray) -> bytes:
     return words.tobytes()
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_MAPS = 4  # ... the final maps of this many subsequences, picked by a fixed seed
+
+
+def surfel_columns(m: np.ndarray):
+    """a surfel map as finite float32 arrays: the matrix (n, 11) of its fields in SURFEL_DTYPE order with every NaN / inf
+    written as 0, and per surfel a code that says which fields were not finite -- field i contributes c * 4^i, c = 1 NaN,
+    2 +inf, 3 -inf (22 bits: exact in float32).  The reference keeps surfels with NaN attributes in its maps, so a caller
+    does receive them; the two int32 counters are far below 2^24 and convert exactly."""
+    cols = np.zeros((len(m), len(m.dtype.names)), np.float32)
+    code = np.zeros(len(m), np.int64)
+    for i, f in enumerate(m.dtype.names):
+        x = m[f]
+        if x.dtype.kind == "i":
+            assert len(m) == 0 or int(np.abs(x).max()) < (1 << 24), f
+        else:
+            c = np.where(np.isnan(x), 1, np.where(np.isposinf(x), 2, np.where(np.isneginf(x), 3, 0)))
+            code += c * 4 ** i
+            x = np.where(c == 0, x, 0)
+        cols[:, i] = x
+    return cols, code.astype(np.float32)
+
+
+def dump_outputs(out_dir, maps):
+    """`--dump-outputs DIR`: the maps {subsequence: surfel array} the timed region left behind, as DIR/map_s<b>.npy (the
+    fields) and DIR/map_s<b>_nonfinite.npy (the codes of the fields that were NaN / inf), see surfel_columns; if they exceed
+    DUMP_BYTES together, the same fixed-seed sample of rows of every map."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(len(m) for m in maps.values()) * 4 * 12
+    frac = min(1.0, (DUMP_BYTES - 2 * 4096 * len(maps)) / total) if total else 1.0  # (4 KB per file for its .npy header)
+    rng = np.random.default_rng(20240607)
+    for b, m in sorted(maps.items()):
+        if frac < 1.0:
+            m = m[np.sort(rng.choice(len(m), int(len(m) * frac), replace=False))]
+        cols, code = surfel_columns(m)
+        np.save(os.path.join(out_dir, f"map_s{b:03d}.npy"), cols)
+        np.save(os.path.join(out_dir, f"map_s{b:03d}_nonfinite.npy"), code)
+
+
+def dump_subsequences(n):
+    """which subsequences' maps --dump-outputs writes: a fixed-seed sample, the same for the same --streams"""
+    return sorted(int(b) for b in np.random.default_rng(7).choice(n, min(n, DUMP_MAPS), replace=False))
+
+
 def oracle_replay_worker(spec_json):
     """`python bench.py --oracle-replay-worker '<json>'`: the CPU oracle's replay of one subsequence of the headline from an
     empty map through frame `frames` - 1 -- the CHECKER of the timed region (started beside the GPU run, never inside a timed
@@ -334,8 +378,9 @@ def self_launch(n_gpus):
     import socket
     import subprocess
     one_device = os.environ.get("DSM_BENCH_ONE_DEVICE", "0") == "1"
-    import torch
-    seen = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    if not one_device:  # (one-device test runs: this process never opens the GPU, its ranks share it)
+        import torch
+        seen = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if not one_device and seen < n_gpus:
         print(f"bench.py: --gpus {n_gpus} needs {n_gpus} visible GPUs, this box shows {seen}; nothing was measured", file=sys.stderr)
         return 2
@@ -467,6 +512,8 @@ def sharded_workload(args, world, rank, device, dist, coll_dev, group_error):
         dt = max(float(t_[1].item()) for t_ in every)
     n_final = eng.ff.map_size()
     got = eng.cloud() if spec else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {0: eng.cloud()})
     merge_s, counts = None, [n_final]
     if dist is not None:
         cloud = eng.cloud_tensor(torch, f"cuda:{device}").to(coll_dev)
@@ -592,8 +639,14 @@ def main():
                          "subsequence per GPU streamed from page-locked host memory through replay.HipEngine, all-gather of the final clouds")
     ap.add_argument("--no-rccl-world1", action="store_true",
                     help="--gpus 1: do not create the process group of one through which the final cloud merge runs on RCCL")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the final maps they left (rank 0: a fixed sample of its subsequences) as "
+                         "DIR/map_s<b>.npy, float32 (n, 11) in SURFEL_DTYPE field order with NaN / inf as 0, and "
+                         "DIR/map_s<b>_nonfinite.npy, which fields were NaN / inf per surfel; at most 64 MB in all")
     ap.add_argument("--oracle-replay-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if args.frames_per_step <= 0:
         args.frames_per_step = 48 if args.workload == "sharded" else 32
 
@@ -784,6 +837,8 @@ def main():
     for sp in oracle_specs:
         got = handles[sp["subsequence"]].map_download()
         end_maps[sp["subsequence"]] = (int(len(got)), hashlib.sha256(canon_bytes(got)).hexdigest())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {b: handles[b].map_download() for b in dump_subsequences(B)})
 
     # merge of the final clouds (outside the timed region): RCCL all-gather over xGMI
     merged_total = sum(m_end)

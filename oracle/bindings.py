@@ -199,7 +199,7 @@ class RefSurfelMap:
 
     def __init__(self, cam, drift_free_poses=10, kind=None, lib_path=None):
         # kind "map_threads": real std::threads, for timing only (the reference's warp_surfels races, SM.cpp:791-824)
-        # lib_path: another build of the same driver (tests/_build/libdsm_ref_map_on_product.so: the reference's
+        # lib_path: another build of the same driver (oracle/_ref/libdsm_ref_map_on_product.so: the reference's
         # surfel_map.cpp on top of the product's engine facade)
         lib = C.CDLL(lib_path or ref_lib_path(kind or ("map_rgbd" if cam.rgbd else "map")))
         lib.refmap_create.restype = _vp

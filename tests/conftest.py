@@ -99,7 +99,8 @@ def node_hostemu_lib(oracle_built):
     return out
 
 
-from ref_on_product import REF_SRC, build_ref_map_on_product, build_ros_node_on_product  # noqa: E402
+from ref_on_product import (REF_MAP_ON_PRODUCT, REF_SRC, ROS_NODE_ON_PRODUCT, build_ref_map_on_product,  # noqa: E402
+                            build_ros_node_on_product)
 
 
 def _prebuilt_or_skip(out):
@@ -113,9 +114,8 @@ def ros_node_on_product():
     """The reference's own surfel_fusion/src/ros_node.cpp, compiled IN PLACE and UNCHANGED, with include/ros_compat in
     front of it: `SurfelMap surfel_map(nh)` and its subscriber bindings are the product's node class.  ROS itself is
     shimmed (oracle/shims + tests/ros_shims: a message pump fed from a recorded log).  Built where the reference
-    exists (tests/ref_on_product.py); the binary travels to the GPU box."""
-    out = os.path.join(ROOT, "tests", "_build", "ros_node_on_product")
-    return build_ros_node_on_product() if os.path.isdir(REF_SRC) else _prebuilt_or_skip(out)
+    exists (oracle/Makefile `on_product`, into oracle/_ref/ with the other reference builds), prebuilt elsewhere."""
+    return build_ros_node_on_product() if os.path.isdir(REF_SRC) else _prebuilt_or_skip(ROS_NODE_ON_PRODUCT)
 
 
 @pytest.fixture(scope="session")
@@ -123,5 +123,4 @@ def ref_map_on_product():
     """INTEGRATION.md §2 as a build: the reference's surfel_map.{h,cpp} compiled in place and unchanged with
     include/engine_compat in front (its `#include <fusion_functions.h>` resolves to the product's facade), linked against
     libdsm_hip.so -- the reference's node class running on the HIP engine through the drop-in call."""
-    out = os.path.join(ROOT, "tests", "_build", "libdsm_ref_map_on_product.so")
-    return build_ref_map_on_product() if os.path.isdir(REF_SRC) else _prebuilt_or_skip(out)
+    return build_ref_map_on_product() if os.path.isdir(REF_SRC) else _prebuilt_or_skip(REF_MAP_ON_PRODUCT)

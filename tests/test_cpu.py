@@ -45,12 +45,28 @@ def test_port_oracle_matches_golden(ob, synth):
         assert not fields_equal(local, ref_map), case["name"]
 
 
+def _ref_tu_traces():
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_golden_ref_tu
+    return make_golden_ref_tu, json.load(open(make_golden_ref_tu.OUT))
+
+
 def test_port_oracle_matches_reference_tu(ob, synth):
-    """Live comparison with oracle/_ref (only where it was built: needs /root/reference or the prebuilt .so)."""
-    if not ob.have_ref("serial"):
-        pytest.skip("oracle/_ref not built")
+    """The port against the reference TU, frame by frame: labels, seeds, map and counts -- live where oracle/_ref was built
+    (the reference's sources, or the prebuilt .so), and always against the digests of that TU's run
+    (tests/golden/ref_tu_traces.json, tests/golden/make_golden_ref_tu.py)."""
+    mk, gold = _ref_tu_traces()
     # TINY_RAGGED: (size mod 8) > 4, the reference touches superpixel_seeds[-1] for the border pixels (undefined
     # behaviour, harmless in this build: heap bytes in front of the vector); the port pins that record to zero
+    assert [(c["camera"], c["scene_seed"], c["frames"]) for c in gold["sequences"]] == mk.SEQUENCES
+    for case in gold["sequences"]:
+        cam, scene, n = getattr(synth, case["camera"]), synth.Scene(seed=case["scene_seed"]), case["frames"]
+        port = mk.sequence_trace(ob.PortOracle(cam), cam, scene, n, synth, ob.SURFEL_DTYPE)
+        for t, (got, want) in enumerate(zip(port, case["trace"])):
+            assert got == want, (case["camera"], t, ["new surfels", "map size", "labels", "seeds", "map"][next(i for i in range(5) if got[i] != want[i])])
+        assert len(port) == len(case["trace"]) == n
+    if not ob.have_ref("serial"):
+        return
     for cam, scene, n in ((synth.TINY, synth.Scene(seed=3), 40), (synth.KITTI_1241, synth.Scene(seed=4), 3),
                           (synth.TINY_RAGGED, synth.Scene(seed=3), 12)):
         ref, port = ob.RefOracle(cam), ob.PortOracle(cam)
@@ -63,14 +79,23 @@ def test_port_oracle_matches_reference_tu(ob, synth):
             assert np.array_equal(ref.labels(), port.labels())
             assert not fields_equal(ref.seeds(), port.seeds())
             assert not fields_equal(lr, lp)
+    # ... and the fixture is still what the reference TU computes
+    case = gold["sequences"][0]
+    cam = getattr(synth, case["camera"])
+    assert mk.sequence_trace(ob.RefOracle(cam), cam, synth.Scene(seed=case["scene_seed"]), case["frames"], synth, ob.SURFEL_DTYPE) == case["trace"]
 
 
 def test_reference_quirk_states(ob, synth):
     """State-level check of the two scheduling quirks on the reference TU vs the port:
-    random stable flags + random labels, and an unstable seed that owns no pixel mid-chunk."""
+    random stable flags + random labels, and an unstable seed that owns no pixel mid-chunk.  Live where oracle/_ref was
+    built, and always against the digests of the reference TU's run (tests/golden/ref_tu_traces.json)."""
+    mk, gold = _ref_tu_traces()
+    cam = getattr(synth, gold["quirk_states"]["camera"])
+    port = mk.quirk_trace(ob.PortOracle, cam, synth)
+    assert len(port) == mk.QUIRK_TRIALS and port == gold["quirk_states"]["trace"]
     if not ob.have_ref("serial"):
-        pytest.skip("oracle/_ref not built")
-    cam = synth.TINY
+        return
+    assert mk.quirk_trace(ob.RefOracle, cam, synth) == port
     img, dep, _ = synth.render(cam, synth.Scene(seed=8), 0)
     rng = np.random.default_rng(0)
     for trial in range(6):
@@ -1018,6 +1043,39 @@ def test_port_oracle_matches_long_golden(ob, synth):
             after, k = ob.PortOracle(cam).fuse_map(ref, img, dep, pose, m)
             assert (k, len(after)) == (want["n_new"], want["n_local"]), (key, trial)
             assert _map_sha(after, ob.SURFEL_DTYPE) == want["map_sha256"], (key, trial)
+
+
+def test_bench_dump_encoding_is_finite_and_lossless(tmp_path):
+    """bench.py --dump-outputs: every array it writes is finite, and the field matrix with the codes of the non-finite
+    fields gives back the map it came from (NaN, +inf and -inf in any field, counters exact); beyond 64 MB the rows are a
+    fixed-seed sample, the same for the same maps."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from densesurfelmapping_amd import api
+    rng = np.random.default_rng(1)
+    m = np.zeros(1000, api.SURFEL_DTYPE)
+    for f in m.dtype.names:
+        m[f] = rng.integers(0, 1 << 20, len(m)) if m.dtype[f].kind == "i" else rng.normal(size=len(m))
+    for f in ("px", "size", "weight"):
+        for v in (np.nan, np.inf, -np.inf):
+            m[f][rng.integers(0, len(m), 20)] = v
+    cols, code = bench.surfel_columns(m)
+    assert cols.dtype == code.dtype == np.float32 and np.isfinite(cols).all() and np.isfinite(code).all()
+    code = code.astype(np.int64)
+    back = np.zeros_like(m)
+    for i, f in enumerate(m.dtype.names):
+        c = code // 4 ** i % 4
+        x = np.where(c == 1, np.nan, np.where(c == 2, np.inf, np.where(c == 3, -np.inf, cols[:, i])))
+        back[f] = x
+    assert fields_equal(back, m) == []
+    big = {b: np.tile(m, 1500) for b in (3, 9)}  # 2 x 1.5 M surfels: beyond 64 MB
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["map_s003.npy", "map_s003_nonfinite.npy", "map_s009.npy", "map_s009_nonfinite.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        assert np.load(tmp_path / "a" / f).tobytes() == np.load(tmp_path / "b" / f).tobytes(), f
 
 
 def test_bench_gpus_flag_fails_loudly_without_devices():

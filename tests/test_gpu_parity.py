@@ -1199,10 +1199,10 @@ def test_replay_engine_streams_in_chunks(mods, depth, chunk):
         src.close()
 
 
-@pytest.mark.parametrize("world,workload", [(2, "headline"), (8, "headline"), (2, "sharded"), (8, "sharded")])
+@pytest.mark.parametrize("world,workload", [(2, "headline"), (3, "headline"), (2, "sharded"), (3, "sharded")])
 def test_bench_ranks_on_one_gpu(world, workload):
-    """bench.py's multi-rank paths (sharding, barriers, max-over-ranks timing, all-gather merge) with two ranks, and with the
-    node's eight, sharing the one GPU of the test box; collectives on gloo (the driver runs the real thing on RCCL).  Launched
+    """bench.py's multi-rank paths (sharding, barriers, max-over-ranks timing, all-gather merge) with two ranks, and with
+    three, sharing the one GPU of the test box; collectives on gloo (the driver runs the real thing on RCCL).  Launched
     the way a user would: `python bench.py --gpus N` starts its own ranks.  `headline`: the weak-scaled batched replay;
     `sharded`: BASELINE configs[2] itself -- one sequence cut into one streamed subsequence per rank.  A multi-rank line is
     checked like a one-rank line, on EVERY rank: maps the TIMED run left behind against the CPU oracle's replay of the same frames
@@ -1216,6 +1216,8 @@ def test_bench_ranks_on_one_gpu(world, workload):
         extra = ["--steps", "20" if world == 2 else "6", "--warmup", "5" if world == 2 else "2", "--streams", "2", "--frames-per-step", "4"]
     else:
         extra = ["--workload", "sharded", "--steps", "3", "--warmup", "1", "--frames-per-step", "24" if world == 2 else "13", "--no-roofline"]
+    # (at most three ranks: with the test process and torch.distributed.run's agent that stays within the six processes
+    # a shared machine lets hold one GPU)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + extra,
                        env=env, capture_output=True, text=True, timeout=900)
     out = _bench_line(r)
@@ -1343,6 +1345,38 @@ def test_bench_sharded_workload_one_gpu():
     assert out["multi_gpu"]["backend"] == "nccl" and out["roofline"]["frac"] > 0 and out["cpu_baseline"]["value"] > 0
 
 
+def test_bench_dump_outputs_are_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the final maps the timed steps left (a fixed sample of subsequences, float32
+    (n, 11) in SURFEL_DTYPE field order and the codes of their non-finite fields, all finite, at most 64 MB), and two runs with the same arguments write the same arrays;
+    --steps sets the number of timed steps and ms_per_step is the time of one."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DSM_BENCH_ONE_DEVICE", "DSM_BENCH_BACKEND")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--streams", "8", "--batches", "2",
+                            "--frames-per-step", "4", "--no-roofline", "--no-dropin", "--no-cpu-baseline", "--no-verify", "--no-rccl-world1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900)
+        out = _bench_line(r)
+        assert out["steps"] == 3 and out["config"]["timed_frame_indices"] == [4, 15]
+        assert abs(out["ms_per_step"] * 3 - out["config"]["timed_seconds"] * 1e3) < 0.01 * out["ms_per_step"] + 1e-3
+        files = sorted(os.listdir(d))
+        maps = [f for f in files if not f.endswith("_nonfinite.npy")]
+        assert maps and all(f.startswith("map_s") and f.endswith(".npy") for f in files), files
+        assert files == sorted(maps + [f[:-4] + "_nonfinite.npy" for f in maps]), files
+        arrays = {f: np.load(d / f) for f in files}
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        for f in maps:
+            a, code = arrays[f], arrays[f[:-4] + "_nonfinite.npy"]
+            assert a.ndim == 2 and a.shape[1] == 11 and len(a) > 0 and code.shape == (len(a),)
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert dumps[0][f].tobytes() == dumps[1][f].tobytes(), f
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """`python bench.py --gpus N` on a box with fewer than N devices must fail loudly -- not run one GPU and print n_gpus 1."""
     import subprocess
@@ -1362,14 +1396,20 @@ def test_bench_refuses_more_gpus_than_visible():
 
 
 def test_bench_two_gpus_rccl():
-    """The real thing where two devices exist: two ranks, one GPU each, RCCL all-gather of the final clouds."""
+    """Two ranks through `python bench.py --gpus 2`, RCCL all-gather of the final clouds where two devices exist (one GPU
+    each, the real thing).  On a box with one GPU the same command runs with both ranks on it and the collectives on gloo
+    (RCCL takes one rank per device): the two-rank line, its merge and its check against the CPU oracle are asserted alike."""
     import subprocess
     import sys
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
+    two = torch.cuda.device_count() >= 2
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DSM_BENCH_ONE_DEVICE", "DSM_BENCH_BACKEND")}
+    if not two:
+        env.update(DSM_BENCH_BACKEND="gloo", DSM_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--streams", "8",
                         "--batches", "1", "--frames-per-step", "8", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
     out = _bench_line(r)
-    assert out["n_gpus"] == 2 and out["multi_gpu"]["backend"] == "nccl" and out["multi_gpu"]["world_size_seen_by_backend"] == 2
+    mg = out["multi_gpu"]
+    assert out["n_gpus"] == 2 and mg["backend"] == ("nccl" if two else "gloo") and mg["world_size_seen_by_backend"] == 2
+    assert len(mg["per_rank_frames_per_s"]) == 2 and mg["final_cloud_bytes_all_ranks"] == 44 * out["config"]["final_surfels_all_ranks"] > 0
+    assert out["verified"] is True and out["verified_timed_region"] is True, out.get("verification")
