@@ -145,7 +145,7 @@ def test_dropin_delta_download(mods):
     assert st["calls"] == 90 and st["delta_calls"] >= 60, st
     groups_in_map = (n + 63) // 64
     assert st["delta_groups"] / st["delta_calls"] < 0.6 * groups_in_map, (st, groups_in_map)
-    assert grew and n > 40000
+    assert grew and shrank and n > 40000
     print("drop-in delta download:", st, "groups in the final map:", groups_in_map)
     ff.close()
     # ---- the reference node's own path: fuse_initialize_map + the caller's compaction loop (here: the oracle's fuse_map, which
@@ -547,14 +547,10 @@ def test_rgbd_constant_set(mods):
         _compare_frame(f"rgbd frame {t}", ff, orc, lg, lo.astype(api.SURFEL_DTYPE))
 
 
-def test_edge_inputs(mods):
-    """Empty depth (no surfels), all-holes rows, constant image: same answers as the oracle."""
-    api, synth, ob = mods
-    cam = synth.TINY
-    ff = api.FusionFunctions.from_camera(cam, surfel_capacity=65536)
-    orc = ob.PortOracle(cam)
+def edge_cases(cam):
+    """{name: (image, depth)}: the hostile frames of test_edge_inputs at any camera size (also fed to the batched kernels,
+    tests/test_gpu_adversarial.py)."""
     rng = np.random.default_rng(3)
-    pose = np.eye(4, dtype=np.float32)
     cases = {
         "zero depth": (np.full((cam.height, cam.width), 100, np.uint8), np.zeros((cam.height, cam.width), np.float32)),
         "flat wall": (np.full((cam.height, cam.width), 128, np.uint8), np.full((cam.height, cam.width), 4.0, np.float32)),
@@ -580,7 +576,17 @@ def test_edge_inputs(mods):
                                                        np.where(u < 0.15, np.float32(-np.inf), np.where(u < 0.2, -nd, nd)))).astype(np.float32))
     # few grey levels over a flat wall: whole regions of exact cost ties (the first candidate in scan order wins, FF.cpp:430)
     cases["two greys"] = (np.where((np.arange(cam.width)[None, :] // 24 + np.arange(cam.height)[:, None] // 16) % 2, 64, 192).astype(np.uint8), cases["flat wall"][1])
-    for name, (img, dep) in cases.items():
+    return cases
+
+
+def test_edge_inputs(mods):
+    """Empty depth (no surfels), all-holes rows, constant image: same answers as the oracle."""
+    api, synth, ob = mods
+    cam = synth.TINY
+    ff = api.FusionFunctions.from_camera(cam, surfel_capacity=65536)
+    orc = ob.PortOracle(cam)
+    pose = np.eye(4, dtype=np.float32)
+    for name, (img, dep) in edge_cases(cam).items():
         lg, kg = ff.fuse_map(0, img, dep, pose, np.zeros(0, api.SURFEL_DTYPE))
         lo, ko = orc.fuse_map(0, img, dep, pose, np.zeros(0, ob.SURFEL_DTYPE))
         assert kg == ko, name
