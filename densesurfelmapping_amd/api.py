@@ -39,6 +39,8 @@ DSM_FLAG_NO_GRAPH = 1
 DSM_FLAG_UPLOAD_STREAM = 2
 DSM_FLAG_WAVE_STAMPS = 4
 DSM_MAX_STAGES = 32
+# dsm_status
+DSM_OK, DSM_E_INVALID, DSM_E_NO_DEVICE, DSM_E_HIP, DSM_E_CAPACITY, DSM_E_STATE = 0, -1, -2, -3, -4, -5
 
 # every symbol include/dsm.h declares
 ABI_SYMBOLS = (
@@ -49,7 +51,7 @@ ABI_SYMBOLS = (
     "dsm_map_upload", "dsm_map_size", "dsm_map_capacity", "dsm_map_download", "dsm_map_copy_to_device",
     "dsm_map_warp", "dsm_warp_grouped_device", "dsm_map_extract", "dsm_map_append",
     "dsm_store_deactivate", "dsm_store_activate", "dsm_store_erase", "dsm_store_warp", "dsm_store_size",
-    "dsm_store_download",
+    "dsm_store_download", "dsm_cloud_compose", "dsm_frame_cloud",
     "dsm_frame_upload", "dsm_frame_upload_device", "dsm_frame_pitch", "dsm_frame_upload_async", "dsm_frames_upload_async", "dsm_frame_uploads_wait", "dsm_fuse_frame_resident", "dsm_replay_enqueue", "dsm_replay_enqueue_host", "dsm_replay_wait",
     "dsm_synchronize", "dsm_last_new_count", "dsm_stream",
     "dsm_batch_create", "dsm_batch_destroy", "dsm_batch_last_error", "dsm_batch_replay_enqueue", "dsm_batch_synchronize",
@@ -58,6 +60,11 @@ ABI_SYMBOLS = (
     "dsm_debug_run_stages", "dsm_debug_get_label_buffer", "dsm_debug_set_label_buffer", "dsm_debug_get_seed_state",
     "dsm_debug_set_seed_state",
 )
+
+
+# dsm_cloud_compose's map part (include/dsm.h dsm_cloud_select)
+CLOUD_SELECT_NONE, CLOUD_SELECT_MATURE, CLOUD_SELECT_NONZERO = 0, 1, 2
+CLOUD_TILE = 1024  # records per workgroup of the map compaction (dsm_device.h kCloudTile)
 
 
 class DsmError(RuntimeError):
@@ -132,6 +139,8 @@ def load_library():
     lib.dsm_store_warp.argtypes = [_vp, C.c_int32, _vp, _vp, _vp]
     lib.dsm_store_size.argtypes = [_vp, _vp]
     lib.dsm_store_download.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
+    lib.dsm_cloud_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, _vp, C.c_int, C.c_int32, _vp]
+    lib.dsm_frame_cloud.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int32, _vp]
     lib.dsm_frame_upload.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_upload_device.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_pitch.argtypes = [_vp, _vp]
@@ -376,6 +385,36 @@ class FusionFunctions:
         c = np.zeros((max(n, 1), 4), np.float32)
         self._check(self._lib.dsm_store_download(self._h, begin, n, _ptr(s), _ptr(c)))
         return s[:n].copy(), c[:n].copy()
+
+    # ---- point-cloud publications (surfel_map.cpp:1115-1151, 1283-1454) ---------------------------
+    def cloud_compose(self, select=CLOUD_SELECT_MATURE, segments=(), dst_ptr=None, cap=None):
+        """dsm_cloud_compose: the map records that pass `select` (CLOUD_SELECT_*), then the store's XYZI runs `segments`
+        [(begin, count), ...].  Returns an (n, 4) float32 array -- or, with dst_ptr (device memory of cap points), n."""
+        seg = np.ascontiguousarray(np.asarray(segments, np.int32).reshape(-1, 2))
+        b = np.ascontiguousarray(seg[:, 0]) if len(seg) else np.zeros(1, np.int32)
+        c = np.ascontiguousarray(seg[:, 1]) if len(seg) else np.zeros(1, np.int32)
+        n = C.c_int32(0)
+        if dst_ptr is not None:
+            self._check(self._lib.dsm_cloud_compose(self._h, select, len(seg), _ptr(b), _ptr(c), _vp(dst_ptr), 1, cap, C.byref(n)))
+            return n.value
+        if cap is None:  # size it from the bound: the map records plus the runs
+            cap = self.map_size() + int(seg[:, 1].sum() if len(seg) else 0)
+        out = np.zeros((max(cap, 1), 4), np.float32)
+        self._check(self._lib.dsm_cloud_compose(self._h, select, len(seg), _ptr(b), _ptr(c), _ptr(out), 0, cap, C.byref(n)))
+        return out[: n.value].copy()
+
+    def frame_cloud(self, slot, pose7, dst_ptr=None, cap=None):
+        """dsm_frame_cloud: publish_raw_pointcloud of the frame in `slot`; pose7 = px py pz qx qy qz qw (geometry_msgs/Pose).
+        Returns a (width * height, 4) float32 array in column-major pixel order -- or, with dst_ptr, n."""
+        p = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        n = C.c_int32(0)
+        if dst_ptr is not None:
+            self._check(self._lib.dsm_frame_cloud(self._h, slot, _ptr(p), _vp(dst_ptr), 1, cap, C.byref(n)))
+            return n.value
+        cap = self.width * self.height if cap is None else cap
+        out = np.zeros((max(cap, 1), 4), np.float32)
+        self._check(self._lib.dsm_frame_cloud(self._h, slot, _ptr(p), _ptr(out), 0, cap, C.byref(n)))
+        return out[: n.value].copy()
 
     def frame_upload(self, slot, image, depth):
         image, depth = self._frame_args(image, depth)

@@ -166,7 +166,7 @@ struct dsm_handle {
     std::vector<void *> allocs; // every hipMalloc of this handle
     std::vector<hipGraphExec_t> retired; // graphs replaced while possibly in flight (map_grows): destroyed at the next synchronisation point
     FrameParams *h_params = nullptr; // pinned staging ring
-    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups; [64..127] the device's scalar block as it came
+    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size; [64..127] the device's scalar block as it came
     int32_t *d_scalars = nullptr;    // the device's scalar block (64 ints: n_local @8, n_local_next @16, n_new @24, n_holes @32, status @48, delta count @56)
     FrameParams *d_params = nullptr;
     uint8_t *d_stage_img = nullptr; // one tightly packed frame on its way into a pitched slot
@@ -245,6 +245,13 @@ struct dsm_handle {
     void *d_store_tmp = nullptr;
     size_t store_tmp_bytes = 0;
     int store_cap = 0, store_n = 0;
+    // point-cloud publications (dsm_cloud_compose / dsm_frame_cloud): grow-only device scratch -- the map part's count, the
+    // tile counts of the compaction and the run table -- and the points on their way to a host destination
+    int32_t *d_pub = nullptr;
+    size_t pub_ints = 0;
+    float4 *d_pub_out = nullptr;
+    size_t pub_out_cap = 0;
+    hipEvent_t ev_pub_dst = nullptr; // a device destination is written behind the null stream's work so far (as hipMemcpy would)
     // drop-in calls (dsm_fuse_map / dsm_fuse_initialize_map): page-locked staging owned by the handle
     uint8_t *pin_frame = nullptr; // one frame, image then depth, rows at the frame slots' pitch
     dsm_surfel *pin_map = nullptr; // shadow of the caller's array: what the last drop-in call returned == the device map
@@ -1272,6 +1279,9 @@ void dsm_destroy(dsm_handle *h) {
     if (h->d_store) (void)hipFree(h->d_store);
     if (h->d_cloud) (void)hipFree(h->d_cloud);
     if (h->d_store_tmp) (void)hipFree(h->d_store_tmp);
+    if (h->d_pub) (void)hipFree(h->d_pub);
+    if (h->d_pub_out) (void)hipFree(h->d_pub_out);
+    if (h->ev_pub_dst) (void)hipEventDestroy(h->ev_pub_dst);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->h_scalars) (void)hipHostFree(h->h_scalars);
     if (h->pin_frame) (void)hipHostFree(h->pin_frame);
@@ -1679,6 +1689,142 @@ int dsm_store_download(dsm_handle *h, int32_t begin, int32_t n, dsm_surfel *surf
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (n && surfels_out) HIP_TRY(h, hipMemcpy(surfels_out, h->d_store + begin, sizeof(dsm_surfel) * (size_t)n, hipMemcpyDeviceToHost));
     if (n && xyzi_out) HIP_TRY(h, hipMemcpy(xyzi_out, h->d_cloud + begin, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ point-cloud publications
+
+namespace {
+
+int pub_reserve(dsm_handle *h, size_t ints, size_t points) {
+    if (ints > h->pub_ints) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_pub) (void)hipFree(h->d_pub);
+        h->d_pub = nullptr;
+        h->pub_ints = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->d_pub, ints * 2 * sizeof(int32_t)));
+        h->pub_ints = ints * 2;
+    }
+    if (points > h->pub_out_cap) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_pub_out) (void)hipFree(h->d_pub_out);
+        h->d_pub_out = nullptr;
+        h->pub_out_cap = 0;
+        const size_t want = points + points / 4;
+        HIP_TRY(h, hipMalloc((void **)&h->d_pub_out, want * sizeof(float4)));
+        h->pub_out_cap = want;
+    }
+    return DSM_OK;
+}
+
+// the caller's device memory is written on the handle's stream: behind what the null stream (torch's default stream, a
+// hipMemset of the buffer) has been given so far -- the order dsm_map_copy_to_device's hipMemcpy gets
+int pub_order_dst(dsm_handle *h) {
+    if (!h->ev_pub_dst) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pub_dst, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(h->ev_pub_dst, nullptr));
+    HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_pub_dst, 0));
+    return DSM_OK;
+}
+
+} // namespace
+
+int dsm_cloud_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, void *dst,
+                      int dst_on_device, int32_t cap, int32_t *n) {
+    if (!h || !n || cap < 0) return DSM_E_INVALID;
+    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
+    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
+    if (cap > 0 && !dst) return fail(h, DSM_E_INVALID, "null output");
+    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
+    // the runs, checked before anything reaches the device; empty ones are dropped
+    std::vector<int32_t> seg;
+    int64_t runs_total = 0;
+    for (int32_t s = 0; s < n_segments; s++) {
+        const int32_t b = store_begin[s], c = store_count[s];
+        if (b < 0 || c < 0 || (int64_t)b + c > h->store_n)
+            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, c, h->store_n);
+        if (!c) continue;
+        seg.push_back(b);
+        seg.push_back(c);
+        seg.push_back((int32_t)runs_total);
+        runs_total += c;
+    }
+    if (runs_total > INT32_MAX) return fail(h, DSM_E_INVALID, "%lld points in the runs", (long long)runs_total);
+    int rc = bind_device(h);
+    if (rc) return rc;
+    const int n_upper = select == kCloudNone ? 0 : h->map_upper;
+    const size_t tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    // where the points go: the caller's device memory, or staging for a host destination (no more than the points there can be)
+    const int64_t bound = (int64_t)n_upper + runs_total;
+    const int32_t dev_cap = (int32_t)(bound < cap ? bound : cap);
+    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), dst_on_device ? 0 : (size_t)dev_cap))) return rc;
+    if (dst_on_device && (rc = pub_order_dst(h))) return rc;
+    float4 *out = dst_on_device ? (float4 *)dst : h->d_pub_out;
+    int32_t *d_total = h->d_pub, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
+    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    hipError_t e = launch_cloud_map(h->hc.local, h->hc.n_local, n_upper, select, d_tiles, d_total, out, dev_cap, h->stream);
+    if (e == hipSuccess) e = launch_cloud_gather(h->d_cloud, d_seg, (int)(seg.size() / 3), (int)runs_total, d_total, out, dev_cap, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "cloud launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const int64_t total = (int64_t)h->h_scalars[5] + runs_total;
+    *n = (int32_t)total;
+    if (total > cap) return fail(h, DSM_E_CAPACITY, "%lld points exceed the caller's capacity %d", (long long)total, cap);
+    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
+int dsm_frame_cloud(dsm_handle *h, int slot, const double *pose7, void *dst, int dst_on_device, int32_t cap, int32_t *n) {
+    if (!h || !n || cap < 0) return DSM_E_INVALID;
+    if (!pose7) return fail(h, DSM_E_INVALID, "null pose");
+    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
+    const int w = h->hc.w, hh = h->hc.h;
+    const int64_t total = (int64_t)w * hh;
+    *n = (int32_t)total;
+    if (total > cap) return fail(h, DSM_E_CAPACITY, "%lld points exceed the caller's capacity %d", (long long)total, cap);
+    if (!dst) return fail(h, DSM_E_INVALID, "null output");
+    int rc = bind_device(h);
+    if (rc) return rc;
+    if (!dst_on_device && (rc = pub_reserve(h, 0, (size_t)total))) return rc;
+    if (dst_on_device && (rc = pub_order_dst(h))) return rc;
+    // behind the asynchronous uploads that wrote the slot (the frames enqueued before it on the map stream come behind theirs)
+    {
+        const ReadSlots reads(h, slot, slot + 1);
+        if ((rc = wait_uploads(h, h->stream, kSerialBit))) return rc;
+    }
+    // SM.cpp:1117-1128: Quaternionf from the message's doubles, toRotationMatrix() in float (Eigen/src/Geometry/Quaternion.h)
+    RawCloudParams p;
+    const float x = (float)pose7[3], y = (float)pose7[4], z = (float)pose7[5], qw = (float)pose7[6];
+    const float tx = 2.0f * x, ty = 2.0f * y, tz = 2.0f * z;
+    const float twx = tx * qw, twy = ty * qw, twz = tz * qw;
+    const float txx = tx * x, txy = ty * x, txz = tz * x;
+    const float tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    float *R = p.rot; // column-major: R[c * 4 + r] = (r, c)
+    for (int k = 0; k < 16; k++) R[k] = 0.0f;
+    R[0] = 1.0f - (tyy + tzz);
+    R[4] = txy - twz;
+    R[8] = txz + twy;
+    R[1] = txy + twz;
+    R[5] = 1.0f - (txx + tzz);
+    R[9] = tyz - twx;
+    R[2] = txz - twy;
+    R[6] = tyz + twx;
+    R[10] = 1.0f - (txx + tyy);
+    R[15] = 1.0f;
+    p.t[0] = (float)pose7[0];
+    p.t[1] = (float)pose7[1];
+    p.t[2] = (float)pose7[2];
+    p.fx = h->cfg.fx;
+    p.fy = h->cfg.fy;
+    p.cx = h->cfg.cx;
+    p.cy = h->cfg.cy;
+    float4 *out = dst_on_device ? (float4 *)dst : h->d_pub_out;
+    const uint8_t *img = (const uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems;
+    const float *dep = (const float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
+    hipError_t e = total ? launch_cloud_raw(img, dep, h->hc.pitch, w, hh, p, out, h->stream) : hipSuccess;
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "raw cloud launch: %s", hipGetErrorString(e));
+    // the call returns when the points are there: nothing enqueued later (an upload into this slot) can overtake the read
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost));
     return DSM_OK;
 }
 

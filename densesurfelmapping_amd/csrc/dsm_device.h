@@ -174,4 +174,23 @@ hipError_t launch_append_count(const DeviceCtx &ctx, int n, hipStream_t st);
 // group numbers in `idx`; count[0] = how many there are (may exceed cap_groups: those are not packed), flags cleared
 hipError_t launch_delta_pack(const DeviceCtx &ctx, dsm_surfel *buf, int32_t *idx, int32_t *count, int cap_groups, int n_upper, hipStream_t st);
 
+// ---- point-cloud publications (dsm_k_cloud.h)
+constexpr int kCloudNone = 0, kCloudMature = 1, kCloudNonzero = 2; // dsm_cloud_select of include/dsm.h
+constexpr int kCloudChunks = 4;                   // 64-record chunks per wave of the compaction
+constexpr int kCloudTile = 4 * 64 * kCloudChunks; // records per workgroup of its count / scatter passes (1024)
+struct RawCloudParams {
+    float rot[16]; // column-major 4x4, rotation in the upper 3x3 (xform_dir reads that part only)
+    float t[3];
+    float fx, fy, cx, cy;
+};
+// XYZI of the records [0, min(*n_ptr, n_upper)) that pass `select` (kCloudMature / kCloudNonzero), in map order, into
+// out[0, cap); total[0] = how many passed (also those beyond cap).  tile_cnt: ceil(n_upper / 1024) ints of scratch
+hipError_t launch_cloud_map(const dsm_surfel *rec, const int32_t *n_ptr, int n_upper, int select, int32_t *tile_cnt, int32_t *total,
+                            float4 *out, int cap, hipStream_t st);
+// runs of src (seg: n_seg triples begin, count, exclusive output offset; `total` points in all) to out[*base_ptr + ...], below cap
+hipError_t launch_cloud_gather(const float4 *src, const int32_t *seg, int n_seg, int total, const int32_t *base_ptr, float4 *out, int cap,
+                               hipStream_t st);
+// w * h world points of a pitched frame, column-major (index i * h + j for column i, row j)
+hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, int w, int h, const RawCloudParams &p, float4 *out, hipStream_t st);
+
 } // namespace dsm

@@ -8,7 +8,7 @@
 // absent from this image; the few operations the node takes from it are written out from their published
 // definitions: 4x4 product with left-to-right accumulation, 4x4 inverse by the adjugate closed form,
 // Quaterniond <-> rotation matrix (Eigen/src/Geometry/Quaternion.h), Vector3f normalize / cross.
-#include "../../include/dsm_surfel_map.h"
+#include "dsm_surfel_map_node.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,20 +28,9 @@
 
 namespace {
 
+using namespace dsm_node;
+
 // ------------------------------------------------------------------ fp64 rigid-transform helpers
-struct Mat4 {
-    double d[16]; // column-major, d[j*4+i] = (i,j)
-    double &operator()(int i, int j) { return d[j * 4 + i]; }
-    double operator()(int i, int j) const { return d[j * 4 + i]; }
-};
-
-Mat4 identity4() {
-    Mat4 m;
-    for (int k = 0; k < 16; k++) m.d[k] = 0.0;
-    m(0, 0) = m(1, 1) = m(2, 2) = m(3, 3) = 1.0;
-    return m;
-}
-
 Mat4 mul(const Mat4 &a, const Mat4 &b) {
     Mat4 c;
     for (int j = 0; j < 4; j++)
@@ -139,89 +128,8 @@ bool same_position(const dsm_pose_msg &a, const dsm_pose_msg &b) { return a.px =
 
 double to_sec(dsm_stamp s) { return (double)s.sec + 1e-9 * (double)s.nsec; }
 
-// ------------------------------------------------------------------ node state
-struct PoseElement { // surfel_map.h:36-46; attached_surfels live in the handle's store
-    dsm_pose_msg cam_pose, loop_pose;
-    std::vector<int> linked_pose_index;
-    int segment = -1; // index into dsm_surfel_map::segments while the keyframe is inactive, else -1
-    dsm_stamp cam_stamp = {0, 0};
-};
-
-// The inactive set as a segment table.  The handle's store holds the surfels of the inactive keyframes back to
-// back in deactivation order; entry i of the table says which keyframe owns the i-th run and how long it is, and a
-// run starts where the runs before it end.  This one table is what the reference spreads over three members:
-// PoseElement::attached_surfels.size() (count), PoseElement::points_begin_index (start) and
-// pointcloud_pose_index / PoseElement::points_pose_index (the table order and its inverse), surfel_map.h:36-46,134.
-struct Segment {
-    int keyframe;
-    int begin; // sum of the counts before this entry (kept, not recomputed: the taps read it)
-    int count;
-};
-
-struct Frame {
-    dsm_stamp stamp;
-    uint8_t *bytes; // tightly packed rows: a page-locked block of the node's pool, or (overflow) pageable memory
-    bool pinned;
-};
-
-// Frames wait for their pose in page-locked memory so that the upload of a frame is one DMA -- but only the first
-// kPinnedFrames of each kind: the reference's subscriber queues are 5000 deep (ros_node.cpp:24-25) in PAGEABLE memory, and
-// a stalled pose source must not pin 5000 x 2.3 MB of host RAM.  The overflow lives in pageable blocks (their upload is a
-// staged copy: slower, still correct) that are freed as soon as they leave the queue; free page-locked blocks beyond
-// kPooledFrames go back to the system as well.
-constexpr size_t kPinnedFrames = 256, kPooledFrames = 64;
-
-struct FramePool {
-    std::vector<uint8_t *> free_blocks; // page-locked, ready for reuse
-    size_t pinned_live = 0;             // page-locked blocks handed out and not yet released
-    uint8_t *take(size_t bytes, bool *pinned) {
-        if (!free_blocks.empty()) {
-            uint8_t *p = free_blocks.back();
-            free_blocks.pop_back();
-            pinned_live++;
-            *pinned = true;
-            return p;
-        }
-        if (pinned_live < kPinnedFrames) {
-            void *p = nullptr;
-            if (dsm_host_alloc(&p, bytes) == DSM_OK) {
-                pinned_live++;
-                *pinned = true;
-                return (uint8_t *)p;
-            }
-        }
-        *pinned = false;
-        return (uint8_t *)malloc(bytes ? bytes : 1);
-    }
-    void release(const Frame &f) {
-        if (!f.pinned) { free(f.bytes); return; }
-        pinned_live--;
-        if (free_blocks.size() < kPooledFrames) free_blocks.push_back(f.bytes);
-        else dsm_host_free(f.bytes);
-    }
-    void drain() {
-        for (uint8_t *p : free_blocks) dsm_host_free(p);
-        free_blocks.clear();
-    }
-};
-
 } // namespace
 
-struct dsm_surfel_map {
-    dsm_surfel_map_config cfg;
-    dsm_handle *engine = nullptr;
-    std::list<Frame> image_buffer, depth_buffer;                                 // surfel_map.h:96-97
-    FramePool image_pool, depth_pool;                                            // where the buffered frames' bytes live
-    std::list<std::tuple<dsm_stamp, dsm_pose_msg, int>> pose_reference_buffer; // :98
-    std::vector<PoseElement> poses_database;                                     // :120
-    std::set<int> local_surfels_indexs;                                          // :122
-    std::vector<Segment> segments;                                               // inactive set, store order (:134)
-    int64_t poses_dropped = 0, frames_dropped = 0;
-    bool failed = false; // an engine call failed half-way through a state change: refuse further input
-    Mat4 transform_kitti = identity4();                                          // function-static at surfel_map.cpp:215
-    int64_t frames_fused = 0;
-    std::string err;
-};
 
 namespace {
 
@@ -242,25 +150,6 @@ int engine_fail(dsm_surfel_map *m, int rc, const char *what) { return fail(m, rc
         const int rc_ = (expr);                              \
         if (rc_ != DSM_OK) return engine_fail(m, rc_, #expr); \
     } while (0)
-
-// SurfelMap::get_driftfree_poses (:1643-1673): breadth-first over linked_pose_index, root first,
-// driftfree_range - 1 levels, each pose once in discovery order
-void get_driftfree_poses(const dsm_surfel_map *m, int root_index, std::vector<int> &driftfree_poses, int driftfree_range) {
-    if ((int)m->poses_database.size() < root_index + 1) return;
-    std::vector<int> this_level, next_level;
-    this_level.push_back(root_index);
-    driftfree_poses.push_back(root_index);
-    for (int i = 1; i < driftfree_range; i++) {
-        for (int p : this_level)
-            for (int linked : m->poses_database[p].linked_pose_index)
-                if (std::find(driftfree_poses.begin(), driftfree_poses.end(), linked) == driftfree_poses.end()) {
-                    next_level.push_back(linked);
-                    driftfree_poses.push_back(linked);
-                }
-        this_level.swap(next_level);
-        next_level.clear();
-    }
-}
 
 // SurfelMap::get_add_remove_poses (:1597-1641)
 void get_add_remove_poses(const dsm_surfel_map *m, int root_index, std::vector<int> &pose_to_add, std::vector<int> &pose_to_remove) {
@@ -435,8 +324,15 @@ int synchronize_msgs(dsm_surfel_map *m) {
     ENGINE_TRY(m, dsm_frame_upload(m->engine, slot, m->image_buffer.front().bytes, (size_t)w,
                                    (const float *)m->depth_buffer.front().bytes, (size_t)w * 4));
     ENGINE_TRY(m, dsm_fuse_frame_resident(m->engine, slot, relative_index, pose16));
+    m->last.valid = true;
+    m->last.stamp = std::get<0>(m->pose_reference_buffer.front()); // fuse_stamp (:112)
+    m->last.relative_index = relative_index;
+    m->last.fuse_pose = matrix_to_pose(fuse_pose); // fuse_pose_ros (:151-152)
+    m->last.slot = slot;
     m->pose_reference_buffer.pop_front(); // :163
     m->frames_fused++;
+    // :189-197 publish results (dsm_surfel_map_set_publish; nothing to do unless it installed a publisher)
+    if (m->on_fused) return m->on_fused(m);
     return DSM_OK;
 }
 
@@ -543,6 +439,7 @@ void dsm_surfel_map_destroy(dsm_surfel_map *m) {
     for (const Frame &f : m->depth_buffer) m->depth_pool.release(f);
     m->image_pool.drain();
     m->depth_pool.drain();
+    if (m->release_publish) m->release_publish(m);
     delete m;
 }
 

@@ -1,0 +1,160 @@
+// dsm_surfel_map_node.h -- the state of the node (include/dsm_surfel_map.h), shared by its two translation units:
+// dsm_surfel_map.cpp (the host logic of class SurfelMap) and dsm_surfel_map_clouds.cpp (the point-cloud publications).
+// dsm_surfel_map.cpp calls only the engine entry points it always called; the publications reach it through the function
+// pointers of struct dsm_surfel_map.  Internal: not installed, not part of the C ABI.
+#pragma once
+#include "../../include/dsm_surfel_map.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <list>
+#include <set>
+#include <string>
+#include <tuple>
+#include <vector>
+
+namespace dsm_node {
+
+// ------------------------------------------------------------------ fp64 rigid-transform helpers
+struct Mat4 {
+    double d[16]; // column-major, d[j*4+i] = (i,j)
+    double &operator()(int i, int j) { return d[j * 4 + i]; }
+    double operator()(int i, int j) const { return d[j * 4 + i]; }
+};
+
+inline Mat4 identity4() {
+    Mat4 m;
+    for (int k = 0; k < 16; k++) m.d[k] = 0.0;
+    m(0, 0) = m(1, 1) = m(2, 2) = m(3, 3) = 1.0;
+    return m;
+}
+
+// ------------------------------------------------------------------ node state
+struct PoseElement { // surfel_map.h:36-46; attached_surfels live in the handle's store
+    dsm_pose_msg cam_pose, loop_pose;
+    std::vector<int> linked_pose_index;
+    int segment = -1; // index into dsm_surfel_map::segments while the keyframe is inactive, else -1
+    dsm_stamp cam_stamp = {0, 0};
+};
+
+// The inactive set as a segment table.  The handle's store holds the surfels of the inactive keyframes back to
+// back in deactivation order; entry i of the table says which keyframe owns the i-th run and how long it is, and a
+// run starts where the runs before it end.  This one table is what the reference spreads over three members:
+// PoseElement::attached_surfels.size() (count), PoseElement::points_begin_index (start) and
+// pointcloud_pose_index / PoseElement::points_pose_index (the table order and its inverse), surfel_map.h:36-46,134.
+struct Segment {
+    int keyframe;
+    int begin; // sum of the counts before this entry (kept, not recomputed: the taps read it)
+    int count;
+};
+
+struct Frame {
+    dsm_stamp stamp;
+    uint8_t *bytes; // tightly packed rows: a page-locked block of the node's pool, or (overflow) pageable memory
+    bool pinned;
+};
+
+// Frames wait for their pose in page-locked memory so that the upload of a frame is one DMA -- but only the first
+// kPinnedFrames of each kind: the reference's subscriber queues are 5000 deep (ros_node.cpp:24-25) in PAGEABLE memory, and
+// a stalled pose source must not pin 5000 x 2.3 MB of host RAM.  The overflow lives in pageable blocks (their upload is a
+// staged copy: slower, still correct) that are freed as soon as they leave the queue; free page-locked blocks beyond
+// kPooledFrames go back to the system as well.
+constexpr size_t kPinnedFrames = 256, kPooledFrames = 64;
+
+struct FramePool {
+    std::vector<uint8_t *> free_blocks; // page-locked, ready for reuse
+    size_t pinned_live = 0;             // page-locked blocks handed out and not yet released
+    uint8_t *take(size_t bytes, bool *pinned) {
+        if (!free_blocks.empty()) {
+            uint8_t *p = free_blocks.back();
+            free_blocks.pop_back();
+            pinned_live++;
+            *pinned = true;
+            return p;
+        }
+        if (pinned_live < kPinnedFrames) {
+            void *p = nullptr;
+            if (dsm_host_alloc(&p, bytes) == DSM_OK) {
+                pinned_live++;
+                *pinned = true;
+                return (uint8_t *)p;
+            }
+        }
+        *pinned = false;
+        return (uint8_t *)malloc(bytes ? bytes : 1);
+    }
+    void release(const Frame &f) {
+        if (!f.pinned) { free(f.bytes); return; }
+        pinned_live--;
+        if (free_blocks.size() < kPooledFrames) free_blocks.push_back(f.bytes);
+        else dsm_host_free(f.bytes);
+    }
+    void drain() {
+        for (uint8_t *p : free_blocks) dsm_host_free(p);
+        free_blocks.clear();
+    }
+};
+
+// what the publications of one fuse refer to (synchronize_msgs, surfel_map.cpp:143-152)
+struct FuseInfo {
+    bool valid = false;
+    dsm_stamp stamp = {0, 0};   // fuse_stamp
+    int relative_index = -1;
+    dsm_pose_msg fuse_pose = {}; // fuse_pose_ros = pose_eigen2ros(reference_pose * relative_pose)
+    int slot = 0;               // the engine frame slot that holds the fused frame
+};
+
+} // namespace dsm_node
+
+struct dsm_surfel_map {
+    using Frame = dsm_node::Frame;
+    using FramePool = dsm_node::FramePool;
+    using PoseElement = dsm_node::PoseElement;
+    using Segment = dsm_node::Segment;
+    using FuseInfo = dsm_node::FuseInfo;
+    using Mat4 = dsm_node::Mat4;
+    dsm_surfel_map_config cfg;
+    dsm_handle *engine = nullptr;
+    std::list<Frame> image_buffer, depth_buffer;                                 // surfel_map.h:96-97
+    FramePool image_pool, depth_pool;                                            // where the buffered frames' bytes live
+    std::list<std::tuple<dsm_stamp, dsm_pose_msg, int>> pose_reference_buffer; // :98
+    std::vector<PoseElement> poses_database;                                     // :120
+    std::set<int> local_surfels_indexs;                                          // :122
+    std::vector<Segment> segments;                                               // inactive set, store order (:134)
+    int64_t poses_dropped = 0, frames_dropped = 0;
+    bool failed = false; // an engine call failed half-way through a state change: refuse further input
+    Mat4 transform_kitti = dsm_node::identity4();                                          // function-static at surfel_map.cpp:215
+    int64_t frames_fused = 0;
+    std::string err;
+    // the latest fuse, what the clouds of dsm_surfel_map_get_cloud refer to (set by synchronize_msgs; last.valid false before)
+    FuseInfo last;
+    // dsm_surfel_map_set_publish (dsm_surfel_map_clouds.cpp) installs these: called after every fuse where the reference
+    // publishes (surfel_map.cpp:189-197), and by dsm_surfel_map_destroy.  Null (the default): no extra work, no synchronisation.
+    int (*on_fused)(dsm_surfel_map *m) = nullptr;
+    void (*release_publish)(dsm_surfel_map *m) = nullptr;
+    void *publish = nullptr; // the publisher's own state
+};
+
+namespace dsm_node {
+
+// SurfelMap::get_driftfree_poses (:1643-1673): breadth-first over linked_pose_index, root first,
+// driftfree_range - 1 levels, each pose once in discovery order
+inline void get_driftfree_poses(const dsm_surfel_map *m, int root_index, std::vector<int> &driftfree_poses, int driftfree_range) {
+    if ((int)m->poses_database.size() < root_index + 1) return;
+    std::vector<int> this_level, next_level;
+    this_level.push_back(root_index);
+    driftfree_poses.push_back(root_index);
+    for (int i = 1; i < driftfree_range; i++) {
+        for (int p : this_level)
+            for (int linked : m->poses_database[p].linked_pose_index)
+                if (std::find(driftfree_poses.begin(), driftfree_poses.end(), linked) == driftfree_poses.end()) {
+                    next_level.push_back(linked);
+                    driftfree_poses.push_back(linked);
+                }
+        this_level.swap(next_level);
+        next_level.clear();
+    }
+}
+
+} // namespace dsm_node

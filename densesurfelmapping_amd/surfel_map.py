@@ -20,14 +20,30 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_save_cloud", "dsm_surfel_map_save_mesh", "dsm_surfel_map_save_map",
     "dsm_surfel_map_engine", "dsm_surfel_map_frames_fused", "dsm_surfel_map_dropped_poses", "dsm_surfel_map_pose_count",
     "dsm_surfel_map_get_pose", "dsm_surfel_map_get_links", "dsm_surfel_map_get_attached",
-    "dsm_surfel_map_get_inactive_cloud",
+    "dsm_surfel_map_get_inactive_cloud", "dsm_surfel_map_get_cloud", "dsm_surfel_map_get_cloud_device", "dsm_surfel_map_set_publish",
 )
+
+# dsm_cloud_kind of include/dsm_surfel_map.h
+CLOUD_ACTIVE, CLOUD_INACTIVE, CLOUD_ALL, CLOUD_NEIGHBOR, CLOUD_RAW = range(5)
+CLOUD_KINDS = ("active", "inactive", "all", "neighbor", "raw")
 
 _vp = C.c_void_p
 
 
 class _Stamp(C.Structure):
     _fields_ = [("sec", C.c_uint32), ("nsec", C.c_uint32)]
+
+
+class _PoseMsg(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("px", "py", "pz", "qx", "qy", "qz", "qw")]
+
+
+class _Publication(C.Structure):
+    _fields_ = [("stamp", _Stamp), ("relative_index", C.c_int32), ("fuse_pose", _PoseMsg), ("kinds_mask", C.c_uint32),
+                ("points", C.POINTER(C.c_float) * 5), ("n_points", C.c_int32 * 5)]
+
+
+_PublishFn = C.CFUNCTYPE(None, _vp, C.POINTER(_Publication))
 
 
 class _MapConfig(C.Structure):
@@ -65,6 +81,10 @@ def _bind(lib):
         lib.dsm_map_download.argtypes = [_vp, _vp, C.c_int32, _vp]
         lib.dsm_last_error.argtypes = [_vp]
         lib.dsm_last_error.restype = C.c_char_p
+        if hasattr(lib, "dsm_surfel_map_get_cloud"):  # (the tests' CPU stand-in of the node has no clouds)
+            lib.dsm_surfel_map_get_cloud.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
+            lib.dsm_surfel_map_get_cloud_device.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
+            lib.dsm_surfel_map_set_publish.argtypes = [_vp, C.c_uint32, _PublishFn, _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -92,6 +112,7 @@ class SurfelMap:
 
     def close(self):
         if getattr(self, "_h", None):
+            self._publish_cb = None
             self._lib.dsm_surfel_map_destroy(self._h)
             self._h = None
 
@@ -194,3 +215,52 @@ class SurfelMap:
         out = np.zeros((max(n.value, 1), 4), dtype=np.float32)
         self._check(self._lib.dsm_surfel_map_get_inactive_cloud(self._h, _ptr(out), n.value, C.byref(n)))
         return out[: n.value]
+
+    # ---- point-cloud topics (publish_*_pointcloud, surfel_map.cpp:1115-1151, 1283-1454)
+    @staticmethod
+    def _kind(kind) -> int:
+        return CLOUD_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+
+    def cloud(self, kind) -> np.ndarray:
+        """The cloud of `kind` (CLOUD_* or its name) for the current state, (n, 4) float32 x y z intensity."""
+        k = self._kind(kind)
+        n = C.c_int32()
+        rc = self._lib.dsm_surfel_map_get_cloud(self._h, k, None, 0, C.byref(n))  # the count (DSM_E_CAPACITY unless empty)
+        if rc not in (0, api.DSM_E_CAPACITY):
+            self._check(rc)
+        out = np.zeros((max(n.value, 1), 4), dtype=np.float32)
+        self._check(self._lib.dsm_surfel_map_get_cloud(self._h, k, _ptr(out), n.value, C.byref(n)))
+        return out[: n.value]
+
+    def cloud_to_device(self, kind, dst_ptr: int, cap: int) -> int:
+        """The cloud of `kind` into device memory (cap points of 16 bytes); returns the count (map_copy_to_device's convention)."""
+        n = C.c_int32()
+        self._check(self._lib.dsm_surfel_map_get_cloud_device(self._h, self._kind(kind), _vp(dst_ptr), cap, C.byref(n)))
+        return n.value
+
+    def set_publish(self, kinds, fn):
+        """After every fuse call fn(publication) with publication = {"stamp", "relative_index", "fuse_pose" (7 doubles),
+        "clouds": {name: (n, 4) float32 copy}} for the kinds asked for (names or CLOUD_*); kinds empty or fn None: off."""
+        mask = 0
+        for k in kinds or ():
+            mask |= 1 << self._kind(k)
+        if not mask or fn is None:
+            self._check(self._lib.dsm_surfel_map_set_publish(self._h, 0, _PublishFn(), None))
+            self._publish_cb = None
+            return
+
+        def trampoline(_user, pub_p):
+            pub = pub_p.contents
+            p = pub.fuse_pose
+            clouds = {}
+            for k in range(5):
+                if pub.kinds_mask & (1 << k):
+                    n = pub.n_points[k]
+                    clouds[CLOUD_KINDS[k]] = (np.ctypeslib.as_array(pub.points[k], shape=(n, 4)).copy() if n
+                                              else np.zeros((0, 4), np.float32))
+            fn({"stamp": (pub.stamp.sec, pub.stamp.nsec), "relative_index": pub.relative_index,
+                "fuse_pose": np.array([p.px, p.py, p.pz, p.qx, p.qy, p.qz, p.qw]), "clouds": clouds})
+
+        cb = _PublishFn(trampoline)
+        self._check(self._lib.dsm_surfel_map_set_publish(self._h, mask, cb, None))
+        self._publish_cb = cb  # kept alive as long as the library may call it

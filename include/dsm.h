@@ -220,6 +220,29 @@ int dsm_store_size(dsm_handle *h, int32_t *n);
 /* either output may be NULL; xyzi_out receives 4 floats per point (x, y, z, intensity).  Synchronises. */
 int dsm_store_download(dsm_handle *h, int32_t begin, int32_t n, dsm_surfel *surfels_out, float *xyzi_out);
 
+/* ---- point-cloud publications (the reference's publish_*_pointcloud, surfel_map.cpp:1115-1151, 1283-1454): XYZI points,
+ * 4 floats each (x, y, z, intensity), the layout of dsm_store_download's xyzi_out ---- */
+typedef enum {
+    DSM_CLOUD_SELECT_NONE = 0,    /* no map part */
+    DSM_CLOUD_SELECT_MATURE = 1,  /* resident records with update_times >= 5, map order (publish_active_pointcloud :1398-1417) */
+    DSM_CLOUD_SELECT_NONZERO = 2  /* resident records with update_times != 0, map order (publish_neighbor_pointcloud :1292-1303) */
+} dsm_cloud_select;
+/* The map part chosen by `select`, then the store's XYZI shadow runs [store_begin[s], +store_count[s]) for s < n_segments,
+ * in list order (empty runs and an empty list are allowed).  ACTIVE = (MATURE, no runs), INACTIVE = (NONE, [0, store size)),
+ * ALL = (MATURE, [0, store size)), NEIGHBOR = (NONZERO, the runs of the drift-free neighbours).  dst is host memory
+ * (dst_on_device = 0; pageable or dsm_host_alloc'ed) or device memory.  *n = the number of points; more than cap:
+ * DSM_E_CAPACITY, *n = the count needed, nothing written past cap.  A run outside the store: DSM_E_INVALID before any device
+ * work.  A device destination is written behind the work enqueued on the null stream so far (as by a hipMemcpy).
+ * Synchronises. */
+int dsm_cloud_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                      void *dst, int dst_on_device, int32_t cap, int32_t *n);
+/* publish_raw_pointcloud (:1115-1151) of the frame in `slot`: width * height points, unfiltered, COLUMN-major (point i * height + j
+ * is pixel column i, row j), world = R * ((i - cx) * d / fx, (j - cy) * d / fy, d) + T with R = Quaternionf(qw, qx, qy, qz)
+ * (the doubles cast to float, not normalised).toRotationMatrix(), T = (px, py, pz) as float; intensity = the image byte.
+ * pose7 = px py pz qx qy qz qw.  The launch reads the slot: a later upload into it comes behind (the call synchronises).  A
+ * device destination is ordered like dsm_cloud_compose's. */
+int dsm_frame_cloud(dsm_handle *h, int slot, const double *pose7, void *dst, int dst_on_device, int32_t cap, int32_t *n);
+
 /* Copy a frame into frame slot `slot` (0 .. frame_slots-1 of the config) and return when it is there (the host
  * buffers may be reused).  By default the copy is ordered behind everything enqueued so far.  With
  * DSM_FLAG_UPLOAD_STREAM it runs on the handle's upload stream instead: it waits only for the enqueued frames that

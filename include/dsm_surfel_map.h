@@ -11,8 +11,11 @@
  * logic in this library; the surfels themselves never leave HBM: the active map is the resident map of
  * a dsm_handle (include/dsm.h) and the inactive set is its device-side store (dsm_store_*).
  *
- * Not mirrored: the publish_* methods (RViz markers / point-cloud topics, surfel_map.cpp:906-1058,
- * 1115-1151, 1283-1454) -- read the same data through the taps at the end of this header.
+ * Point-cloud topics: the five clouds of publish_{active,inactive,all,neighbor,raw}_pointcloud (surfel_map.cpp:1115-1151,
+ * 1283-1454) are built on the GPU, bit-identical to the reference's, and either pulled (dsm_surfel_map_get_cloud*) or handed
+ * to a callback after every fuse (dsm_surfel_map_set_publish), at the point where the reference publishes (:189-197).
+ * Not mirrored: the RViz markers of publish_pose_graph / publish_camera_position (:906-1058) -- read the same data through
+ * the taps at the end of this header.
  *
  * Errors: the reference returns void and prints; these return a dsm_status (include/dsm.h) and keep a
  * message for dsm_surfel_map_last_error.  Inputs on which the reference indexes out of range (undefined
@@ -85,6 +88,43 @@ int dsm_surfel_map_orb_results_input(dsm_surfel_map *m, dsm_stamp loop_stamp, co
 int dsm_surfel_map_save_cloud(dsm_surfel_map *m, const char *path); /* :1153-1174, ASCII PCD of XYZI points */
 int dsm_surfel_map_save_mesh(dsm_surfel_map *m, const char *path);  /* :1176-1281, ASCII PLY, one hexagon per surfel */
 int dsm_surfel_map_save_map(dsm_surfel_map *m, const char *path);   /* :75-81 = save_mesh */
+
+/* ---- point clouds: 4 floats per point (x, y, z, intensity), the reference's PointXYZI ---- */
+typedef enum {
+    DSM_CLOUD_ACTIVE = 0,   /* publish_active_pointcloud (:1398-1417): resident surfels with update_times >= 5, map order */
+    DSM_CLOUD_INACTIVE = 1, /* publish_inactive_pointcloud (:1385-1396): inactive_pointcloud as it is */
+    DSM_CLOUD_ALL = 2,      /* publish_all_pointcloud (:1419-1454): ACTIVE, then INACTIVE */
+    DSM_CLOUD_NEIGHBOR = 3, /* publish_neighbor_pointcloud (:1283-1319, method 1): resident surfels with update_times != 0, then
+                               the inactive points of the non-local poses of get_driftfree_poses(relative_index, 2 *
+                               drift_free_poses), in its breadth-first order */
+    DSM_CLOUD_RAW = 4,      /* publish_raw_pointcloud (:1115-1151): the fused frame, cam_width * cam_height points, unfiltered,
+                               column-major (point i * cam_height + j = pixel column i, row j), posed with fuse_pose_ros */
+    DSM_CLOUD_KINDS = 5
+} dsm_cloud_kind;
+#define DSM_CLOUD_BIT(kind) (1u << (kind))
+
+/* The cloud of `kind` for the current state; NEIGHBOR and RAW refer to the latest fuse (its relative_index, its frame and
+ * fuse_pose_ros).  DSM_E_STATE before the first fuse; more than cap points: DSM_E_CAPACITY with *n = the count needed.
+ * Synchronises. */
+int dsm_surfel_map_get_cloud(dsm_surfel_map *m, int kind, float *xyzi_out, int32_t cap, int32_t *n);
+/* the same into device memory of the node's GPU (e.g. a torch tensor's data_ptr) */
+int dsm_surfel_map_get_cloud_device(dsm_surfel_map *m, int kind, void *dst_device, int32_t cap, int32_t *n);
+
+/* What one fuse publishes.  points[k] / n_points[k] for every kind k in the mask (NULL / 0 for the others) are page-locked
+ * buffers of the library, valid until the callback returns. */
+typedef struct dsm_surfel_map_publication {
+    dsm_stamp stamp;          /* fuse_stamp: header.stamp of the clouds */
+    int32_t relative_index;   /* the reference keyframe of the fused frame */
+    dsm_pose_msg fuse_pose;   /* fuse_pose_ros */
+    uint32_t kinds_mask;
+    const float *points[DSM_CLOUD_KINDS];
+    int32_t n_points[DSM_CLOUD_KINDS];
+} dsm_surfel_map_publication;
+typedef void (*dsm_surfel_map_publish_fn)(void *user, const dsm_surfel_map_publication *pub);
+/* After every fuse (synchronize_msgs, after fuse_map and before the next pose is handled) build the clouds of kinds_mask
+ * (DSM_CLOUD_BIT(kind) | ...) and call fn(user, &publication) on the calling thread.  kinds_mask 0 or fn NULL: off (the
+ * default; no extra work, no synchronisation). */
+int dsm_surfel_map_set_publish(dsm_surfel_map *m, uint32_t kinds_mask, dsm_surfel_map_publish_fn fn, void *user);
 
 /* ---- taps (what the publish_* methods read) ---- */
 dsm_handle *dsm_surfel_map_engine(dsm_surfel_map *m); /* active map: dsm_map_size / dsm_map_download */

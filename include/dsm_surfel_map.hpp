@@ -21,6 +21,7 @@
 #define DSM_SURFEL_MAP_HPP
 
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -163,6 +164,32 @@ class SurfelMap {
     int save_cloud(const std::string &save_path_name) { return check(dsm_surfel_map_save_cloud(m_, save_path_name.c_str())); }
     int save_mesh(const std::string &save_path_name) { return check(dsm_surfel_map_save_mesh(m_, save_path_name.c_str())); }
 
+    // the point-cloud topics (publish_*_pointcloud, surfel_map.cpp:1115-1151, 1283-1454): xyzi = 4 floats per point
+    int get_cloud(dsm_cloud_kind kind, std::vector<float> &xyzi) {
+        int32_t n = 0;
+        int rc = dsm_surfel_map_get_cloud(m_, kind, nullptr, 0, &n);
+        while (rc == DSM_E_CAPACITY) {
+            xyzi.resize((size_t)n * 4);
+            rc = dsm_surfel_map_get_cloud(m_, kind, xyzi.data(), n, &n);
+        }
+        if (rc == DSM_OK) xyzi.resize((size_t)n * 4);
+        return check(rc);
+    }
+    // fn(publication) after every fuse, for the kinds in kinds_mask (DSM_CLOUD_BIT(kind) | ...); an empty fn or mask 0: off.
+    // The publication's buffers are valid while fn runs.
+    using PublishFn = std::function<void(const dsm_surfel_map_publication &)>;
+    int set_publish(uint32_t kinds_mask, PublishFn fn) {
+        if (!kinds_mask || !fn) {
+            const int rc = dsm_surfel_map_set_publish(m_, 0, nullptr, nullptr);
+            publish_.reset();
+            return check(rc);
+        }
+        std::unique_ptr<PublishFn> next(new PublishFn(std::move(fn)));
+        const int rc = dsm_surfel_map_set_publish(m_, kinds_mask, &SurfelMap::publish_trampoline, next.get());
+        if (rc == DSM_OK) publish_ = std::move(next);
+        return check(rc);
+    }
+
     dsm_surfel_map *handle() const { return m_; }
     dsm_handle *engine() const { return dsm_surfel_map_engine(m_); }
 
@@ -179,6 +206,7 @@ class SurfelMap {
         o.qx = p.orientation.x; o.qy = p.orientation.y; o.qz = p.orientation.z; o.qw = p.orientation.w;
         return o;
     }
+    static void publish_trampoline(void *user, const dsm_surfel_map_publication *pub) { (*(PublishFn *)user)(*pub); }
     int check(int rc) {
 #if !defined(DSM_NO_EXCEPTIONS) && !defined(DSM_WITH_ROS)
         if (rc != DSM_OK) throw std::runtime_error(std::string("dsm::SurfelMap: ") + dsm_surfel_map_last_error(m_));
@@ -186,6 +214,7 @@ class SurfelMap {
         return rc; // (with DSM_WITH_ROS the callbacks report and carry on, as the reference's void callbacks do)
     }
     dsm_surfel_map *m_ = nullptr;
+    std::unique_ptr<PublishFn> publish_; // the callback: outlives the map (the destructor body destroys the map first)
 };
 
 } // namespace dsm
