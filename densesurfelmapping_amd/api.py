@@ -38,6 +38,7 @@ assert SURFEL_DTYPE.itemsize == 44 and SEED_DTYPE.itemsize == 60
 DSM_FLAG_NO_GRAPH = 1
 DSM_FLAG_UPLOAD_STREAM = 2
 DSM_FLAG_WAVE_STAMPS = 4
+DSM_FLAG_EIGEN33_PRODUCTS = 8  # the reference's 3x3 products in Eigen >= 3.3's order (include/dsm.h)
 DSM_MAX_STAGES = 32
 # dsm_status
 DSM_OK, DSM_E_INVALID, DSM_E_NO_DEVICE, DSM_E_HIP, DSM_E_CAPACITY, DSM_E_STATE = 0, -1, -2, -3, -4, -5

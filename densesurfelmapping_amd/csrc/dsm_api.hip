@@ -407,6 +407,10 @@ struct ReadSlots { // the slots an enqueue call reads, for the lifetime of the c
 
 int fuse_grid_bound(const dsm_handle *h) { return h->hc.cap; }
 
+// DSM_FLAG_EIGEN33_PRODUCTS: the kernels that transform normals run in their Eigen >= 3.3 product-order instantiation.  Fixed
+// at dsm_create, so every graph a handle (or a batch of handles that agree on it) captures holds the right one.
+bool eigen33_products(const dsm_handle *h) { return (h->cfg.flags & DSM_FLAG_EIGEN33_PRODUCTS) != 0; }
+
 // What launch_frame is told about the map size for k_frame_tail (dsm_device.h): graphs are captured once, so they carry
 // the capacity -- but only from the moment the map can be large (map_grows); eager launches pass the running bound.
 int tail_bound(const dsm_handle *h) { return h->tail_large ? h->hc.cap : 0; }
@@ -483,7 +487,7 @@ std::string capture_graph(const std::function<hipError_t(hipStream_t)> &launch, 
 
 int capture(dsm_handle *h, const DeviceCtx &ctx, bool with_compaction, int lo, int hi, hipGraphExec_t *out) {
     if (*out) return DSM_OK;
-    const std::string err = capture_graph([&](hipStream_t st) { return launch_frame(ctx, fuse_grid_bound(h), tail_bound(h), with_compaction, st, nullptr, lo, hi); }, out);
+    const std::string err = capture_graph([&](hipStream_t st) { return launch_frame(ctx, eigen33_products(h), fuse_grid_bound(h), tail_bound(h), with_compaction, st, nullptr, lo, hi); }, out);
     if (!err.empty()) return fail(h, DSM_E_HIP, "%s", err.c_str());
     return DSM_OK;
 }
@@ -552,7 +556,7 @@ int submit_frame(dsm_handle *h, bool with_compaction, const HostFrames *host = n
             if (int rc = upload_host_frames(h, *host, 0, 0, 1, h->stream)) return rc;
         }
         if (eager) {
-            hipError_t e = launch_frame(pp.ctx, h->map_upper, h->map_upper, with_compaction, h->stream, nullptr);
+            hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, nullptr);
             if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
         } else {
             int rc = capture(h, pp.ctx, with_compaction, 0, kNumStages - 1, &pp.g_all[wc]);
@@ -574,7 +578,7 @@ int submit_frame(dsm_handle *h, bool with_compaction, const HostFrames *host = n
             if (int rc = upload_host_frames(h, *host, p, 0, 1, pp.stream)) return rc;
         }
         if (eager) {
-            hipError_t e = launch_frame(pp.ctx, h->map_upper, h->map_upper, with_compaction, pp.stream, nullptr, 0, kLastSuperpixelStage);
+            hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, pp.stream, nullptr, 0, kLastSuperpixelStage);
             if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
         } else {
             int rc = capture(h, pp.ctx, with_compaction, 0, kLastSuperpixelStage, &pp.g_sp);
@@ -584,7 +588,7 @@ int submit_frame(dsm_handle *h, bool with_compaction, const HostFrames *host = n
         HIP_TRY(h, hipEventRecord(pp.ev_sp, pp.stream));
         HIP_TRY(h, hipStreamWaitEvent(h->stream, pp.ev_sp, 0));
         if (eager) {
-            hipError_t e = launch_frame(pp.ctx, h->map_upper, h->map_upper, with_compaction, h->stream, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
+            hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
             if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
         } else {
             int rc = capture(h, pp.ctx, with_compaction, kLastSuperpixelStage + 1, kNumStages - 1, &pp.g_map[wc]);
@@ -655,7 +659,7 @@ int submit_group(dsm_handle *h, const HostFrames *host = nullptr) {
     }
     if (!h->g_group[half]) {
         const std::string err = capture_graph([&](hipStream_t st) {
-            return launch_frame(lead.ctx, fuse_grid_bound(h), tail_bound(h), true, st, nullptr, 0, kLastSuperpixelStage, h->d_pipe_ctxs + p0, G, 4);
+            return launch_frame(lead.ctx, eigen33_products(h), fuse_grid_bound(h), tail_bound(h), true, st, nullptr, 0, kLastSuperpixelStage, h->d_pipe_ctxs + p0, G, 4);
         }, &h->g_group[half]);
         if (!err.empty()) return fail(h, DSM_E_HIP, "%s", err.c_str());
     }
@@ -668,7 +672,7 @@ int submit_group(dsm_handle *h, const HostFrames *host = nullptr) {
         const std::string err = capture_graph([&](hipStream_t st) {
             hipError_t le = hipSuccess;
             for (int j = 0; j < G && le == hipSuccess; j++)
-                le = launch_frame(h->pipe[p0 + j].ctx, fuse_grid_bound(h), tail_bound(h), true, st, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
+                le = launch_frame(h->pipe[p0 + j].ctx, eigen33_products(h), fuse_grid_bound(h), tail_bound(h), true, st, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
             return le;
         }, &h->g_group_map[half]);
         if (!err.empty()) return fail(h, DSM_E_HIP, "%s", err.c_str());
@@ -676,7 +680,7 @@ int submit_group(dsm_handle *h, const HostFrames *host = nullptr) {
             const std::string err2 = capture_graph([&](hipStream_t st) {
                 hipError_t le = hipSuccess;
                 for (int j = 0; j < G && le == hipSuccess; j++)
-                    le = launch_frame(h->pipe[p0 + j].ctx, fuse_grid_bound(h), h->hc.cap, true, st, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
+                    le = launch_frame(h->pipe[p0 + j].ctx, eigen33_products(h), fuse_grid_bound(h), h->hc.cap, true, st, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
                 return le;
             }, &h->g_group_map_large[half]);
             if (!err2.empty()) return fail(h, DSM_E_HIP, "%s", err2.c_str());
@@ -705,7 +709,7 @@ int submit_serial(dsm_handle *h, bool with_compaction, hipEvent_t *ev, int lo, i
         h->params_pending &= ~kSerialBit;
     }
     if (int rc = wait_uploads(h, h->stream, kSerialBit)) return rc;
-    hipError_t e = launch_frame(pp.ctx, h->map_upper, h->map_upper, with_compaction, h->stream, ev, lo, hi);
+    hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, ev, lo, hi);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
     if (h->n_pipe > 1) {
         HIP_TRY(h, hipEventRecord(pp.ev_map, h->stream));
@@ -737,7 +741,7 @@ int submit_part(dsm_handle *h, bool with_compaction, bool map_part) {
     if (int rc = wait_uploads(h, h->stream, kSerialBit)) return rc;
     const int lo = map_part ? kLastSuperpixelStage + 1 : 0, hi = map_part ? kNumStages - 1 : kLastSuperpixelStage;
     if (h->cfg.flags & DSM_FLAG_NO_GRAPH) {
-        hipError_t e = launch_frame(pp.ctx, h->map_upper, h->map_upper, with_compaction, h->stream, nullptr, lo, hi);
+        hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, nullptr, lo, hi);
         if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
     } else {
         hipGraphExec_t *g = map_part ? &pp.g_map[with_compaction ? 1 : 0] : &pp.g_sp_main;
@@ -1820,7 +1824,7 @@ int dsm_frame_cloud(dsm_handle *h, int slot, const double *pose7, void *dst, int
     float4 *out = dst_on_device ? (float4 *)dst : h->d_pub_out;
     const uint8_t *img = (const uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems;
     const float *dep = (const float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
-    hipError_t e = total ? launch_cloud_raw(img, dep, h->hc.pitch, w, hh, p, out, h->stream) : hipSuccess;
+    hipError_t e = total ? launch_cloud_raw(img, dep, h->hc.pitch, w, hh, p, eigen33_products(h), out, h->stream) : hipSuccess;
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "raw cloud launch: %s", hipGetErrorString(e));
     // the call returns when the points are there: nothing enqueued later (an upload into this slot) can overtake the read
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2502,6 +2506,8 @@ int dsm_batch_create(dsm_handle *const *handles, int32_t n, dsm_batch **out) {
         if (h->own_up_stream) return bfail(nullptr, DSM_E_INVALID, "handles of a batch must not use DSM_FLAG_UPLOAD_STREAM (a batch does not wait on a handle's upload stream)");
         if (h->device != handles[0]->device || h->hc.w != handles[0]->hc.w || h->hc.h != handles[0]->hc.h)
             return bfail(nullptr, DSM_E_INVALID, "handles of a batch must share device and image size");
+        if ((h->cfg.flags ^ handles[0]->cfg.flags) & DSM_FLAG_EIGEN33_PRODUCTS)
+            return bfail(nullptr, DSM_E_INVALID, "handles of a batch must agree on DSM_FLAG_EIGEN33_PRODUCTS (one launch runs one product order)");
         if (h->frames_submitted % kParamRing != handles[0]->frames_submitted % kParamRing)
             return bfail(nullptr, DSM_E_STATE, "handles of a batch must have fused the same number of frames (their parameter rings advance together)");
     }
@@ -2590,7 +2596,7 @@ int dsm_batch_replay_enqueue_inv(dsm_batch *b, int32_t n_frames, const int32_t *
         if ((rc = batch_map_grows(b, m))) return rc;
         if (!b->graph) {
             const std::string err = capture_graph([&](hipStream_t st) {
-                return launch_frame(h0->pipe[0].ctx, b->cap_max, b->tail_large ? b->cap_max : 0, true, st, nullptr, 0, kNumStages - 1, b->d_ctxs, (int)b->hs.size());
+                return launch_frame(h0->pipe[0].ctx, eigen33_products(h0), b->cap_max, b->tail_large ? b->cap_max : 0, true, st, nullptr, 0, kNumStages - 1, b->d_ctxs, (int)b->hs.size());
             }, &b->graph);
             if (!err.empty()) return bfail(b, DSM_E_HIP, "%s", err.c_str());
         }
@@ -2629,7 +2635,7 @@ int dsm_batch_replay_timed(dsm_batch *b, int32_t n_frames, const int32_t *slots,
         int rc = batch_stage(b, n_frames, i, 1, slots, ref_idx, poses16);
         if (rc) return rc;
         if ((rc = batch_map_grows(b, 1))) return rc;
-        const hipError_t e = launch_frame(h0->pipe[0].ctx, b->cap_max, b->tail_large ? b->cap_max : 0, true, b->stream, b->ev, 0, kNumStages - 1, b->d_ctxs, n);
+        const hipError_t e = launch_frame(h0->pipe[0].ctx, eigen33_products(h0), b->cap_max, b->tail_large ? b->cap_max : 0, true, b->stream, b->ev, 0, kNumStages - 1, b->d_ctxs, n);
         if (e != hipSuccess) return bfail(b, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
         if ((rc = batch_advance(b, 1))) return rc;
         if ((rc = dsm_batch_synchronize(b))) return rc;

@@ -151,7 +151,9 @@ extern const char *const kStageNames[kNumStages];
 // lanes_from: frames per launch from which the per-seed stages take their lane-per-seed forms (0 = the default for independent
 // handles, kLaneBatch; the frame groups of one sequence pass 4: with other groups' kernels sharing the GPU the lane forms win
 // from four frames on -- profiles/r06_wave_vs_lane.md)
-hipError_t launch_frame(const DeviceCtx &ctx, int map_upper_bound, int tail_map_bound, bool with_compaction,
+// eigen33: the kernels that transform normals (k_seed_finish, k_fuse_surfels) in their Eigen >= 3.3 product-order instantiation
+// (DSM_FLAG_EIGEN33_PRODUCTS of the handle; a captured graph holds the instantiation it was captured with)
+hipError_t launch_frame(const DeviceCtx &ctx, bool eigen33, int map_upper_bound, int tail_map_bound, bool with_compaction,
                         hipStream_t stream, hipEvent_t *ev, int stage_lo = 0, int stage_hi = kNumStages - 1,
                         const DeviceCtx *d_batch = nullptr, int n_batch = 1, int lanes_from = 0);
 
@@ -191,6 +193,8 @@ hipError_t launch_cloud_map(const dsm_surfel *rec, const int32_t *n_ptr, int n_u
 hipError_t launch_cloud_gather(const float4 *src, const int32_t *seg, int n_seg, int total, const int32_t *base_ptr, float4 *out, int cap,
                                hipStream_t st);
 // w * h world points of a pitched frame, column-major (index i * h + j for column i, row j)
-hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, int w, int h, const RawCloudParams &p, float4 *out, hipStream_t st);
+// (eigen33: rotation_R * cam_point in Eigen >= 3.3's product order, DSM_FLAG_EIGEN33_PRODUCTS)
+hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, int w, int h, const RawCloudParams &p, bool eigen33, float4 *out,
+                            hipStream_t st);
 
 } // namespace dsm

@@ -134,7 +134,8 @@ __global__ __launch_bounds__(256) void k_cloud_gather(const float4 *__restrict__
 
 // SM.cpp:1117-1150.  One tile of kRawTileW columns x kRawTileH rows per workgroup: pixels are read along rows (coalesced),
 // the points go through LDS and leave along columns (output index i * h + j: runs of kRawTileH points, 16-byte stores).
-__global__ __launch_bounds__(256) void k_cloud_raw(const uint8_t *__restrict__ img, const float *__restrict__ depth, int pitch, int w, int h,
+// E33: rotation_R * cam_point in Eigen >= 3.3's order (DSM_FLAG_EIGEN33_PRODUCTS).
+template <bool E33 = false> __global__ __launch_bounds__(256) void k_cloud_raw(const uint8_t *__restrict__ img, const float *__restrict__ depth, int pitch, int w, int h,
                                                    const RawCloudParams p, float4 *__restrict__ out) {
     __shared__ float4 s_pt[kRawTileW * (kRawTileH + 1)];
     const int i0 = blockIdx.x * kRawTileW, j0 = blockIdx.y * kRawTileH;
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(256) void k_cloud_raw(const uint8_t *__restrict__ i
                 const float d = depth[(int64_t)j * pitch + i];
                 const float cam[3] = {((float)i - p.cx) * d / p.fx, ((float)j - p.cy) * d / p.fy, d};
                 float o[3];
-                xform_dir(p.rot, cam, o); // rotation_R * cam_point
+                xform_dir_as<E33>(p.rot, cam, o); // rotation_R * cam_point
                 s_pt[il * (kRawTileH + 1) + jl] = make_float4(o[0] + p.t[0], o[1] + p.t[1], o[2] + p.t[2], (float)img[(int64_t)j * pitch + i]);
             }
         }
@@ -180,9 +181,11 @@ hipError_t launch_cloud_gather(const float4 *src, const int32_t *seg, int n_seg,
     return hipGetLastError();
 }
 
-hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, int w, int h, const RawCloudParams &p, float4 *out, hipStream_t st) {
+hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, int w, int h, const RawCloudParams &p, bool eigen33, float4 *out,
+                            hipStream_t st) {
     const dim3 grid((w + kRawTileW - 1) / kRawTileW, (h + kRawTileH - 1) / kRawTileH);
-    hipLaunchKernelGGL(k_cloud_raw, grid, dim3(256), 0, st, img, depth, pitch, w, h, p, out);
+    if (eigen33) hipLaunchKernelGGL(k_cloud_raw<true>, grid, dim3(256), 0, st, img, depth, pitch, w, h, p, out);
+    else hipLaunchKernelGGL(k_cloud_raw<false>, grid, dim3(256), 0, st, img, depth, pitch, w, h, p, out);
     return hipGetLastError();
 }
 

@@ -83,7 +83,8 @@ template <int NT = 256> __device__ __forceinline__ void records_land(float *s_re
     records_land_one(s_rec, p.v2, s1, n_dw, tid + 2 * NT);
 }
 
-template <bool BATCH> __global__ __launch_bounds__(256) void k_fuse_surfels(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch) {
+// E33: the normals' 3x3 products in Eigen >= 3.3's order (DSM_FLAG_EIGEN33_PRODUCTS, dsm_math.h: xform_dir_e33)
+template <bool BATCH, bool E33 = false> __global__ __launch_bounds__(256) void k_fuse_surfels(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch) {
     const BlockOf blk = block_of<BATCH>();
     DeviceCtx batch_ctx;
     if (BATCH) batch_ctx = load_ctx(batch + blk.z);
@@ -134,7 +135,7 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_fuse_surfels(cons
             e.update_times = __float_as_int(r[9]); e.last_update = __float_as_int(r[10]);
             int ui, vi;
             float pc[3], nc[3];
-            FuseOutcome oc = fuse_project(fc, ref_idx, inv, e, ui, vi, pc, nc);
+            FuseOutcome oc = fuse_project<E33>(fc, ref_idx, inv, e, ui, vi, pc, nc);
             if (oc == kFuseNeedPixel) {
                 const unsigned p4 = (unsigned)(__mul24(vi, c->pitch) + ui) << 2; // byte offsets, see ld_off
                 const int sidx = label_at(c->label, p4 >> 2);
@@ -153,7 +154,7 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_fuse_surfels(cons
                     sd.px = ld_off(sf, so + 24); sd.py = ld_off(sf, so + 28); sd.pz = ld_off(sf, so + 32);
                     sd.view_cos = ld_off(sf, so + 36); sd.mean_depth = ld_off(sf, so + 40); sd.mean_intensity = ld_off(sf, so + 44);
                 }
-                oc = fuse_update(fc, ref_idx, pose, e, pc, nc, pix_depth, sd, w1);
+                oc = fuse_update<E33>(fc, ref_idx, pose, e, pc, nc, pix_depth, sd, w1);
                 // the seed's `fused` mark: idempotent, but ~60 surfels fuse into a seed and a byte store into a line that
                 // thousands of lanes are writing is a read-modify-write in L2 -- look first (a stale 0 only repeats the store)
                 if (oc == kFuseFused && c->fused_flag[sidx] == 0) { c->seeds[sidx].fused = 1; c->fused_flag[sidx] = 1; }

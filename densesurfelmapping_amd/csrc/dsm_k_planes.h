@@ -821,8 +821,9 @@ template <int TIER> __device__ __forceinline__ void fit_group(const DeviceCtx *_
 }
 
 // The seed record (FF.cpp:872-914: plane to normal / position / view angle) and the per-seed part of initialize_surfels
-// (FF.cpp:315-361, up to the `fused` test that k_frame_tail applies), one thread per seed.
-template <bool BATCH> __global__ __launch_bounds__(256) void k_seed_finish(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch) {
+// (FF.cpp:315-361, up to the `fused` test that k_frame_tail applies), one thread per seed.  E33: the new surfel's normal in
+// Eigen >= 3.3's product order (DSM_FLAG_EIGEN33_PRODUCTS).
+template <bool BATCH, bool E33 = false> __global__ __launch_bounds__(256) void k_seed_finish(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch) {
     const BlockOf blk = block_of<BATCH>();
     DeviceCtx batch_ctx;
     if (BATCH) batch_ctx = load_ctx(batch + blk.z);
@@ -862,7 +863,7 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_seed_finish(const
     sd.view_cos = out.view_cos; sd.mean_depth = out.mean_depth; sd.mean_intensity = out.mean_intensity;
     const bool ok = seed_spawns(sd, false);
     if (ok) {
-        const Surfel e = spawn_surfel(K, fp.ref_idx, fp.pose, sd);
+        const Surfel e = spawn_surfel<E33>(K, fp.ref_idx, fp.pose, sd);
         dsm_surfel o;
         o.px = e.px; o.py = e.py; o.pz = e.pz; o.nx = e.nx; o.ny = e.ny; o.nz = e.nz;
         o.size = e.size; o.color = e.color; o.weight = e.weight;

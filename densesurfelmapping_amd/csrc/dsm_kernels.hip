@@ -48,8 +48,9 @@ const char *const kStageNames[kNumStages] = {
 
 // d_batch != nullptr: the kernels take their context from d_batch[blockIdx.z], z < n_batch (handles of equal geometry
 // advancing in lockstep: one launch per kernel for all of them); hc is then any one of them (grid sizes).
-hipError_t launch_frame(const DeviceCtx &hc, int map_upper_bound, int tail_map_bound, bool with_compaction,
-                        hipStream_t st, hipEvent_t *ev, int stage_lo, int stage_hi, const DeviceCtx *d_batch, int n_batch, int lanes_from) {
+template <bool E33>
+static hipError_t launch_frame_as(const DeviceCtx &hc, int map_upper_bound, int tail_map_bound, bool with_compaction,
+                                  hipStream_t st, hipEvent_t *ev, int stage_lo, int stage_hi, const DeviceCtx *d_batch, int n_batch, int lanes_from) {
     int stage = 0;
     hipError_t err = hipSuccess;
     const bool batched = d_batch != nullptr;
@@ -120,19 +121,19 @@ hipError_t launch_frame(const DeviceCtx &hc, int map_upper_bound, int tail_map_b
     DSM_MARK();
     hipLaunchStage((k_seed_fit<false, kFitAll>), (k_seed_fit<true, kFitSmall>), dim3((S + kFitSeeds - 1) / kFitSeeds), dim3(64));
     if (batched) hipLaunchStage((k_seed_fit<false, kFitAll>), (k_seed_fit<true, kFitLarge>), dim3(kFitLargeBlocks), dim3(64));
-    hipLaunchStage(k_seed_finish<false>, k_seed_finish<true>, g_seed_thr, dim3(256));
+    hipLaunchStage((k_seed_finish<false, E33>), (k_seed_finish<true, E33>), g_seed_thr, dim3(256));
     DSM_MARK();
     // grid-stride over the map with no more workgroups than the device holds at once (the ones that start late would run
     // all their trips after the others have finished theirs), and fewer than that: see resident_blocks
     int fuse_blocks = (map_upper_bound + 255) / 256;
     if (fuse_blocks < 1) fuse_blocks = 1;
-    const int fuse_cap = batched ? resident_blocks(k_fuse_surfels<true>, 256, kFuseBlocksPerCu) : resident_blocks(k_fuse_surfels<false>, 256, kFuseBlocksPerCu);
+    const int fuse_cap = batched ? resident_blocks(k_fuse_surfels<true, E33>, 256, kFuseBlocksPerCu) : resident_blocks(k_fuse_surfels<false, E33>, 256, kFuseBlocksPerCu);
     if (fuse_blocks > fuse_cap) fuse_blocks = fuse_cap;
     // ... for the launch as a whole: the handles of a batch share the cap (round 6).  Capped per handle, a launch over 32 handles
     // was 24 000 workgroups of one or two trips each, every one of them setting up its context, constants and the two
     // matrices first (80 scalar instructions per wave); +2.6 % on the headline over five alternating runs
     if (batched && nz > 1 && fuse_blocks > (fuse_cap / nz > 1 ? fuse_cap / nz : 1)) fuse_blocks = fuse_cap / nz > 1 ? fuse_cap / nz : 1;
-    hipLaunchStage(k_fuse_surfels<false>, k_fuse_surfels<true>, dim3(fuse_blocks), dim3(256));
+    hipLaunchStage((k_fuse_surfels<false, E33>), (k_fuse_surfels<true, E33>), dim3(fuse_blocks), dim3(256));
     DSM_MARK();
     // (a map that may be beyond the tail's one-workgroup path gets a workgroup per chunk of its hole bitmap on top; they
     // leave at once while the map is small, but starting them is not free -- 8 us per launch for eight handles -- so
@@ -151,6 +152,12 @@ hipError_t launch_frame(const DeviceCtx &hc, int map_upper_bound, int tail_map_b
 #undef DSM_MARK
 #undef hipLaunchStage
     return hipGetLastError();
+}
+
+hipError_t launch_frame(const DeviceCtx &hc, bool eigen33, int map_upper_bound, int tail_map_bound, bool with_compaction,
+                        hipStream_t st, hipEvent_t *ev, int stage_lo, int stage_hi, const DeviceCtx *d_batch, int n_batch, int lanes_from) {
+    return eigen33 ? launch_frame_as<true>(hc, map_upper_bound, tail_map_bound, with_compaction, st, ev, stage_lo, stage_hi, d_batch, n_batch, lanes_from)
+                   : launch_frame_as<false>(hc, map_upper_bound, tail_map_bound, with_compaction, st, ev, stage_lo, stage_hi, d_batch, n_batch, lanes_from);
 }
 
 } // namespace dsm

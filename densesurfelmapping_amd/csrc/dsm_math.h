@@ -613,6 +613,17 @@ DSM_HD void xform_point(const float *m, const float *p, float *o) {
 DSM_HD void xform_dir(const float *m, const float *v, float *o) {
     for (int i = 0; i < 3; i++) o[i] = (m[i] * v[0] + m[4 + i] * v[1]) + m[8 + i] * v[2];
 }
+// The same product in Eigen >= 3.3's order (DSM_FLAG_EIGEN33_PRODUCTS): a fixed 3x3 * 3x1 coefficient is the redux of
+// lhs.row(i) .* rhs, which redux_novec_unroller splits at 1 -- a0*b0 + (a1*b1 + a2*b2).  Eigen 3.2 (xform_dir above)
+// accumulates left to right.
+DSM_HD void xform_dir_e33(const float *m, const float *v, float *o) {
+    for (int i = 0; i < 3; i++) o[i] = m[i] * v[0] + (m[4 + i] * v[1] + m[8 + i] * v[2]);
+}
+// E33: the kernels' compile-time choice between the two
+template <bool E33> DSM_HD void xform_dir_as(const float *m, const float *v, float *o) {
+    if constexpr (E33) xform_dir_e33(m, v, o);
+    else xform_dir(m, v, o);
+}
 DSM_HD float depth_weight(float d) { // FF.cpp:99-102
     double w = 1.0 / (double)d / (double)d;
     return (float)(1.0 < w ? 1.0 : w);
@@ -678,7 +689,7 @@ DSM_HD float fuse_depth_tolerance(const FuseConst &c, float z) {
 
 // Stage 1 of fuse_surfels_kernel (FF.cpp:205-238): pruning and projection.  Returns kFuseNeedPixel
 // with (ui,vi) and camera-frame position/normal when the surfel lands inside the image.
-DSM_HD FuseOutcome fuse_project(const FuseConst &c, int ref_idx, const float *inv, Surfel &e, int &ui, int &vi,
+template <bool E33 = false> DSM_HD FuseOutcome fuse_project(const FuseConst &c, int ref_idx, const float *inv, Surfel &e, int &ui, int &vi,
                                 float pc[3], float nc[3]) {
     if (ref_idx - e.last_update > 5 && e.update_times < 5) {
         e.update_times = 0;
@@ -688,7 +699,7 @@ DSM_HD FuseOutcome fuse_project(const FuseConst &c, int ref_idx, const float *in
     float pw[3] = {e.px, e.py, e.pz}, nw[3] = {e.nx, e.ny, e.nz};
     xform_point(inv, pw, pc);
     if (pc[2] < c.near_d || pc[2] > c.far_d) return kFuseSkip;
-    xform_dir(inv, nw, nc);
+    xform_dir_as<E33>(inv, nw, nc);
     float u = pc[0] * c.k.fx / pc[2] + c.k.cx, v = pc[1] * c.k.fy / pc[2] + c.k.cy; // FF.cpp:85-89
     ui = round_to_pixel(u);
     vi = round_to_pixel(v);
@@ -699,7 +710,7 @@ DSM_HD FuseOutcome fuse_project(const FuseConst &c, int ref_idx, const float *in
 // Stage 2 (FF.cpp:239-311) given the depth at the projected pixel and the seed owning it.
 // (c prepared by fuse_const_prepare; w1 = depth_weight(sd.mean_depth), which k_seed_fit leaves per seed: two double
 // divides that every surfel fusing into the seed would repeat)
-DSM_HD FuseOutcome fuse_update(const FuseConst &c, int ref_idx, const float *pose, Surfel &e, const float pc[3],
+template <bool E33 = false> DSM_HD FuseOutcome fuse_update(const FuseConst &c, int ref_idx, const float *pose, Surfel &e, const float pc[3],
                                const float nc[3], float pix_depth, const SeedView &sd, float w1) {
     if ((double)pc[2] < (double)pix_depth - 1.0) {
         e.update_times = 0;
@@ -728,7 +739,7 @@ DSM_HD FuseOutcome fuse_update(const FuseConst &c, int ref_idx, const float *pos
     fn[1] = fn[1] / len;
     fn[2] = fn[2] / len;
     float fw[3];
-    xform_dir(pose, fn, fw);
+    xform_dir_as<E33>(pose, fn, fw);
     e.px = fpx; e.py = fpy; e.pz = fpz;
     e.nx = fw[0]; e.ny = fw[1]; e.nz = fw[2];
     e.weight = ws;
@@ -748,10 +759,10 @@ DSM_HD bool seed_spawns(const SeedView &sd, bool fused) {
     if (sd.nx == 0 && sd.ny == 0 && sd.nz == 0) return false;
     return true;
 }
-DSM_HD Surfel spawn_surfel(const Intrinsics &k, int ref_idx, const float *pose, const SeedView &sd) {
+template <bool E33 = false> DSM_HD Surfel spawn_surfel(const Intrinsics &k, int ref_idx, const float *pose, const SeedView &sd) {
     float pc[3] = {sd.px, sd.py, sd.pz}, nc[3] = {sd.nx, sd.ny, sd.nz}, pw[3], nw[3];
     xform_point(pose, pc, pw);
-    xform_dir(pose, nc, nw);
+    xform_dir_as<E33>(pose, nc, nw);
     float cam_f = camera_focal(k);
     Surfel e;
     e.px = pw[0]; e.py = pw[1]; e.pz = pw[2];

@@ -410,8 +410,15 @@ extern "C" {
 int dsm_surfel_map_create(const dsm_surfel_map_config *cfg, dsm_surfel_map **out) {
     if (!cfg || !out) return DSM_E_INVALID;
     *out = nullptr;
-    if (cfg->struct_size != sizeof(dsm_surfel_map_config)) return DSM_E_INVALID; // built against another header
+    // built against another header: this one, or the one before engine_flags (its fields are a prefix of these, engine_flags 0)
+    if (cfg->struct_size != sizeof(dsm_surfel_map_config) && cfg->struct_size != offsetof(dsm_surfel_map_config, engine_flags))
+        return DSM_E_INVALID;
+    dsm_surfel_map_config c = {};
+    memcpy(&c, cfg, cfg->struct_size);
+    c.struct_size = sizeof(dsm_surfel_map_config);
+    cfg = &c;
     if (cfg->drift_free_poses < 1) return DSM_E_INVALID;
+    if (cfg->engine_flags & ~DSM_FLAG_EIGEN33_PRODUCTS) return DSM_E_INVALID;
     dsm_surfel_map *m = new dsm_surfel_map();
     m->cfg = *cfg;
     dsm_config ec;
@@ -421,6 +428,7 @@ int dsm_surfel_map_create(const dsm_surfel_map_config *cfg, dsm_surfel_map **out
     ec.surfel_capacity = cfg->surfel_capacity;
     ec.pipeline_depth = 1; // live callbacks: one frame at a time,
     ec.flags |= DSM_FLAG_UPLOAD_STREAM; // the next frame goes up while this one is fused
+    ec.flags |= cfg->engine_flags;
     int rc = dsm_create(&ec, &m->engine); // SurfelMap::SurfelMap -> fusion_functions.initialize (:53)
     if (rc == DSM_OK) rc = dsm_map_upload(m->engine, nullptr, 0);
     if (rc != DSM_OK) {

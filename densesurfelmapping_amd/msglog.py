@@ -14,6 +14,9 @@ A log holds, in publication order, exactly what the node's three subscribers wou
 tests/cpp/node_replay_test.cpp reads the same format through include/dsm_surfel_map.hpp.
 
     python -m densesurfelmapping_amd.msglog LOG --save-cloud map.PCD --save-mesh map_mesh.PLY
+
+--eigen-products 3.3 fuses with the 3x3 products in the order of a reference built against Eigen >= 3.3
+(DSM_FLAG_EIGEN33_PRODUCTS); the default, 3.2, is the order of Eigen 3.2, as without the flag.
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ import json
 
 import numpy as np
 
-from . import synth
+from . import api, synth
 
 _KIND = {"image": 0, "depth": 1, "orb": 2}
 
@@ -81,11 +84,15 @@ def read_log(path):
     return cam, dfp, events()
 
 
-def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0):
+EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-products -> SurfelMap(engine_flags=...)
+
+
+def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2"):
     """Feed a log to a SurfelMap on the GPU; returns a summary dict."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
-    node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity)
+    node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity,
+                                engine_flags=EIGEN_PRODUCTS[eigen_products])
     n = 0
     for ev in events:
         node.feed(ev)
@@ -106,12 +113,14 @@ def main():
     ap.add_argument("--save-cloud", help="ASCII PCD (SurfelMap::save_cloud)")
     ap.add_argument("--save-mesh", help="ASCII PLY hexagon mesh (SurfelMap::save_mesh)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
+                    help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
     ap.add_argument("--synth", type=int, metavar="N", help="first write LOG: N frames of the synthetic circuit at 1226x370")
     args = ap.parse_args()
     if args.synth:
         cam = synth.KITTI_1226
         write_log(args.log, cam, 10, synth.node_messages(cam, synth.Scene(), args.synth, lap=120))
-    print(json.dumps(replay(args.log, args.save_cloud, args.save_mesh, device=args.device)))
+    print(json.dumps(replay(args.log, args.save_cloud, args.save_mesh, device=args.device, eigen_products=args.eigen_products)))
 
 
 if __name__ == "__main__":

@@ -51,7 +51,7 @@ class _MapConfig(C.Structure):
                 ("cam_fx", C.c_float), ("cam_fy", C.c_float), ("cam_cx", C.c_float), ("cam_cy", C.c_float),
                 ("fuse_far_distence", C.c_float), ("fuse_near_distence", C.c_float),
                 ("drift_free_poses", C.c_int32), ("rgbd", C.c_int32), ("device", C.c_int32),
-                ("surfel_capacity", C.c_int32), ("max_buffered_frames", C.c_int32)]
+                ("surfel_capacity", C.c_int32), ("max_buffered_frames", C.c_int32), ("engine_flags", C.c_uint32)]
 
 
 def _bind(lib):
@@ -98,12 +98,13 @@ class SurfelMap:
     (surfel_map.cpp:13-28; launch defaults of kitti_orb.launch: drift_free_poses = 10)."""
 
     def __init__(self, cam, drift_free_poses: int = 10, device: int = 0, surfel_capacity: int = 0,
-                 max_buffered_frames: int = 0, _library=None):
+                 max_buffered_frames: int = 0, engine_flags: int = 0, _library=None):
+        # engine_flags: 0 or api.DSM_FLAG_EIGEN33_PRODUCTS (a reference built against Eigen >= 3.3, include/dsm_surfel_map.h)
         # _library: tests bind the same class to their CPU stand-in build of the host logic (tests/node_hostemu.cpp)
         self._lib = _bind(_library if _library is not None else api.load_library())
         self.cam = cam
         cfg = _MapConfig(C.sizeof(_MapConfig), cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy, cam.far, cam.near, drift_free_poses,
-                         1 if cam.rgbd else 0, device, surfel_capacity, max_buffered_frames)
+                         1 if cam.rgbd else 0, device, surfel_capacity, max_buffered_frames, engine_flags)
         h = _vp()
         rc = self._lib.dsm_surfel_map_create(C.byref(cfg), C.byref(h))
         if rc != 0:

@@ -114,6 +114,16 @@ typedef struct dsm_config {
                                    its kernels and dsm_create REFUSES the flag (DSM_E_INVALID): a profiling run on the wrong
                                    library fails at once instead of reading an empty buffer later */
 
+#define DSM_FLAG_EIGEN33_PRODUCTS 8u /* evaluate the reference's 3x3 * 3x1 products -- the camera-frame normal of every surfel
+                                        (FF.cpp:228, its delete test at :265-268), the normal of every new and every fused
+                                        surfel (:296, :341) and dsm_frame_cloud's rotation_R * cam_point (SM.cpp:1139) -- in
+                                        the order Eigen 3.3 / 3.4 give them, a0*b0 + (a1*b1 + a2*b2), instead of Eigen 3.2's
+                                        (a0*b0 + a1*b1) + a2*b2.  Set it to match a reference built against Eigen >= 3.3 (what
+                                        Ubuntu 18.04 and later ship) byte for byte; leave it clear for Eigen 3.2 (the default).
+                                        The other products (the 4x4 ones, and dsm_warp_surfels' dynamic
+                                        MatrixXf products of SM.cpp:724, 774) are unchanged: DESIGN.md section 6.  Handles of
+                                        one batch must agree on it. */
+
 typedef struct dsm_handle dsm_handle;
 
 /* Fill cfg with the driving constant set (fusion_functions.h:13-16) or, if rgbd != 0, the
@@ -322,6 +332,8 @@ int dsm_stream(dsm_handle *h, void **hip_stream);
  * behind the batch when it is next used, by every per-handle call and by dsm_batch_synchronize; a batch call itself touches
  * no stream but the batch's own -- the handles' streams share hardware queues with the other batches). ---- */
 typedef struct dsm_batch dsm_batch;
+/* the handles: pipeline_depth 1, no DSM_FLAG_UPLOAD_STREAM, one device and image size, the same number of frames fused, and
+ * all or none with DSM_FLAG_EIGEN33_PRODUCTS; otherwise DSM_E_INVALID (DSM_E_STATE for the frame count) */
 int dsm_batch_create(dsm_handle *const *handles, int32_t n, dsm_batch **out);
 void dsm_batch_destroy(dsm_batch *b);
 const char *dsm_batch_last_error(const dsm_batch *b);

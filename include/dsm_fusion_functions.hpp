@@ -16,6 +16,11 @@
 // neither OpenCV nor Eigen.  SurfelElement must have the 44-byte layout of elements.h:22-31.
 // Errors: the reference returns void and prints; these methods throw std::runtime_error with the
 // library's message (define DSM_NO_EXCEPTIONS to get the int status instead).
+//
+// Eigen product order (DSM_FLAG_EIGEN33_PRODUCTS, include/dsm.h): the reference's 3x3 * 3x1 products round differently
+// under Eigen 3.2 and Eigen >= 3.3.  The engine follows Eigen 3.2 unless asked otherwise: set_engine_flags() before
+// initialize(), or define DSM_MATCH_CALLER_EIGEN and include Eigen before this header -- the default flags then follow the
+// caller's own EIGEN_WORLD_VERSION / EIGEN_MAJOR_VERSION (and it is an error to define it without them).
 #ifndef DSM_FUSION_FUNCTIONS_HPP
 #define DSM_FUSION_FUNCTIONS_HPP
 
@@ -29,6 +34,21 @@
 #include "dsm.h"
 
 namespace dsm {
+
+// The engine flag that reproduces the products of a reference built against Eigen `world`.`major`
+constexpr uint32_t eigen_products_flag(int world, int major) {
+    return (world > 3 || (world == 3 && major >= 3)) ? DSM_FLAG_EIGEN33_PRODUCTS : 0u;
+}
+
+// The flags FusionFunctions and SurfelMap start with: none, or with DSM_MATCH_CALLER_EIGEN the caller's own Eigen's
+#ifdef DSM_MATCH_CALLER_EIGEN
+#if !defined(EIGEN_WORLD_VERSION) || !defined(EIGEN_MAJOR_VERSION)
+#error "DSM_MATCH_CALLER_EIGEN: include <Eigen/Core> (or any Eigen header) before the dsm headers"
+#endif
+constexpr uint32_t kDefaultEngineFlags = eigen_products_flag(EIGEN_WORLD_VERSION, EIGEN_MAJOR_VERSION);
+#else
+constexpr uint32_t kDefaultEngineFlags = 0u;
+#endif
 
 namespace detail {
 // pose.inverse() with the CALLER's matrix library when the pose type has one (Eigen::Matrix4f in the reference,
@@ -51,6 +71,10 @@ class FusionFunctions {
     FusionFunctions &operator=(const FusionFunctions &) = delete;
     ~FusionFunctions() { dsm_destroy(h_); }
 
+    // DSM_FLAG_* for dsm_config.flags of the next initialize() (DSM_FLAG_EIGEN33_PRODUCTS: Eigen >= 3.3's product order)
+    void set_engine_flags(uint32_t flags) { engine_flags_ = flags; }
+    uint32_t engine_flags() const { return engine_flags_; }
+
     // fusion_functions.h:84-87.  rgbd selects the constant set of fusion_functions.h:17-21.
     int initialize(int width, int height, float fx, float fy, float cx, float cy, float far_dist, float near_dist,
                    bool rgbd = false, int device = 0, int surfel_capacity = 0) {
@@ -60,6 +84,7 @@ class FusionFunctions {
         dsm_config_init(&cfg, width, height, fx, fy, cx, cy, far_dist, near_dist, rgbd ? 1 : 0);
         cfg.device = device;
         cfg.surfel_capacity = surfel_capacity;
+        cfg.flags |= engine_flags_;
         n_seed_ = (width / 8) * (height / 8);
         return check(dsm_create(&cfg, &h_), nullptr);
     }
@@ -112,6 +137,7 @@ class FusionFunctions {
     }
     dsm_handle *h_ = nullptr;
     int n_seed_ = 0;
+    uint32_t engine_flags_ = kDefaultEngineFlags;
 };
 
 } // namespace dsm

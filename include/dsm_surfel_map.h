@@ -61,6 +61,9 @@ typedef struct dsm_surfel_map_config {
                                     beyond; 0 = 5000, the depth of the reference's subscriber queues (ros_node.cpp:24-25;
                                     its own lists behind them are unbounded, surfel_map.h:96-97); < 0 = unbounded.  Only the
                                     first 256 waiting frames of each kind sit in page-locked memory, the rest is pageable */
+    uint32_t engine_flags;   /* 0 or DSM_FLAG_EIGEN33_PRODUCTS (include/dsm.h): the engine's 3x3 products, and with them the
+                                RAW cloud, in Eigen >= 3.3's order; any other bit is refused (DSM_E_INVALID).  A caller built
+                                against the header before this field (struct_size ending at max_buffered_frames) reads as 0 */
 } dsm_surfel_map_config;
 
 int dsm_surfel_map_create(const dsm_surfel_map_config *cfg, dsm_surfel_map **out); /* SurfelMap::SurfelMap */

@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "dsm_fusion_functions.hpp" // kDefaultEngineFlags
 #include "dsm_surfel_map.h"
 
 namespace dsm {
@@ -103,6 +104,7 @@ class SurfelMap {
         int device = 0;
         int surfel_capacity = 0;
         int max_buffered_frames = 0; // frames kept waiting for a pose: 0 = 5000 (ros_node.cpp:24-25), < 0 = unbounded (dsm_surfel_map.h)
+        uint32_t engine_flags = kDefaultEngineFlags; // 0 or DSM_FLAG_EIGEN33_PRODUCTS (dsm_fusion_functions.hpp)
     };
 
     explicit SurfelMap(const Params &p) {
@@ -121,6 +123,7 @@ class SurfelMap {
         c.device = p.device;
         c.surfel_capacity = p.surfel_capacity;
         c.max_buffered_frames = p.max_buffered_frames;
+        c.engine_flags = p.engine_flags;
         const int rc = dsm_surfel_map_create(&c, &m_);
         if (rc != DSM_OK) {
             m_ = nullptr;
