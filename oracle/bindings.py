@@ -90,21 +90,32 @@ class _Base:
     def _call(self, name, *a):
         return getattr(self.lib, self.prefix + name)(self.h_, *a)
 
-    # FusionFunctions::fuse_initialize_map (FF.cpp:30-83)
-    def fuse_initialize_map(self, ref_idx, image, depth, pose, local):
+    def _inv_args(self, name, inv_pose):
+        """(entry point, extra leading argument) for the caller's own inverse: inv_pose None -> the closed form; else 16
+        floats, column-major (the layout of the product's *_inv entry points), used as given.  PortOracle only."""
+        if inv_pose is None:
+            return name, (), None
+        if self.prefix != "dsmo_":
+            raise TypeError(f"{type(self).__name__} takes no caller inverse (only PortOracle restates the *_inv entry points)")
+        inv = np.ascontiguousarray(np.asarray(inv_pose, np.float32).reshape(16))
+        return name + "_inv", (_ptr(inv),), inv
+
+    # FusionFunctions::fuse_initialize_map (FF.cpp:30-83); inv_pose: the caller's pose.inverse() (FF.cpp:59), column-major
+    def fuse_initialize_map(self, ref_idx, image, depth, pose, local, inv_pose=None):
         image = np.ascontiguousarray(image, np.uint8)
         depth = np.ascontiguousarray(depth, np.float32)
         pose_cm = np.ascontiguousarray(np.asarray(pose, np.float32).T).ravel()  # column-major
         local = np.ascontiguousarray(local, SURFEL_DTYPE).copy()
         fresh = np.zeros(self.S, SURFEL_DTYPE)
         n_new = C.c_int(0)
-        rc = self._call("fuse_initialize_map", ref_idx, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0],
-                        _ptr(pose_cm), _ptr(local), len(local), _ptr(fresh), self.S, C.byref(n_new))
+        name, inv, _keep = self._inv_args("fuse_initialize_map", inv_pose)
+        rc = self._call(name, ref_idx, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0],
+                        _ptr(pose_cm), *inv, _ptr(local), len(local), _ptr(fresh), self.S, C.byref(n_new))
         assert rc == 0
         return local, fresh[: n_new.value].copy()
 
     # SurfelMap::fuse_map (SM.cpp:1060-1113)
-    def fuse_map(self, ref_idx, image, depth, pose, local):
+    def fuse_map(self, ref_idx, image, depth, pose, local, inv_pose=None):
         image = np.ascontiguousarray(image, np.uint8)
         depth = np.ascontiguousarray(depth, np.float32)
         pose_cm = np.ascontiguousarray(np.asarray(pose, np.float32).T).ravel()
@@ -113,8 +124,9 @@ class _Base:
         buf[: len(local)] = local
         n_local = C.c_int(len(local))
         n_new = C.c_int(0)
-        rc = self._call("fuse_map", ref_idx, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0],
-                        _ptr(pose_cm), _ptr(buf), C.byref(n_local), cap, C.byref(n_new))
+        name, inv, _keep = self._inv_args("fuse_map", inv_pose)
+        rc = self._call(name, ref_idx, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0],
+                        _ptr(pose_cm), *inv, _ptr(buf), C.byref(n_local), cap, C.byref(n_new))
         assert rc == 0
         return buf[: n_local.value].copy(), n_new.value
 
@@ -187,6 +199,11 @@ class PortOracle(_Base):
     def __init__(self, cam, threads=1):
         lib = C.CDLL(os.path.join(HERE, "liboracle_port.so"))
         lib.dsmo_set_constants.argtypes = [_vp, C.c_double, C.c_double, C.c_double, C.c_double]
+        lib.dsmo_fuse_initialize_map_inv.restype = C.c_int
+        lib.dsmo_fuse_initialize_map_inv.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int, _vp,
+                                                     C.c_int, _vp]
+        lib.dsmo_fuse_map_inv.restype = C.c_int
+        lib.dsmo_fuse_map_inv.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_int, _vp]
         super().__init__(lib, cam)
         if cam.rgbd:
             lib.dsmo_set_constants(self.h_, 0.05, 0.08, 1.0, 0.05)  # fusion_functions.h:17-21

@@ -489,10 +489,18 @@ static int spawn_surfels(dsmo_ctx *c, int ref_idx, const float *pose, dsmo_surfe
 int dsmo_fuse_initialize_map(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
                              size_t depth_step, const float *pose16, dsmo_surfel *local, int n_local,
                              dsmo_surfel *new_out, int new_cap, int *n_new) {
+    return dsmo_fuse_initialize_map_inv(c, ref_idx, img, img_step, depth, depth_step, pose16, NULL, local, n_local, new_out,
+                                        new_cap, n_new);
+}
+
+int dsmo_fuse_initialize_map_inv(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
+                                 size_t depth_step, const float *pose16, const float *inv16, dsmo_surfel *local, int n_local,
+                                 dsmo_surfel *new_out, int new_cap, int *n_new) {
     float inv[16];
     dsmo_set_frame(c, img, img_step, depth, depth_step);
     dsmo_generate_super_pixels(c);
-    inverse4f(pose16, inv); /* FF.cpp:59 */
+    if (inv16) memcpy(inv, inv16, sizeof inv); /* the caller's own pose.inverse(), used as given (NaN, inf, singular) */
+    else inverse4f(pose16, inv); /* FF.cpp:59 */
     fuse_local(c, ref_idx, pose16, inv, local, n_local);
     int k = spawn_surfels(c, ref_idx, pose16, new_out, new_cap);
     if (k < 0) return -1;
@@ -522,10 +530,16 @@ int dsmo_compact(dsmo_surfel *local, int *n_local, int cap, const dsmo_surfel *f
 
 int dsmo_fuse_map(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
                   size_t depth_step, const float *pose16, dsmo_surfel *local, int *n_local, int cap, int *n_new) {
+    return dsmo_fuse_map_inv(c, ref_idx, img, img_step, depth, depth_step, pose16, NULL, local, n_local, cap, n_new);
+}
+
+int dsmo_fuse_map_inv(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
+                      size_t depth_step, const float *pose16, const float *inv16, dsmo_surfel *local, int *n_local, int cap,
+                      int *n_new) {
     dsmo_surfel *fresh = (dsmo_surfel *)malloc(sizeof(dsmo_surfel) * (size_t)c->n_seed);
     int k = 0;
-    int rc = dsmo_fuse_initialize_map(c, ref_idx, img, img_step, depth, depth_step, pose16, local, *n_local, fresh,
-                                      c->n_seed, &k);
+    int rc = dsmo_fuse_initialize_map_inv(c, ref_idx, img, img_step, depth, depth_step, pose16, inv16, local, *n_local, fresh,
+                                          c->n_seed, &k);
     if (rc == 0) rc = dsmo_compact(local, n_local, cap, fresh, k);
     free(fresh);
     *n_new = k;

@@ -56,6 +56,14 @@ int dsmo_fuse_initialize_map(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_
                              dsmo_surfel *new_out, int new_cap, int *n_new);
 int dsmo_fuse_map(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
                   size_t depth_step, const float *pose16, dsmo_surfel *local, int *n_local, int cap, int *n_new);
+/* the same with the caller's own world -> camera matrix (column-major inv16: what pose.inverse() of ITS matrix library
+ * returned, FF.cpp:59), used as given; NULL = the closed form above, exactly dsmo_fuse_initialize_map / dsmo_fuse_map */
+int dsmo_fuse_initialize_map_inv(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
+                                 size_t depth_step, const float *pose16, const float *inv16, dsmo_surfel *local, int n_local,
+                                 dsmo_surfel *new_out, int new_cap, int *n_new);
+int dsmo_fuse_map_inv(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
+                      size_t depth_step, const float *pose16, const float *inv16, dsmo_surfel *local, int *n_local, int cap,
+                      int *n_new);
 /* surfel_map.cpp:1077-1109 on its own */
 int dsmo_compact(dsmo_surfel *local, int *n_local, int cap, const dsmo_surfel *fresh, int n_fresh);
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, fields_equal
+import inverse_cases
 
 
 @pytest.fixture(scope="module")
@@ -1155,6 +1156,65 @@ def test_inverse_pose_golden_is_the_perturbed_reference_tu(oracle_built):
         assert (k, len(local)) == (int(g["n_new"][t]), int(g["n_local"][t])), t
     assert local.tobytes() == g["final_map"].tobytes()
     ref.lib.dsmref_set_eigen_perturb(None, None)
+
+
+def test_port_takes_the_callers_inverse(oracle_built):
+    """The C restatement's *_inv form (dsmo_fuse_map_inv: the caller's own pose.inverse(), FF.cpp:59, used as given) -- what
+    tests/test_gpu_inverse.py takes as its oracle for arbitrary inverses.  Everywhere: fed the recorded inverses of
+    tests/golden/inv_pose_perturbed.npz it reproduces that fixture (per-frame counts, final map) byte for byte, and with NULL
+    it is the closed form.  Where the reference's sources exist: it equals the reference's own TU with Matrix4f::inverse()
+    moved by three more ulp patterns (libdsm_ref_serial_perturb.so), fed the inverse that TU reports for each frame, at TINY
+    and at 166x103 (the size with a ragged superpixel border), per-frame counts and map bytes."""
+    import ctypes
+    from densesurfelmapping_amd import synth
+    from oracle.bindings import SURFEL_DTYPE, PortOracle
+    g = np.load(os.path.join(ROOT, "tests", "golden", "inv_pose_perturbed.npz"))
+    cam, scene, n = getattr(synth, str(g["camera"])), synth.Scene(seed=int(g["scene_seed"])), int(g["frames"])
+    orc, plain = PortOracle(cam), PortOracle(cam)
+    lo, lp, lc = (np.zeros(0, SURFEL_DTYPE) for _ in range(3))
+    cf = PortOracle(cam)
+    for t, img, dep, pose, ridx in synth.sequence(cam, scene, n):
+        lo, k = orc.fuse_map(ridx, img, dep, pose, lo, inv_pose=g["inv_poses_cm"][t])
+        assert (k, len(lo)) == (int(g["n_new"][t]), int(g["n_local"][t])), t
+        lp, _ = plain.fuse_map(ridx, img, dep, pose, lp)
+        lc, _ = cf.fuse_map(ridx, img, dep, pose, lc, inv_pose=inverse_cases.closed_form(pose))
+    assert lo.tobytes() == g["final_map"].tobytes()
+    assert lc.tobytes() == lp.tobytes()  # (the closed form handed in is the NULL case)
+    assert lp.tobytes() != lo.tobytes() and len(lp) == int(g["unperturbed_final_count"])
+    if not os.path.isdir("/root/reference/surfel_fusion/src"):
+        return
+    subprocess.run(["make", "-s", "-C", oracle_built, "perturb"], check=True)
+    from oracle.bindings import RefOracle
+    rng = np.random.default_rng(20261015)
+    patterns = [inverse_cases.ulp_pattern(rng) for _ in range(3)]
+    for camera in ("TINY", "TINY_RAGGED"):
+        cam = getattr(synth, camera)
+        frames = list(synth.sequence(cam, synth.Scene(seed=777), 30))
+        base = PortOracle(cam)
+        lb = np.zeros(0, SURFEL_DTYPE)
+        for t, img, dep, pose, ridx in frames:
+            lb, _ = base.fuse_map(ridx, img, dep, pose, lb)
+        for k_pat, ulps in enumerate(patterns):
+            ref = RefOracle(cam, kind="serial_perturb")
+            ref.lib.dsmref_set_eigen_perturb.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            ref.lib.dsmref_inverse4f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            ulps = np.ascontiguousarray(ulps, np.int32)
+            ref.lib.dsmref_set_eigen_perturb(ulps.ctypes.data_as(ctypes.c_void_p), None)
+            orc = PortOracle(cam)
+            lr, lo = np.zeros(0, SURFEL_DTYPE), np.zeros(0, SURFEL_DTYPE)
+            try:
+                for t, img, dep, pose, ridx in frames:
+                    pose_cm = inverse_cases.colmajor(pose)
+                    inv = np.zeros(16, np.float32)
+                    ref.lib.dsmref_inverse4f(pose_cm.ctypes.data_as(ctypes.c_void_p), inv.ctypes.data_as(ctypes.c_void_p))
+                    assert inv.tobytes() == inverse_cases.ulp_move(inverse_cases.closed_form(pose), ulps).tobytes(), (camera, k_pat, t)
+                    lr, kr = ref.fuse_map(ridx, img, dep, pose, lr)
+                    lo, ko = orc.fuse_map(ridx, img, dep, pose, lo, inv_pose=inv)
+                    assert (ko, len(lo)) == (kr, len(lr)), (camera, k_pat, t)
+                    assert lo.tobytes() == lr.tobytes(), (camera, k_pat, t)
+            finally:
+                ref.lib.dsmref_set_eigen_perturb(None, None)
+            assert lo.tobytes() != lb.tobytes(), f"{camera} pattern {k_pat} changes nothing: the case does not exercise the inverse"
 
 
 def test_shipped_sources_carry_no_hooks():
