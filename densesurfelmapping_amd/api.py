@@ -60,7 +60,28 @@ ABI_SYMBOLS = (
     "dsm_get_labels", "dsm_get_seeds", "dsm_seed_count", "dsm_replay_timed", "dsm_debug_wave_stamps", "dsm_debug_set_fit_small_cap", "dsm_debug_tier_counts", "dsm_debug_dropin_stats",
     "dsm_debug_run_stages", "dsm_debug_get_label_buffer", "dsm_debug_set_label_buffer", "dsm_debug_get_seed_state",
     "dsm_debug_set_seed_state",
+    # sensor-native uint16 depth, converted on the device
+    "dsm_frame_upload_u16", "dsm_frame_upload_device_u16", "dsm_frame_upload_async_u16", "dsm_frames_upload_async_u16",
+    "dsm_replay_enqueue_host_u16", "dsm_host_pack_frames_u16", "dsm_debug_get_frame",
 )
+
+# dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
+DEPTH_U16_DIVIDE, DEPTH_U16_MULTIPLY = 0, 1
+_DEPTH_OPS = {"divide": DEPTH_U16_DIVIDE, "multiply": DEPTH_U16_MULTIPLY}
+
+
+def depth_op_code(op) -> int:
+    """'divide' / 'multiply' (or the DEPTH_U16_* code itself) -> the code; anything else is passed on for the library to refuse"""
+    return _DEPTH_OPS[op] if isinstance(op, str) else int(op)
+
+
+def depth_from_u16(u, scale, op="divide") -> np.ndarray:
+    """Host reference of the device conversion: 'divide' = u16.astype(float32) / float32(scale) (TUM PNGs: 5000, KITTI-style: 256),
+    'multiply' = u16.astype(float32) * float32(scale) (ROS depth_image_proc's depth * 0.001f); 0 stays 0."""
+    u = np.asarray(u, np.uint16).astype(np.float32)
+    s = np.float32(scale)
+    with np.errstate(over="ignore"):
+        return (u / s if depth_op_code(op) == DEPTH_U16_DIVIDE else u * s).astype(np.float32)
 
 
 # dsm_cloud_compose's map part (include/dsm.h dsm_cloud_select)
@@ -174,6 +195,14 @@ def load_library():
     lib.dsm_batch_replay_enqueue.argtypes = [_vp, C.c_int32, _vp, _vp, _vp]
     lib.dsm_batch_synchronize.argtypes = [_vp]
     lib.dsm_batch_replay_timed.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, C.POINTER(_StageTimes)]
+    lib.dsm_frame_upload_u16.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_float, C.c_int32]
+    lib.dsm_frame_upload_device_u16.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_float, C.c_int32]
+    lib.dsm_frame_upload_async_u16.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_float, C.c_int32]
+    lib.dsm_frames_upload_async_u16.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_float, C.c_int32]
+    lib.dsm_replay_enqueue_host_u16.argtypes = [_vp, C.c_int32, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp,
+                                                C.c_float, C.c_int32]
+    lib.dsm_host_pack_frames_u16.argtypes = [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t]
+    lib.dsm_debug_get_frame.argtypes = [_vp, C.c_int, _vp, _vp]
     _lib = lib
     return lib
 
@@ -442,8 +471,52 @@ class FusionFunctions:
         one transfer per plane for all of them -- of a block with tight rows too (PinnedFrames(..., tight=True))"""
         assert 0 <= first and first + n <= pinned.n and (pinned.h, pinned.w) == (self.height, self.width) and pinned.pitch in (self.frame_pitch(), self.width)
         img, dep = pinned.image(first), pinned.depth(first)
+        if pinned.depth_u16 is not None:  # uint16 depth: converted on the device (PinnedFrames(..., depth_u16=(scale, op)))
+            self._check(self._lib.dsm_frames_upload_async_u16(self._h, slot0, n, _ptr(img), img.strides[0], pinned.pitch * pinned.h,
+                                                              _ptr(dep), dep.strides[0], pinned.pitch * pinned.h * 2, *pinned.depth_u16_args))
+            return
         self._check(self._lib.dsm_frames_upload_async(self._h, slot0, n, _ptr(img), img.strides[0], pinned.pitch * pinned.h,
                                                       _ptr(dep), dep.strides[0], pinned.pitch * pinned.h * 4))
+
+    def _frame_args_u16(self, image, depth):
+        image = np.asarray(image)
+        depth = np.asarray(depth)
+        if image.dtype != np.uint8 or depth.dtype != np.uint16:
+            raise TypeError("image must be uint8 (CV_8UC1) and depth uint16 (CV_16UC1)")
+        if image.shape != (self.height, self.width) or depth.shape != (self.height, self.width):
+            raise ValueError("image/depth shape does not match initialize()")
+        if image.strides[1] != 1 or image.strides[0] < self.width:
+            image = np.ascontiguousarray(image)
+        if depth.strides[1] != 2 or depth.strides[0] < self.width * 2:
+            depth = np.ascontiguousarray(depth)
+        return image, depth
+
+    def frame_upload_u16(self, slot, image, depth, scale, op="divide"):
+        """dsm_frame_upload_u16: uint16 depth converted to metres on the device (depth_from_u16(depth, scale, op) bit for bit)"""
+        image, depth = self._frame_args_u16(image, depth)
+        self._check(self._lib.dsm_frame_upload_u16(self._h, slot, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0],
+                                                   scale, depth_op_code(op)))
+
+    def frame_upload_device_u16(self, slot, image_ptr, img_step, depth_ptr, depth_step, scale, op="divide"):
+        self._check(self._lib.dsm_frame_upload_device_u16(self._h, slot, _vp(image_ptr), img_step, _vp(depth_ptr), depth_step,
+                                                          scale, depth_op_code(op)))
+
+    def frame_upload_async_u16(self, slot, image, depth, scale, op="divide"):
+        """dsm_frame_upload_async_u16: views of PAGE-LOCKED memory (PinnedFrames(..., depth_u16=...)), untouched until
+        frame_uploads_wait()"""
+        if image.dtype != np.uint8 or depth.dtype != np.uint16 or image.shape != (self.height, self.width) or depth.shape != image.shape:
+            raise TypeError("image must be uint8 [H,W], depth uint16 [H,W]")
+        if image.strides[1] != 1 or depth.strides[1] != 2:
+            raise ValueError("rows must be contiguous")
+        self._check(self._lib.dsm_frame_upload_async_u16(self._h, slot, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0],
+                                                         scale, depth_op_code(op)))
+
+    def frame(self, slot):
+        """debug tap (dsm_debug_get_frame): (image uint8 [H,W], depth float32 [H,W]) of a frame slot as the kernels read them"""
+        img = np.zeros((self.height, self.width), np.uint8)
+        dep = np.zeros((self.height, self.width), np.float32)
+        self._check(self._lib.dsm_debug_get_frame(self._h, slot, _ptr(img), _ptr(dep)))
+        return img, dep
 
     def frame_uploads_wait(self):
         self._check(self._lib.dsm_frame_uploads_wait(self._h))
@@ -488,6 +561,11 @@ class FusionFunctions:
             inv = _ptr(inv_poses_cm)
         ref_idx = np.ascontiguousarray(ref_idx, np.int32)
         poses_cm = np.ascontiguousarray(poses_cm, np.float32).reshape(n, 16)
+        if pinned.depth_u16 is not None:
+            self._check(self._lib.dsm_replay_enqueue_host_u16(self._h, n, _ptr(img), img.strides[0], pinned.pitch * pinned.h, _ptr(dep),
+                                                              dep.strides[0], pinned.pitch * pinned.h * 2, _ptr(ref_idx), _ptr(poses_cm), inv,
+                                                              *pinned.depth_u16_args))
+            return
         self._check(self._lib.dsm_replay_enqueue_host(self._h, n, _ptr(img), img.strides[0], pinned.pitch * pinned.h, _ptr(dep), dep.strides[0],
                                                       pinned.pitch * pinned.h * 4, _ptr(ref_idx), _ptr(poses_cm), inv))
 
@@ -586,12 +664,17 @@ class PinnedFrames:
     """n frames in page-locked host memory (dsm_host_alloc), rows laid out with a handle's slot pitch, pad columns zero:
     image(i) / depth(i) are [H,W] views that dsm_frame_upload_async moves in one transfer per plane."""
 
-    def __init__(self, ff, n: int, tight: bool = False):
+    def __init__(self, ff, n: int, tight: bool = False, depth_u16=None):
         """ff: a FusionFunctions (its slot layout), or a (height, width) pair -- the pitch is then the library's rule,
         ceil(width / 64) * 64 elements per row, and frames_upload_async checks it against the handle's.  tight=True: rows
         `width` elements apart, frames back to back (`pitch` = width) -- the asynchronous uploads then move no pad bytes over
-        the link and set the rows to the slots' pitch on the device."""
+        the link and set the rows to the slots' pitch on the device.  depth_u16=(scale, op): the depth planes hold the sensor's
+        uint16 (2 bytes a pixel), and frames_upload_async / replay_enqueue_host send them to the *_u16 entry points, which
+        convert on the device (depth_from_u16)."""
         self._lib = load_library()
+        self.depth_u16 = None if depth_u16 is None else (float(depth_u16[0]), depth_u16[1])
+        self.depth_u16_args = None if depth_u16 is None else (self.depth_u16[0], depth_op_code(self.depth_u16[1]))
+        de = 4 if depth_u16 is None else 2
         if isinstance(ff, tuple):
             self.n, self.h, self.w = n, int(ff[0]), int(ff[1])
             self.pitch = (self.w + 63) // 64 * 64
@@ -599,7 +682,7 @@ class PinnedFrames:
             self.n, self.h, self.w, self.pitch = n, ff.height, ff.width, ff.frame_pitch()
         if tight:
             self.pitch = self.w
-        self._bytes_img, self._bytes_dep = self.pitch * self.h, self.pitch * self.h * 4
+        self._bytes_img, self._bytes_dep = self.pitch * self.h, self.pitch * self.h * de
         p = _vp()
         rc = self._lib.dsm_host_alloc(C.byref(p), n * (self._bytes_img + self._bytes_dep))
         if rc:
@@ -608,7 +691,7 @@ class PinnedFrames:
         raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n * (self._bytes_img + self._bytes_dep),))
         raw[:] = 0
         self._img = raw[: n * self._bytes_img].reshape(n, self.h, self.pitch)
-        self._dep = raw[n * self._bytes_img:].view(np.float32).reshape(n, self.h, self.pitch)
+        self._dep = raw[n * self._bytes_img:].view(np.float32 if de == 4 else np.uint16).reshape(n, self.h, self.pitch)
 
     def image(self, i):
         return self._img[i, :, : self.w]
@@ -629,9 +712,10 @@ class PinnedFrames:
         if first < 0 or first + n > self.n or len(depths) != n:
             raise ValueError("frames out of range")
         keep = []
+        dt = self._dep.dtype
         for im, dp in zip(images, depths):
             im = im if (im.dtype == np.uint8 and im.strides[1] == 1) else np.ascontiguousarray(im, np.uint8)
-            dp = dp if (dp.dtype == np.float32 and dp.strides[1] == 4) else np.ascontiguousarray(dp, np.float32)
+            dp = dp if (dp.dtype == dt and dp.strides[1] == dt.itemsize) else np.ascontiguousarray(dp, dt)
             if im.shape != (self.h, self.w) or dp.shape != (self.h, self.w):
                 raise ValueError("frame size")
             keep.append((im, dp))
@@ -639,9 +723,10 @@ class PinnedFrames:
         dp_ = (C.c_void_p * n)(*[k[1].ctypes.data for k in keep])
         ist = (C.c_size_t * n)(*[k[0].strides[0] for k in keep])
         dst = (C.c_size_t * n)(*[k[1].strides[0] for k in keep])
-        rc = self._lib.dsm_host_pack_frames(n, self.w, self.h, ip, ist, dp_, dst,
-                                            C.c_void_p(self._img[first].ctypes.data), C.c_size_t(self.pitch), C.c_size_t(self._bytes_img),
-                                            C.c_void_p(self._dep[first].ctypes.data), C.c_size_t(self.pitch * 4), C.c_size_t(self._bytes_dep))
+        pack = self._lib.dsm_host_pack_frames if dt == np.float32 else self._lib.dsm_host_pack_frames_u16
+        rc = pack(n, self.w, self.h, ip, ist, dp_, dst,
+                  C.c_void_p(self._img[first].ctypes.data), C.c_size_t(self.pitch), C.c_size_t(self._bytes_img),
+                  C.c_void_p(self._dep[first].ctypes.data), C.c_size_t(self.pitch * dt.itemsize), C.c_size_t(self._bytes_dep))
         if rc:
             raise DsmError(rc, self._lib.dsm_last_error(None).decode())
 

@@ -176,6 +176,10 @@ struct dsm_handle {
     uint8_t *d_stage_frames_img = nullptr;
     float *d_stage_frames_depth = nullptr;
     int stage_frames_cap = 0;
+    // the *_u16 uploads: a uint16 depth plane per frame slot ([n_slots][pitch * h], allocated at the handle's first u16 call).  Slot s's
+    // plane is written only by uploads into slot s and read by their conversion kernel, on the same stream right behind the copy:
+    // the rules that order uploads into a slot against the frames that read it cover it as well
+    uint16_t *d_stage_u16 = nullptr;
     // DSM_FLAG_UPLOAD_STREAM: frames go up on a stream of their own, so that the upload of the next frame overlaps the
     // kernels of the current one; ev_slot[s] = the last frame submitted by dsm_fuse_frame_resident that reads slot s
     // has finished (recorded on the map stream).  Otherwise up_stream == stream.
@@ -496,26 +500,81 @@ int capture(dsm_handle *h, const DeviceCtx &ctx, bool with_compaction, int lo, i
 // image + i * img_frame_step / depth + i * depth_frame_step.  They go up ON THE STREAM THAT RUNS THEIR SUPERPIXEL STAGES, right
 // in front of them, into the frame slots of the pipelines that take them (slot = pipeline): no upload stream, no event between
 // an upload and its consumer, and a transfer holds up only the hardware queue of the work that waits for it anyway.
+// uint16 depth and how it becomes metres (the *_u16 entry points of include/dsm.h)
+struct DepthU16 {
+    float scale;
+    int op; // DSM_DEPTH_U16_DIVIDE or DSM_DEPTH_U16_MULTIPLY
+};
+bool depth_u16_ok(float scale, int op) {
+    return scale > 0.0f && scale <= 3.402823466e38f && (op == DSM_DEPTH_U16_DIVIDE || op == DSM_DEPTH_U16_MULTIPLY); // (false for NaN)
+}
+#define DEPTH_U16_CHECK(h, scale, op)                                                                                            \
+    do {                                                                                                                         \
+        if (!depth_u16_ok(scale, op))                                                                                            \
+            return fail(h, DSM_E_INVALID, "depth_scale %g / depth_op %d: the scale must be finite and > 0, the op "               \
+                                          "DSM_DEPTH_U16_DIVIDE or DSM_DEPTH_U16_MULTIPLY", (double)(scale), (int)(op));          \
+    } while (0)
+
+// n frames of uint16 depth (frame i at depth + i * frame_step bytes, rows `step` bytes apart) converted into the float depth planes of
+// slots slot0 .. slot0 + n - 1, on `st`: the rows go into the slots' u16 staging -- rows at the slot pitch and frames a slot apart, or
+// tight rows and frames back to back, as one transfer; any other layout frame by frame (row by row unless at the pitch) at the pitch --
+// and ONE kernel converts all n behind the copy.  Device memory with even pointer and steps is read where it is.
+int upload_depth_u16(dsm_handle *h, int slot0, int n, const void *depth, size_t step, size_t frame_step, hipMemcpyKind kind, const DepthU16 &u,
+                     hipStream_t st) {
+    if (!h->d_stage_u16) { // (no memset behind the allocation: it would race the first copy, which is on another stream)
+        void *p = nullptr;
+        HIP_TRY(h, hipMalloc(&p, (size_t)h->hc.n_slots * (size_t)h->hc.slot_elems * 2 + 256));
+        h->allocs.push_back(p);
+        h->d_stage_u16 = (uint16_t *)p;
+    }
+    const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
+    const size_t plane = (size_t)h->hc.slot_elems, tight = (size_t)w * (size_t)hh;
+    float *dd = (float *)h->hc.depth_base + (int64_t)slot0 * h->hc.slot_elems;
+    uint16_t *sg = h->d_stage_u16 + (size_t)slot0 * plane;
+    const uint16_t *src = sg;
+    int64_t src_row = pitch, src_frame = (int64_t)plane;
+    const bool flat = step == (size_t)pitch * 2, tight_rows = step == (size_t)w * 2;
+    if (kind == hipMemcpyDeviceToDevice && step % 2 == 0 && ((uintptr_t)depth & 1) == 0 && (n == 1 || frame_step % 2 == 0)) {
+        src = (const uint16_t *)depth;
+        src_row = (int64_t)(step / 2);
+        src_frame = n == 1 ? 0 : (int64_t)(frame_step / 2);
+    } else if (flat && (n == 1 || frame_step == plane * 2)) {
+        HIP_TRY(h, hipMemcpyAsync(sg, depth, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 2, kind, st));
+    } else if (tight_rows && (n == 1 || frame_step == tight * 2)) {
+        HIP_TRY(h, hipMemcpyAsync(sg, depth, tight * (size_t)n * 2, kind, st)); // (n tight frames fit the n slots' planes)
+        src_row = w;
+        src_frame = (int64_t)tight;
+    } else {
+        for (int i = 0; i < n; i++) {
+            const char *fs = (const char *)depth + (size_t)i * frame_step;
+            if (flat) HIP_TRY(h, hipMemcpyAsync(sg + (size_t)i * plane, fs, ((size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 2, kind, st));
+            else HIP_TRY(h, hipMemcpy2DAsync(sg + (size_t)i * plane, (size_t)pitch * 2, fs, step, (size_t)w * 2, (size_t)hh, kind, st));
+        }
+    }
+    const hipError_t e = launch_depth_u16(dd, pitch, h->hc.slot_elems, src, src_row, src_frame, w, hh, n, u.scale, u.op, st);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "u16 depth conversion: %s", hipGetErrorString(e));
+    return DSM_OK;
+}
+
 struct HostFrames {
     const uint8_t *image = nullptr;
-    const float *depth = nullptr;
+    const void *depth = nullptr; // float, or uint16 with u16 set
     size_t img_step = 0, img_frame_step = 0, depth_step = 0, depth_frame_step = 0;
+    const DepthU16 *u16 = nullptr;
 };
-// frames [first, first + n) of `f0` into the frame slots slot_base + first ..., on `st`
+// frames [first, first + n) of `f0` into the frame slots slot_base + first ..., on `st` (u16 depth: converted right behind its copy)
 int upload_host_frames(dsm_handle *h, const HostFrames &f0, int slot_base, int first, int n, hipStream_t st) {
-    constexpr int which = 3;
     if (n <= 0) return DSM_OK;
     HostFrames f = f0;
     f.image = f0.image + (size_t)first * f0.img_frame_step;
-    f.depth = (const float *)((const char *)f0.depth + (size_t)first * f0.depth_frame_step);
+    f.depth = (const char *)f0.depth + (size_t)first * f0.depth_frame_step;
     const int slot0 = slot_base + first;
     const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot0 * h->hc.slot_elems;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot0 * h->hc.slot_elems;
     const size_t plane = (size_t)pitch * (size_t)hh;
     const bool img_flat = f.img_step == (size_t)pitch, dep_flat = f.depth_step == (size_t)pitch * 4;
-    if (!(which & 1)) {
-    } else if (img_flat && (n == 1 || f.img_frame_step == plane)) {
+    if (img_flat && (n == 1 || f.img_frame_step == plane)) {
         HIP_TRY(h, hipMemcpyAsync(di, f.image, plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w, hipMemcpyHostToDevice, st));
     } else {
         for (int i = 0; i < n; i++) {
@@ -524,7 +583,8 @@ int upload_host_frames(dsm_handle *h, const HostFrames &f0, int slot_base, int f
             else HIP_TRY(h, hipMemcpy2DAsync(di + (size_t)i * plane, (size_t)pitch, src, f.img_step, (size_t)w, (size_t)hh, hipMemcpyHostToDevice, st));
         }
     }
-    if (!(which & 2)) {
+    if (f.u16) {
+        if (int rc = upload_depth_u16(h, slot0, n, f.depth, f.depth_step, f.depth_frame_step, hipMemcpyHostToDevice, *f.u16, st)) return rc;
     } else if (dep_flat && (n == 1 || f.depth_frame_step == plane * 4)) {
         HIP_TRY(h, hipMemcpyAsync(dd, f.depth, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 4, hipMemcpyHostToDevice, st));
     } else {
@@ -957,12 +1017,13 @@ int sync_and_fetch_counts(dsm_handle *h) {
     return check_status(h);
 }
 
+// u16: the depth is uint16, converted into the slot on the upload's stream (the call returns when the conversion is done)
 int upload_frame(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
-                 hipMemcpyKind kind) {
+                 hipMemcpyKind kind, const DepthU16 *u16 = nullptr) {
     if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth");
     if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
     const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    if (img_step < (size_t)w || depth_step < (size_t)w * 4) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (img_step < (size_t)w || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
     hipStream_t up = h->up_stream;
@@ -975,7 +1036,7 @@ int upload_frame(dsm_handle *h, int slot, const void *image, size_t img_step, co
         if (h->slot_used[(size_t)slot]) HIP_TRY(h, hipStreamWaitEvent(up, h->ev_slot[(size_t)slot], 0)); // frames still reading this slot
     }
     // tightly packed rows (the usual case): one 1-D copy each, then a repack into the pitched slot on the device
-    const bool img_tight = img_step == (size_t)w, dep_tight = depth_step == (size_t)w * 4;
+    const bool img_tight = img_step == (size_t)w, dep_tight = !u16 && depth_step == (size_t)w * 4;
     const size_t n = (size_t)w * (size_t)hh;
     const uint8_t *s_img = nullptr;
     const float *s_dep = nullptr;
@@ -987,7 +1048,9 @@ int upload_frame(dsm_handle *h, int slot, const void *image, size_t img_step, co
         }
     } else
         HIP_TRY(h, hipMemcpy2DAsync(di, (size_t)pitch, image, img_step, (size_t)w, (size_t)hh, kind, up));
-    if (dep_tight) {
+    if (u16) {
+        if (int rc = upload_depth_u16(h, slot, 1, depth, depth_step, 0, kind, *u16, up)) return rc;
+    } else if (dep_tight) {
         if (kind == hipMemcpyDeviceToDevice) s_dep = (const float *)depth;
         else {
             HIP_TRY(h, hipMemcpyAsync(h->d_stage_depth, depth, n * 4, kind, up));
@@ -1312,13 +1375,14 @@ void dsm_host_free(void *p) {
 // The caller's frames (one pointer + row step each: n cv::Mat pairs) into page-locked memory laid out like frame slots, by a
 // few host threads of the library (process-wide, made at the first call; the caller's thread takes part): one core copies
 // ~10 GB/s of 1226-pixel rows, a replay at fifteen thousand frames a second needs 35.
-int dsm_host_pack_frames(int32_t n, int32_t width, int32_t height, const uint8_t *const *images, const size_t *image_steps,
-                         const float *const *depths, const size_t *depth_steps, uint8_t *dst_image, size_t dst_img_step,
-                         size_t dst_img_frame_step, float *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step) {
+// (depth_elem: bytes per depth pixel, 4 or 2)
+static int host_pack_frames(int32_t n, int32_t width, int32_t height, const uint8_t *const *images, const size_t *image_steps,
+                            const void *const *depths, const size_t *depth_steps, uint8_t *dst_image, size_t dst_img_step,
+                            size_t dst_img_frame_step, void *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step, size_t depth_elem) {
     if (n < 0 || width <= 0 || height <= 0) return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: negative count or empty image");
     if (n == 0) return DSM_OK;
     if (!images || !image_steps || !depths || !depth_steps || !dst_image || !dst_depth) return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: null argument");
-    const size_t row_i = (size_t)width, row_d = (size_t)width * 4;
+    const size_t row_i = (size_t)width, row_d = (size_t)width * depth_elem;
     if (dst_img_step < row_i || dst_depth_step < row_d) return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: destination row step smaller than a row");
     if (n > 1 && (dst_img_frame_step < dst_img_step * (size_t)height || dst_depth_frame_step < dst_depth_step * (size_t)height))
         return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: destination frame step smaller than a frame");
@@ -1348,6 +1412,20 @@ int dsm_host_pack_frames(int32_t n, int32_t width, int32_t height, const uint8_t
         }
     });
     return DSM_OK;
+}
+
+int dsm_host_pack_frames(int32_t n, int32_t width, int32_t height, const uint8_t *const *images, const size_t *image_steps,
+                         const float *const *depths, const size_t *depth_steps, uint8_t *dst_image, size_t dst_img_step,
+                         size_t dst_img_frame_step, float *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step) {
+    return host_pack_frames(n, width, height, images, image_steps, (const void *const *)depths, depth_steps, dst_image, dst_img_step,
+                            dst_img_frame_step, dst_depth, dst_depth_step, dst_depth_frame_step, 4);
+}
+
+int dsm_host_pack_frames_u16(int32_t n, int32_t width, int32_t height, const uint8_t *const *images, const size_t *image_steps,
+                             const uint16_t *const *depths, const size_t *depth_steps, uint8_t *dst_image, size_t dst_img_step,
+                             size_t dst_img_frame_step, uint16_t *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step) {
+    return host_pack_frames(n, width, height, images, image_steps, (const void *const *)depths, depth_steps, dst_image, dst_img_step,
+                            dst_img_frame_step, dst_depth, dst_depth_step, dst_depth_frame_step, 2);
 }
 
 int dsm_seed_count(const dsm_handle *h) { return h ? h->hc.n_seed : DSM_E_INVALID; }
@@ -1848,6 +1926,32 @@ int dsm_frame_upload_device(dsm_handle *h, int slot, const void *image_dev, size
     return upload_frame(h, slot, image_dev, img_step, depth_dev, depth_step, hipMemcpyDeviceToDevice);
 }
 
+int dsm_frame_upload_u16(dsm_handle *h, int slot, const uint8_t *image, size_t img_step, const uint16_t *depth, size_t depth_step,
+                         float depth_scale, int32_t depth_op) {
+    if (!h) return DSM_E_INVALID;
+    DEPTH_U16_CHECK(h, depth_scale, depth_op);
+    const DepthU16 u = {depth_scale, depth_op};
+    if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth"); // (upload_frame checks these too: here, before any device call)
+    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
+    if (img_step < (size_t)h->hc.w || depth_step < (size_t)h->hc.w * 2) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    int rc = bind_device(h);
+    if (rc) return rc;
+    return upload_frame(h, slot, image, img_step, depth, depth_step, hipMemcpyHostToDevice, &u);
+}
+
+int dsm_frame_upload_device_u16(dsm_handle *h, int slot, const void *image_dev, size_t img_step, const void *depth_dev, size_t depth_step,
+                                float depth_scale, int32_t depth_op) {
+    if (!h) return DSM_E_INVALID;
+    DEPTH_U16_CHECK(h, depth_scale, depth_op);
+    const DepthU16 u = {depth_scale, depth_op};
+    if (!image_dev || !depth_dev) return fail(h, DSM_E_INVALID, "null image/depth");
+    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
+    if (img_step < (size_t)h->hc.w || depth_step < (size_t)h->hc.w * 2) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    int rc = bind_device(h);
+    if (rc) return rc;
+    return upload_frame(h, slot, image_dev, img_step, depth_dev, depth_step, hipMemcpyDeviceToDevice, &u);
+}
+
 int dsm_frame_pitch(const dsm_handle *h, int32_t *pitch) {
     if (!h || !pitch) return DSM_E_INVALID;
     *pitch = h->hc.pitch;
@@ -1858,13 +1962,14 @@ int dsm_frame_upload_async(dsm_handle *h, int slot, const uint8_t *image, size_t
     return dsm_frames_upload_async(h, slot, 1, image, img_step, 0, depth, depth_step, 0);
 }
 
-int dsm_frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
-                            const float *depth, size_t depth_step, size_t depth_frame_step) {
+// dsm_frames_upload_async and its u16 form (u16 != nullptr: `depth` is uint16, converted on the upload stream before the event)
+static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
+                               const void *depth, size_t depth_step, size_t depth_frame_step, const DepthU16 *u16) {
     if (!h) return DSM_E_INVALID;
     if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth");
     if (n < 1 || slot0 < 0 || slot0 + n > h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slots [%d,%d) out of range [0,%d)", slot0, slot0 + n, h->hc.n_slots);
     const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    if (img_step < (size_t)w || depth_step < (size_t)w * 4) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (img_step < (size_t)w || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
     if (n > 1 && (img_frame_step < img_step * (size_t)hh || depth_frame_step < depth_step * (size_t)hh)) return fail(h, DSM_E_INVALID, "frame step smaller than a frame");
     // A handle that advances with a batch and whose own stream has carried nothing since the batch last ordered itself
     // behind it (`touched` false: only batch calls since): whatever may still read these slots is covered by the batch's
@@ -1915,7 +2020,7 @@ int dsm_frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *imag
     const bool img_flat = img_step == (size_t)pitch, dep_flat = depth_step == (size_t)pitch * 4;
     const size_t tight = (size_t)w * (size_t)hh;
     const bool img_tight = !img_flat && img_step == (size_t)w && (n == 1 || img_frame_step == tight);
-    const bool dep_tight = !dep_flat && depth_step == (size_t)w * 4 && (n == 1 || depth_frame_step == tight * 4);
+    const bool dep_tight = !u16 && !dep_flat && depth_step == (size_t)w * 4 && (n == 1 || depth_frame_step == tight * 4);
     if ((img_tight || dep_tight) && n > h->stage_frames_cap) {
         HIP_TRY(h, hipStreamSynchronize(up)); // (an earlier call's repack may still read the old buffers)
         if (h->d_stage_frames_img) HIP_TRY(h, hipFree(h->d_stage_frames_img));
@@ -1942,7 +2047,9 @@ int dsm_frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *imag
             else HIP_TRY(h, hipMemcpy2DAsync(di + (size_t)i * plane, (size_t)pitch, src, img_step, (size_t)w, (size_t)hh, hipMemcpyHostToDevice, up));
         }
     }
-    if (dep_tight) { // (already on its way)
+    if (u16) {
+        if (int rc = upload_depth_u16(h, slot0, n, depth, depth_step, depth_frame_step, hipMemcpyHostToDevice, *u16, up)) return rc;
+    } else if (dep_tight) { // (already on its way)
     } else if (dep_flat && (n == 1 || depth_frame_step == plane * 4)) {
         HIP_TRY(h, hipMemcpyAsync(dd, depth, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 4, hipMemcpyHostToDevice, up));
     } else {
@@ -1973,8 +2080,26 @@ int dsm_frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *imag
     e.lo = slot0;
     e.hi = slot0 + n;
     e.pending = ~0ull;
-    HIP_TRY(h, hipEventRecord(e.ev, up));
+    HIP_TRY(h, hipEventRecord(e.ev, up)); // (behind the u16 conversion: the upload has landed when its float plane is there)
     return DSM_OK;
+}
+
+int dsm_frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
+                            const float *depth, size_t depth_step, size_t depth_frame_step) {
+    return frames_upload_async(h, slot0, n, image, img_step, img_frame_step, depth, depth_step, depth_frame_step, nullptr);
+}
+
+int dsm_frame_upload_async_u16(dsm_handle *h, int slot, const uint8_t *image, size_t img_step, const uint16_t *depth, size_t depth_step,
+                               float depth_scale, int32_t depth_op) {
+    return dsm_frames_upload_async_u16(h, slot, 1, image, img_step, 0, depth, depth_step, 0, depth_scale, depth_op);
+}
+
+int dsm_frames_upload_async_u16(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
+                                const uint16_t *depth, size_t depth_step, size_t depth_frame_step, float depth_scale, int32_t depth_op) {
+    if (!h) return DSM_E_INVALID;
+    DEPTH_U16_CHECK(h, depth_scale, depth_op);
+    const DepthU16 u = {depth_scale, depth_op};
+    return frames_upload_async(h, slot0, n, image, img_step, img_frame_step, depth, depth_step, depth_frame_step, &u);
 }
 
 int dsm_frame_uploads_wait(dsm_handle *h) {
@@ -2011,13 +2136,15 @@ int dsm_replay_enqueue(dsm_handle *h, int32_t n, const int32_t *slots, const int
     return dsm_replay_enqueue_inv(h, n, slots, ref_idx, poses16, nullptr);
 }
 
-int dsm_replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, size_t img_step, size_t img_frame_step, const float *depth,
-                            size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16, const float *inv_poses16) {
+// dsm_replay_enqueue_host and its u16 form (u16 != nullptr: `depth` is uint16, each group's converted right behind its copy)
+static int replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, size_t img_step, size_t img_frame_step, const void *depth,
+                               size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16, const float *inv_poses16,
+                               const DepthU16 *u16) {
     if (!h) return DSM_E_INVALID;
     if (n < 0 || (n > 0 && (!image || !depth || !ref_idx || !poses16))) return fail(h, DSM_E_INVALID, "null/negative argument");
     if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
     if (h->hc.n_slots < h->n_pipe) return fail(h, DSM_E_INVALID, "dsm_replay_enqueue_host keeps a frame in the slot of its pipeline: %d frame slots for pipeline_depth %d", h->hc.n_slots, h->n_pipe);
-    if (img_step < (size_t)h->hc.w || depth_step < (size_t)h->hc.w * 4) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (img_step < (size_t)h->hc.w || depth_step < (size_t)h->hc.w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
     if (n > 1 && (img_frame_step < img_step * (size_t)h->hc.h || depth_frame_step < depth_step * (size_t)h->hc.h)) return fail(h, DSM_E_INVALID, "frame step smaller than a frame");
     int rc = bind_device(h);
     if (rc) return rc;
@@ -2027,6 +2154,7 @@ int dsm_replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, size
     for (int i = 0; i < n; i++) slots[(size_t)i] = (int32_t)((h->frames_submitted + i) % h->n_pipe);
     HostFrames hf;
     hf.img_step = img_step; hf.img_frame_step = img_frame_step; hf.depth_step = depth_step; hf.depth_frame_step = depth_frame_step;
+    hf.u16 = u16;
     for (int i = 0; i < n;) {
         int m = 0;
         if ((rc = stage_params_batch(h, n - i, slots.data() + i, ref_idx + i, poses16 + 16 * (size_t)i,
@@ -2034,7 +2162,7 @@ int dsm_replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, size
         for (int j = 0; j < m;) {
             const int G = group_size(h);
             hf.image = image + (size_t)(i + j) * img_frame_step;
-            hf.depth = (const float *)((const char *)depth + (size_t)(i + j) * depth_frame_step);
+            hf.depth = (const char *)depth + (size_t)(i + j) * depth_frame_step;
             if (group_path(h) && m - j >= G && h->frames_submitted % G == 0) {
                 if ((rc = submit_group(h, &hf))) return rc;
                 j += G;
@@ -2055,6 +2183,20 @@ int dsm_replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, size
         h->host_calls++;
     }
     return DSM_OK;
+}
+
+int dsm_replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, size_t img_step, size_t img_frame_step, const float *depth,
+                            size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16, const float *inv_poses16) {
+    return replay_enqueue_host(h, n, image, img_step, img_frame_step, depth, depth_step, depth_frame_step, ref_idx, poses16, inv_poses16, nullptr);
+}
+
+int dsm_replay_enqueue_host_u16(dsm_handle *h, int32_t n, const uint8_t *image, size_t img_step, size_t img_frame_step, const uint16_t *depth,
+                                size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16, const float *inv_poses16,
+                                float depth_scale, int32_t depth_op) {
+    if (!h) return DSM_E_INVALID;
+    DEPTH_U16_CHECK(h, depth_scale, depth_op);
+    const DepthU16 u = {depth_scale, depth_op};
+    return replay_enqueue_host(h, n, image, img_step, img_frame_step, depth, depth_step, depth_frame_step, ref_idx, poses16, inv_poses16, &u);
 }
 
 int dsm_replay_wait(dsm_handle *h, int32_t calls_back) {
@@ -2280,6 +2422,22 @@ int dsm_debug_tier_counts(dsm_handle *h, int32_t *out /* 8 */) {
 }
 
 // debug tap: per-wave phase stamps of the per-seed kernels (only with DSM_FLAG_WAVE_STAMPS)
+int dsm_debug_get_frame(dsm_handle *h, int slot, uint8_t *image, float *depth) {
+    if (!h) return DSM_E_INVALID;
+    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
+    int rc = bind_device(h);
+    if (rc) return rc;
+    { // behind the asynchronous uploads that wrote the slot (the other kinds of upload are ordered before the map stream already)
+        const ReadSlots reads(h, slot, slot + 1);
+        if ((rc = wait_uploads(h, h->stream, kSerialBit))) return rc;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t w = (size_t)h->hc.w, hh = (size_t)h->hc.h, pitch = (size_t)h->hc.pitch;
+    if (image) HIP_TRY(h, hipMemcpy2D(image, w, (const uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems, pitch, w, hh, hipMemcpyDeviceToHost));
+    if (depth) HIP_TRY(h, hipMemcpy2D(depth, w * 4, (const float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems, pitch * 4, w * 4, hh, hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
 int dsm_debug_wave_stamps(dsm_handle *h, int64_t *out /* 5 * n_seed * 8 */) {
     if (!h || !out) return DSM_E_INVALID;
     if (!kWaveStamps) return fail(h, DSM_E_STATE, "this library was built without phase stamps (-DDSM_WAVE_STAMPS=1: tools/wave_stamps.py builds such a copy)");

@@ -169,6 +169,10 @@ hipError_t launch_repack_frames(uint8_t *d_img, float *d_depth, int pitch, int64
                                 int frames, hipStream_t st);
 hipError_t launch_repack(uint8_t *d_img, float *d_depth, int pitch, const uint8_t *s_img, const float *s_depth, int w, int h,
                          hipStream_t st);
+// uint16 depth of `frames` frames (rows src_row elements apart, frames src_frame apart) converted into the pitched depth planes
+// d_depth + f * slot_elems: op = DSM_DEPTH_U16_DIVIDE (u / s) or DSM_DEPTH_U16_MULTIPLY (u * s), one launch, grid.y = frame
+hipError_t launch_depth_u16(float *d_depth, int pitch, int64_t slot_elems, const uint16_t *src, int64_t src_row, int64_t src_frame, int w, int h,
+                            int frames, float s, int op, hipStream_t st);
 hipError_t launch_extract_marked(const DeviceCtx &ctx, dsm_surfel *out, int cap, float4 *cloud_out, hipStream_t st);
 hipError_t launch_extract(const DeviceCtx &ctx, int key, dsm_surfel *out, int cap, int n_upper, hipStream_t st);
 hipError_t launch_append_count(const DeviceCtx &ctx, int n, hipStream_t st);

@@ -832,6 +832,70 @@ hipError_t launch_repack(uint8_t *d_img, float *d_depth, int pitch, const uint8_
     return hipGetLastError();
 }
 
+// Sensor-native depth (the *_u16 uploads): uint16 -> float metres into the pitched depth plane of a slot, what the host would
+// have computed before a float upload -- OP = DSM_DEPTH_U16_DIVIDE: (float)u / s, an IEEE divide (u16.astype(np.float32) /
+// np.float32(scale); the library builds with correctly rounded fp32 division), DSM_DEPTH_U16_MULTIPLY: (float)u * s
+// (depth_image_proc's depth * 0.001f).  0 stays 0.  Only the w pixels of a row are written, as by a float upload's copy.
+template <int OP> __device__ __forceinline__ float depth_from_u16(uint32_t u, float s) {
+    return OP == DSM_DEPTH_U16_DIVIDE ? (float)u / s : (float)u * s;
+}
+// Source rows src_row elements apart, frames src_frame apart, grid.y = frame.  VEC (rows a multiple of eight elements apart,
+// 16-byte aligned: the u16 staging of the slots at their own pitch): a lane takes eight pixels -- one 16-byte load, two 16-byte
+// stores (the slot rows are 64-element aligned); the last partial vector of a row goes pixel by pixel and reads nothing past w.
+// Otherwise (tight rows, a caller's device buffer) a lane takes one pixel.
+template <int OP, bool VEC>
+__global__ __launch_bounds__(256) void k_depth_u16(float *__restrict__ dst, int pitch, int64_t dst_frame, const uint16_t *__restrict__ src,
+                                                   int64_t src_row, int64_t src_frame, int w, int h, float s) {
+    const uint16_t *sf = src + (int64_t)blockIdx.y * src_frame;
+    float *df = dst + (int64_t)blockIdx.y * dst_frame;
+    if (VEC) {
+        const int vpr = (w + 7) >> 3, n = vpr * h;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+            const int y = i / vpr, x = (i - y * vpr) << 3;
+            const uint16_t *sp = sf + (int64_t)y * src_row + x;
+            float *dp = df + (int64_t)y * pitch + x;
+            if (x + 8 <= w) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(sp);
+                float4 a, b;
+                a.x = depth_from_u16<OP>(v.x & 0xffffu, s);
+                a.y = depth_from_u16<OP>(v.x >> 16, s);
+                a.z = depth_from_u16<OP>(v.y & 0xffffu, s);
+                a.w = depth_from_u16<OP>(v.y >> 16, s);
+                b.x = depth_from_u16<OP>(v.z & 0xffffu, s);
+                b.y = depth_from_u16<OP>(v.z >> 16, s);
+                b.z = depth_from_u16<OP>(v.w & 0xffffu, s);
+                b.w = depth_from_u16<OP>(v.w >> 16, s);
+                reinterpret_cast<float4 *>(dp)[0] = a;
+                reinterpret_cast<float4 *>(dp)[1] = b;
+            } else {
+                for (int k = 0; k < w - x; k++) dp[k] = depth_from_u16<OP>(sp[k], s);
+            }
+        }
+    } else {
+        const int n = w * h;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+            const int y = i / w, x = i - y * w;
+            df[(int64_t)y * pitch + x] = depth_from_u16<OP>(sf[(int64_t)y * src_row + x], s);
+        }
+    }
+}
+hipError_t launch_depth_u16(float *d_depth, int pitch, int64_t slot_elems, const uint16_t *src, int64_t src_row, int64_t src_frame, int w, int h,
+                            int frames, float s, int op, hipStream_t st) {
+    const bool vec = src_row % 8 == 0 && src_frame % 8 == 0 && ((uintptr_t)src & 15) == 0;
+    const int n = vec ? ((w + 7) >> 3) * h : w * h;
+    int blocks = (n + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    const dim3 grid(blocks, frames);
+    if (op == DSM_DEPTH_U16_DIVIDE) {
+        if (vec) hipLaunchKernelGGL((k_depth_u16<DSM_DEPTH_U16_DIVIDE, true>), grid, dim3(256), 0, st, d_depth, pitch, slot_elems, src, src_row, src_frame, w, h, s);
+        else hipLaunchKernelGGL((k_depth_u16<DSM_DEPTH_U16_DIVIDE, false>), grid, dim3(256), 0, st, d_depth, pitch, slot_elems, src, src_row, src_frame, w, h, s);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_depth_u16<DSM_DEPTH_U16_MULTIPLY, true>), grid, dim3(256), 0, st, d_depth, pitch, slot_elems, src, src_row, src_frame, w, h, s);
+        else hipLaunchKernelGGL((k_depth_u16<DSM_DEPTH_U16_MULTIPLY, false>), grid, dim3(256), 0, st, d_depth, pitch, slot_elems, src, src_row, src_frame, w, h, s);
+    }
+    return hipGetLastError();
+}
+
 // Timed replays only: keep the GPU busy for `ticks` of the 100 MHz wall clock while the host enqueues
 // the whole frame, so that the events between kernels do not measure host launch latency.
 __global__ void k_delay(long long ticks) {

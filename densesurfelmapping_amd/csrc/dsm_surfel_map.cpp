@@ -26,6 +26,11 @@
 #include <utility>
 #include <vector>
 
+// The engine's u16 upload is referenced weakly: the node's host logic also builds on top of engines without it (a CPU stand-in of
+// the engine for tests), and dsm_surfel_map_depth_input_u16 refuses its input there.
+extern "C" int dsm_frame_upload_u16(dsm_handle *h, int slot, const uint8_t *image, size_t img_step, const uint16_t *depth, size_t depth_step,
+                                    float depth_scale, int32_t depth_op) __attribute__((weak));
+
 namespace {
 
 using namespace dsm_node;
@@ -321,8 +326,12 @@ int synchronize_msgs(dsm_surfel_map *m) {
     const int w = m->cfg.cam_width;
     // two frame slots in turn: this frame goes up (on the engine's upload stream) while the previous one is still being fused
     const int slot = (int)(m->frames_fused & 1);
-    ENGINE_TRY(m, dsm_frame_upload(m->engine, slot, m->image_buffer.front().bytes, (size_t)w,
-                                   (const float *)m->depth_buffer.front().bytes, (size_t)w * 4));
+    const Frame &dep = m->depth_buffer.front();
+    if (dep.u16_scale > 0) // a sensor's uint16 frame: converted to metres on the device, into the slot (dsm_surfel_map_depth_input_u16)
+        ENGINE_TRY(m, dsm_frame_upload_u16(m->engine, slot, m->image_buffer.front().bytes, (size_t)w, (const uint16_t *)dep.bytes, (size_t)w * 2,
+                                           dep.u16_scale, dep.u16_op));
+    else
+        ENGINE_TRY(m, dsm_frame_upload(m->engine, slot, m->image_buffer.front().bytes, (size_t)w, (const float *)dep.bytes, (size_t)w * 4));
     ENGINE_TRY(m, dsm_fuse_frame_resident(m->engine, slot, relative_index, pose16));
     m->last.valid = true;
     m->last.stamp = std::get<0>(m->pose_reference_buffer.front()); // fuse_stamp (:112)
@@ -337,13 +346,16 @@ int synchronize_msgs(dsm_surfel_map *m) {
 }
 
 int copy_frame(dsm_surfel_map *m, std::list<Frame> &buffer, FramePool &pool, dsm_stamp stamp, int32_t width,
-               int32_t height, size_t step, const void *data, size_t elem) {
+               int32_t height, size_t step, const void *data, size_t elem, float u16_scale = 0, int32_t u16_op = 0) {
     if (!data) return fail(m, DSM_E_INVALID, "null image data");
     if (width != m->cfg.cam_width || height != m->cfg.cam_height)
         return fail(m, DSM_E_INVALID, "image is %dx%d, the node was configured for %dx%d", width, height, m->cfg.cam_width, m->cfg.cam_height);
     if (step < (size_t)width * elem) return fail(m, DSM_E_INVALID, "row step smaller than a row");
     Frame f;
     f.stamp = stamp;
+    f.pool = &pool;
+    f.u16_scale = u16_scale;
+    f.u16_op = u16_op;
     f.bytes = pool.take((size_t)width * (size_t)height * elem, &f.pinned);
     if (!f.bytes) return fail(m, DSM_E_HIP, "no host memory for a frame");
     for (int y = 0; y < height; y++) memcpy(f.bytes + (size_t)y * width * elem, (const uint8_t *)data + (size_t)y * step, (size_t)width * elem);
@@ -447,6 +459,7 @@ void dsm_surfel_map_destroy(dsm_surfel_map *m) {
     for (const Frame &f : m->depth_buffer) m->depth_pool.release(f);
     m->image_pool.drain();
     m->depth_pool.drain();
+    m->depth16_pool.drain();
     if (m->release_publish) m->release_publish(m);
     delete m;
 }
@@ -470,6 +483,21 @@ int dsm_surfel_map_depth_input(dsm_surfel_map *m, dsm_stamp stamp, int32_t width
     if (!encoding || strcmp(encoding, "32FC1") != 0)
         return fail(m, DSM_E_INVALID, "depth encoding '%s': only 32FC1 is taken", encoding ? encoding : "(null)");
     const int rc = copy_frame(m, m->depth_buffer, m->depth_pool, stamp, width, height, step, data, 4);
+    return rc ? rc : synchronize_msgs(m);
+}
+
+int dsm_surfel_map_depth_input_u16(dsm_surfel_map *m, dsm_stamp stamp, int32_t width, int32_t height, size_t step, const char *encoding,
+                                   const uint16_t *data, float depth_scale, int32_t depth_op) {
+    if (!m) return DSM_E_INVALID;
+    if (m->failed) return fail(m, DSM_E_STATE, "the node failed half-way through a state change earlier and takes no more input");
+    if (!encoding || (strcmp(encoding, "16UC1") != 0 && strcmp(encoding, "mono16") != 0))
+        return fail(m, DSM_E_INVALID, "depth encoding '%s': dsm_surfel_map_depth_input_u16 takes 16UC1 / mono16", encoding ? encoding : "(null)");
+    if (!dsm_frame_upload_u16) return fail(m, DSM_E_STATE, "this engine has no uint16 depth upload");
+    // (checked here, not first at the upload: a frame that cannot be converted must not wait for its pose)
+    if (!(depth_scale > 0.0f && depth_scale <= 3.402823466e38f) || (depth_op != DSM_DEPTH_U16_DIVIDE && depth_op != DSM_DEPTH_U16_MULTIPLY))
+        return fail(m, DSM_E_INVALID, "depth_scale %g / depth_op %d: the scale must be finite and > 0, the op DSM_DEPTH_U16_DIVIDE or _MULTIPLY",
+                    (double)depth_scale, (int)depth_op);
+    const int rc = copy_frame(m, m->depth_buffer, m->depth16_pool, stamp, width, height, step, data, 2, depth_scale, depth_op);
     return rc ? rc : synchronize_msgs(m);
 }
 

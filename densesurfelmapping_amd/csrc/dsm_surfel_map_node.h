@@ -49,10 +49,14 @@ struct Segment {
     int count;
 };
 
+struct FramePool;
 struct Frame {
     dsm_stamp stamp;
     uint8_t *bytes; // tightly packed rows: a page-locked block of the node's pool, or (overflow) pageable memory
     bool pinned;
+    FramePool *pool;       // the pool the bytes came from (release them there)
+    float u16_scale = 0;   // > 0: a uint16 depth frame (dsm_surfel_map_depth_input_u16), converted on upload with u16_op
+    int32_t u16_op = 0;
 };
 
 // Frames wait for their pose in page-locked memory so that the upload of a frame is one DMA -- but only the first
@@ -85,6 +89,7 @@ struct FramePool {
         return (uint8_t *)malloc(bytes ? bytes : 1);
     }
     void release(const Frame &f) {
+        if (f.pool != this) { f.pool->release(f); return; } // (a depth list holds float and uint16 frames)
         if (!f.pinned) { free(f.bytes); return; }
         pinned_live--;
         if (free_blocks.size() < kPooledFrames) free_blocks.push_back(f.bytes);
@@ -117,7 +122,7 @@ struct dsm_surfel_map {
     dsm_surfel_map_config cfg;
     dsm_handle *engine = nullptr;
     std::list<Frame> image_buffer, depth_buffer;                                 // surfel_map.h:96-97
-    FramePool image_pool, depth_pool;                                            // where the buffered frames' bytes live
+    FramePool image_pool, depth_pool, depth16_pool;                              // where the buffered frames' bytes live (depth16: uint16 frames)
     std::list<std::tuple<dsm_stamp, dsm_pose_msg, int>> pose_reference_buffer; // :98
     std::vector<PoseElement> poses_database;                                     // :120
     std::set<int> local_surfels_indexs;                                          // :122

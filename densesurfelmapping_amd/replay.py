@@ -203,13 +203,15 @@ class HipEngine:
     render / copy; FOUR blocks of `chunk` frames in turn: one being filled, three in flight) unless the source already keeps
     them there (`pinned_run`).  `fuse` is the frame-at-a-time form of the same thing (SurfelMap::fuse_map,
     surfel_map.cpp:1060-1113).  There is no other engine in this package: without a gfx950 device the constructor raises
-    (DSM_E_NO_DEVICE)."""
+    (DSM_E_NO_DEVICE).  depth_u16=(scale, op): the source's frames() yield the sensor's uint16 depth, which is packed and streamed
+    at 2 bytes a pixel and converted to metres on the device (dsm_replay_enqueue_host_u16; api.depth_from_u16 says how)."""
 
     BLOCKS = 4  # page-locked blocks of `chunk` frames the prefetch thread fills in turn (one being filled, up to three in flight)
 
-    def __init__(self, cam, device=0, capacity=0, pipeline_depth=24, chunk=48):
+    def __init__(self, cam, device=0, capacity=0, pipeline_depth=24, chunk=48, depth_u16=None):
         from . import api
         self._api = api
+        self.depth_u16 = depth_u16
         self.chunk = max(1, int(chunk))
         self.depth = int(pipeline_depth) if pipeline_depth else 4
         self.ff = api.FusionFunctions.from_camera(cam, device=device, frame_slots=max(self.depth, 2), surfel_capacity=capacity,
@@ -221,7 +223,10 @@ class HipEngine:
 
     def fuse(self, image, depth, pose, ref_idx):  # one frame: blocking upload into a slot, one enqueue
         slot = self.n % max(self.depth, 2)
-        self.ff.frame_upload(slot, image, depth)
+        if self.depth_u16 is not None:
+            self.ff.frame_upload_u16(slot, image, depth, *self.depth_u16)
+        else:
+            self.ff.frame_upload(slot, image, depth)
         self.ff.fuse_frame_resident(slot, ref_idx, pose)
         self.n += 1
 
@@ -235,12 +240,13 @@ class HipEngine:
         api, ff, C = self._api, self.ff, self.chunk
         n_total = b - a
         chunks = [(a + c0, min(C, n_total - c0)) for c0 in range(0, n_total, C)]  # (first frame, frames)
-        zero_copy = getattr(source, "pinned_run", None) is not None and source.pinned_run(api, a, 1) is not None
+        # (a source's own page-locked blocks hold float depth)
+        zero_copy = self.depth_u16 is None and getattr(source, "pinned_run", None) is not None and source.pinned_run(api, a, 1) is not None
         ready = queue.Queue()
         free = threading.Semaphore(self.BLOCKS)
         stop = threading.Event()
         if not zero_copy and self._pins is None:
-            self._pins = [api.PinnedFrames(ff, C) for _ in range(self.BLOCKS)]
+            self._pins = [api.PinnedFrames(ff, C, depth_u16=self.depth_u16) for _ in range(self.BLOCKS)]
 
         def produce():  # decode / render / copy chunk k into page-locked block k mod BLOCKS, as soon as that block is free
             try:
@@ -297,7 +303,7 @@ class HipEngine:
         self.n += n_total
         dt = time.perf_counter() - t_start
         self.stats = {"frames": n_total, "seconds": dt, "chunk_frames": C, "zero_copy": bool(zero_copy),
-                      "bytes_per_frame": int(ff.frame_pitch() * ff.height * 5)}
+                      "bytes_per_frame": int(ff.frame_pitch() * ff.height * (3 if self.depth_u16 is not None else 5))}
         return n_total
 
     def cloud(self):

@@ -21,6 +21,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_engine", "dsm_surfel_map_frames_fused", "dsm_surfel_map_dropped_poses", "dsm_surfel_map_pose_count",
     "dsm_surfel_map_get_pose", "dsm_surfel_map_get_links", "dsm_surfel_map_get_attached",
     "dsm_surfel_map_get_inactive_cloud", "dsm_surfel_map_get_cloud", "dsm_surfel_map_get_cloud_device", "dsm_surfel_map_set_publish",
+    "dsm_surfel_map_depth_input_u16",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -63,6 +64,7 @@ def _bind(lib):
         lib.dsm_surfel_map_last_error.restype = C.c_char_p
         lib.dsm_surfel_map_image_input.argtypes = [_vp, _Stamp, C.c_int32, C.c_int32, C.c_size_t, C.c_char_p, _vp]
         lib.dsm_surfel_map_depth_input.argtypes = [_vp, _Stamp, C.c_int32, C.c_int32, C.c_size_t, C.c_char_p, _vp]
+        lib.dsm_surfel_map_depth_input_u16.argtypes = [_vp, _Stamp, C.c_int32, C.c_int32, C.c_size_t, C.c_char_p, _vp, C.c_float, C.c_int32]
         lib.dsm_surfel_map_orb_results_input.argtypes = [_vp, _Stamp, _vp, C.c_int32, _vp, C.c_int32, _Stamp, _vp, _vp]
         for name in ("save_cloud", "save_mesh", "save_map"):
             getattr(lib, "dsm_surfel_map_" + name).argtypes = [_vp, C.c_char_p]
@@ -137,6 +139,13 @@ class SurfelMap:
         d = np.ascontiguousarray(depth, dtype=np.float32)
         self._check(self._lib.dsm_surfel_map_depth_input(self._h, _Stamp(*stamp), d.shape[1], d.shape[0], d.strides[0],
                                                          encoding.encode(), _ptr(d)))
+
+    def depth_input_u16(self, stamp, depth, scale, op="divide", encoding: str = "16UC1"):
+        """a sensor's uint16 depth (16UC1), converted to metres on the device at upload: api.depth_from_u16(depth, scale, op)"""
+        from .api import depth_op_code
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        self._check(self._lib.dsm_surfel_map_depth_input_u16(self._h, _Stamp(*stamp), d.shape[1], d.shape[0], d.strides[0],
+                                                             encoding.encode(), _ptr(d), scale, depth_op_code(op)))
 
     def orb_results_input(self, stamp, loop_values, loop_path, this_pose, covariance, this_stamp=None):
         lv = np.ascontiguousarray(loop_values, dtype=np.float32)

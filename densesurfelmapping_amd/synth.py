@@ -186,7 +186,7 @@ def _tum_boxes(scene: Scene) -> np.ndarray:
     return out
 
 
-def _render_tum(cam: Camera, scene: Scene, t: int):
+def _render_tum(cam: Camera, scene: Scene, t: int, as_u16: bool = False):
     W, H = cam.width, cam.height
     pose = scene.pose(t)
     tl = t % scene.frames_per_period
@@ -225,6 +225,8 @@ def _render_tum(cam: Camera, scene: Scene, t: int):
     # ---- the sensor
     z = tt * (1.0 + scene.depth_noise * (_uniform01(pix, salt + 2) - 0.5))
     if not scene.tum_sensor:
+        if as_u16:
+            raise ValueError("render_u16: a tum scene with tum_sensor=False has float depth, not a sensor's uint16")
         return image, np.where(_uniform01(pix, salt + 3) < scene.hole_fraction, 0.0, z).astype(np.float32), pose
     with np.errstate(divide="ignore", invalid="ignore"):
         disp_true = scene.kinect_bf * sc / tt                      # pixels, of the clean geometry: the shadows' extent
@@ -244,8 +246,18 @@ def _render_tum(cam: Camera, scene: Scene, t: int):
     if scene.tum_border > 0:
         valid[:, W - scene.tum_border:] = False
     u16 = np.clip(np.round(np.where(valid, zq, 0.0) * scene.tum_depth_scale), 0, 65535).astype(np.uint16)
+    if as_u16:
+        return image, u16, pose  # what the depth PNG holds
     depth = (u16.astype(np.float32) / np.float32(scene.tum_depth_scale)).astype(np.float32)  # what the depth PNG decodes to
     return image, depth, pose
+
+
+def render_u16(cam: Camera, scene: Scene, t: int):
+    """(image uint8 [H,W], depth uint16 [H,W] = metres x scene.tum_depth_scale as the TUM PNGs store it, pose) of a `tum` scene
+    with its sensor model: render()'s depth is exactly u16.astype(float32) / float32(tum_depth_scale) (api.depth_from_u16)."""
+    if not scene.tum:
+        raise ValueError("render_u16 renders tum scenes (the others have no uint16 sensor depth)")
+    return _render_tum(cam, scene, t, as_u16=True)
 
 
 def render(cam: Camera, scene: Scene, t: int):

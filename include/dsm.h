@@ -292,6 +292,43 @@ int dsm_frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *imag
                             const float *depth, size_t depth_step, size_t depth_frame_step);
 int dsm_frame_uploads_wait(dsm_handle *h); /* blocks the host until this handle's asynchronous uploads have landed */
 
+/* ---- sensor-native depth: the frame's depth as uint16 (TUM RGB-D PNGs, ROS 16UC1, KITTI-style PNGs), converted to float
+ * metres on the device.  depth_op DSM_DEPTH_U16_DIVIDE: d = (float)u / depth_scale, an IEEE fp32 divide (numpy's
+ * u16.astype(np.float32) / np.float32(scale): TUM 5000, KITTI 256, 1 = the plain value); DSM_DEPTH_U16_MULTIPLY:
+ * d = (float)u * depth_scale, an fp32 multiply (depth_image_proc's depth * 0.001f for millimetres).  0 stays 0 (invalid).
+ * depth_scale must be finite and > 0, depth_op one of the two, depth steps are in BYTES (>= 2 * width); anything else is
+ * DSM_E_INVALID before any device work.  The slot's float depth plane then holds exactly what the float upload of the
+ * host-converted frame would have written, so every kernel downstream is unchanged.  The u16 rows go up into a staging plane
+ * of the slot (pitch * height * 2 bytes per slot, allocated at the handle's first u16 call) and one kernel per call converts
+ * them into the slot, on the stream of the copy, before whatever says the upload has landed.  Rows at the slot pitch
+ * (depth_step = 2 * dsm_frame_pitch) are the fast layout; tight rows (2 * width) are taken too. ---- */
+#define DSM_DEPTH_U16_DIVIDE 0
+#define DSM_DEPTH_U16_MULTIPLY 1
+/* dsm_frame_upload with u16 depth: synchronous, on the upload stream with DSM_FLAG_UPLOAD_STREAM */
+int dsm_frame_upload_u16(dsm_handle *h, int slot, const uint8_t *image, size_t img_step, const uint16_t *depth, size_t depth_step,
+                         float depth_scale, int32_t depth_op);
+/* dsm_frame_upload_device with u16 depth (device memory; the kernel reads it in place when the pointer and step are even) */
+int dsm_frame_upload_device_u16(dsm_handle *h, int slot, const void *image_dev, size_t img_step, const void *depth_dev, size_t depth_step,
+                                float depth_scale, int32_t depth_op);
+/* dsm_frame(s)_upload_async with u16 depth: the same slot-ordering contract, the upload's event is recorded behind the conversion */
+int dsm_frame_upload_async_u16(dsm_handle *h, int slot, const uint8_t *image, size_t img_step, const uint16_t *depth, size_t depth_step,
+                               float depth_scale, int32_t depth_op);
+int dsm_frames_upload_async_u16(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
+                                const uint16_t *depth, size_t depth_step, size_t depth_frame_step, float depth_scale, int32_t depth_op);
+/* dsm_replay_enqueue_host with u16 depth: each group's depth is converted on the stream that runs its superpixel stages, right
+ * behind its copy.  Frame f still goes to slot f mod pipeline_depth, overwriting what that slot held, as in the float form. */
+int dsm_replay_enqueue_host_u16(dsm_handle *h, int32_t n, const uint8_t *image, size_t img_step, size_t img_frame_step, const uint16_t *depth,
+                                size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16,
+                                const float *inv_poses16 /* may be NULL */, float depth_scale, int32_t depth_op);
+/* dsm_host_pack_frames with u16 depth planes (copied as they are: the conversion happens on the device) */
+int dsm_host_pack_frames_u16(int32_t n, int32_t width, int32_t height, const uint8_t *const *images, const size_t *image_steps,
+                             const uint16_t *const *depths, const size_t *depth_steps, uint8_t *dst_image, size_t dst_img_step,
+                             size_t dst_img_frame_step, uint16_t *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step);
+/* debug tap: the planes of frame slot `slot` as the kernels read them, tight rows (image: height * width bytes, depth: height *
+ * width floats); either output may be NULL.  Comes behind everything enqueued for the handle and the uploads that wrote the slot
+ * (synchronises). */
+int dsm_debug_get_frame(dsm_handle *h, int slot, uint8_t *image, float *depth);
+
 /* enqueue SurfelMap::fuse_map for the frame in `slot` against the resident map */
 int dsm_fuse_frame_resident(dsm_handle *h, int slot, int reference_frame_index, const float *pose16);
 /* enqueue n frames: frame i uses slots[i], ref_idx[i], poses16[16*i .. 16*i+16) */

@@ -77,6 +77,11 @@ int dsm_surfel_map_image_input(dsm_surfel_map *m, dsm_stamp stamp, int32_t width
 /* SurfelMap::depth_input (:93-101): TYPE_32FC1, metres, 0 = invalid. */
 int dsm_surfel_map_depth_input(dsm_surfel_map *m, dsm_stamp stamp, int32_t width, int32_t height, size_t step,
                                const char *encoding, const void *data);
+/* The same for a sensor's own depth: TYPE_16UC1 (or mono16), converted to metres on the device as dsm_frame_upload_u16 does
+ * (include/dsm.h: depth_scale finite > 0, depth_op DSM_DEPTH_U16_DIVIDE or DSM_DEPTH_U16_MULTIPLY; ROS drivers' millimetres:
+ * 0.001f, DSM_DEPTH_U16_MULTIPLY).  The frame waits for its pose at 2 bytes a pixel. */
+int dsm_surfel_map_depth_input_u16(dsm_surfel_map *m, dsm_stamp stamp, int32_t width, int32_t height, size_t step,
+                                   const char *encoding, const uint16_t *data, float depth_scale, int32_t depth_op);
 /* SurfelMap::orb_results_input (:205-365).
  *   loop_stamp       header.stamp of the sensor_msgs/PointCloud (it becomes the fuse stamp, :363)
  *   loop_values      channels[0].values: flat pairs of keyframe indices, as float32

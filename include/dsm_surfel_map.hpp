@@ -146,6 +146,13 @@ class SurfelMap {
                                                 (int32_t)depth_input->height, (size_t)depth_input->step,
                                                 depth_input->encoding.c_str(), depth_input->data.data()));
     }
+    // a sensor's uint16 depth (16UC1: Kinect / RealSense drivers in millimetres -> (0.001f, DSM_DEPTH_U16_MULTIPLY); TUM PNGs ->
+    // (5000, DSM_DEPTH_U16_DIVIDE)), converted to metres on the device -- no cv_bridge conversion on the callback thread
+    template <typename ImagePtr> int depth_input_u16(const ImagePtr &depth_input, float scale, int op = DSM_DEPTH_U16_DIVIDE) {
+        return check(dsm_surfel_map_depth_input_u16(m_, stamp_of(depth_input->header.stamp), (int32_t)depth_input->width,
+                                                    (int32_t)depth_input->height, (size_t)depth_input->step, depth_input->encoding.c_str(),
+                                                    reinterpret_cast<const uint16_t *>(depth_input->data.data()), scale, (int32_t)op));
+    }
     template <typename PointCloudPtr, typename PathPtr, typename OdometryPtr>
     int orb_results_input(const PointCloudPtr &loop_stamp_input, const PathPtr &loop_path_input, const OdometryPtr &this_pose_input) {
         std::vector<dsm_pose_msg> path(loop_path_input->poses.size());
@@ -248,6 +255,9 @@ class SurfelMap {
 
     void image_input(const sensor_msgs::ImageConstPtr &image_input) { report(impl_.image_input(image_input), "image_input"); }
     void depth_input(const sensor_msgs::ImageConstPtr &image_input) { report(impl_.depth_input(image_input), "depth_input"); }
+    void depth_input_u16(const sensor_msgs::ImageConstPtr &image_input, float scale, int op = DSM_DEPTH_U16_DIVIDE) {
+        report(impl_.depth_input_u16(image_input, scale, op), "depth_input_u16");
+    }
     void orb_results_input(const sensor_msgs::PointCloudConstPtr &loop_stamp_input, const nav_msgs::PathConstPtr &loop_path_input,
                            const nav_msgs::OdometryConstPtr &this_pose_input) {
         report(impl_.orb_results_input(loop_stamp_input, loop_path_input, this_pose_input), "orb_results_input");
