@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the per-frame surfel-fusion hot path (BASELINE.json: depth frames fused/sec @ 1226x370).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--frames-per-step F] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--frames-per-step F] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline alone: it renders the inputs, sets up, warms up, times the K steps, writes --dump-outputs
+and prints its line.  --full adds everything else the benchmark measures or checks: per-kernel and roofline figures, the legs
+beside the headline (other sizes, inputs and configurations), the CPU baseline, the check of the timed run against the CPU
+oracle and the RCCL merge of the final clouds at --gpus 1.
 
 Workload (config.workload): BASELINE configs[1] -- synthetic KITTI-shaped replay, 1226x370, one frame
 = SLIC superpixels + normals/plane fit + projective fuse + new surfels + map compaction
@@ -12,7 +17,7 @@ every subsequence of the rank by F frames, so a step fuses B*F frames per GPU.  
 data path (weak scaling: work per GPU is fixed); the final clouds are merged once, outside the timed
 region, with an RCCL all-gather.
 
-The CPU baseline replays subsequence 0 of rank 0 from its first frame and is timed over the SAME frame
+The CPU baseline (--full) replays subsequence 0 of rank 0 from its first frame and is timed over the SAME frame
 indices, against the same map state, as the GPU's timed region (a bounded prefix of it when the region is long).
 
 Prints ONE JSON line on rank 0.
@@ -211,6 +216,104 @@ def cpu_model():
     return "unknown"
 
 
+def host_cpus():
+    """CPUs this process may keep busy: its affinity mask, capped by OMP_NUM_THREADS where that is set (a share of a
+    larger machine)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "0")) or n)
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+def render_frame(cam, scene, t):
+    """synth.render(cam, scene, t)[:2] for the headline's kind of scene (no stereo, TUM or grey-level options), bit for
+    bit, in about a third of the time: every box is intersected only over the pixels whose rays can reach it -- the rectangle
+    around its projected corners, two pixels wider on every side -- and over the whole image when a corner lies behind
+    the camera.  Every pixel goes through the same float64 operations in the same order as in synth.render; a pixel
+    outside a box's rectangle would have failed that box's hit test there.  Parity: tests/test_cpu.py::test_bench_render_frame_matches_synth."""
+    from densesurfelmapping_amd import synth
+    if scene.tum or scene.stereo or scene.intensity_levels > 0 or scene.saturate_above > 0:
+        raise ValueError("render_frame renders the headline's scenes; synth.render renders the others")
+    W, H = cam.width, cam.height
+    pose = scene.pose(t)
+    tl = t % scene.frames_per_period
+    P = pose.astype(np.float64)
+    org = np.array([P[0, 3], P[1, 3], scene.step * tl * scene.scale])
+    R = P[:3, :3]
+    u = (np.arange(W, dtype=np.float64) - cam.cx) / cam.fx
+    v = (np.arange(H, dtype=np.float64) - cam.cy) / cam.fy
+    dx_c = np.broadcast_to(u[None, :], (H, W))
+    dy_c = np.broadcast_to(v[:, None], (H, W))
+    dx = R[0, 0] * dx_c + R[0, 1] * dy_c + R[0, 2]
+    dy = R[1, 0] * dx_c + R[1, 1] * dy_c + R[1, 2]
+    dz = R[2, 0] * dx_c + R[2, 1] * dy_c + R[2, 2]
+    sc = scene.scale
+    best = np.full((H, W), np.inf)
+    albedo = np.zeros((H, W))
+    to_cam = np.linalg.inv(R).T  # world offset (row) -> camera-frame ray (u t, v t, t)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tg = (1.65 * sc - org[1]) / dy
+        ok = (dy > 1e-9) & (tg > 0)
+        best = np.where(ok, tg, best)
+        albedo = np.where(ok, 110.0, albedo)
+        for sign, alb in ((-1.0, 150.0), (1.0, 90.0)):
+            tw = (sign * 6.0 * sc - org[0]) / dx
+            yh = org[1] + tw * dy
+            ok = (tw > 0) & (yh > -3.0 * sc) & (yh < 1.65 * sc) & (tw < best)
+            best = np.where(ok, tw, best)
+            albedo = np.where(ok, alb, albedo)
+        bx = scene.boxes()
+        for k in range(3):
+            for b in bx:
+                lo = np.array([b[0], b[2], b[3] + k * scene.period * sc])
+                hi = np.array([b[1], 1.65 * sc, b[4] + k * scene.period * sc])
+                q = (np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])]) - org) @ to_cam
+                r0, r1, c0, c1 = 0, H, 0, W
+                if (q[:, 2] > 1e-3).all():
+                    pu, pv = cam.fx * q[:, 0] / q[:, 2] + cam.cx, cam.fy * q[:, 1] / q[:, 2] + cam.cy
+                    c0, c1 = max(0, int(np.floor(pu.min())) - 2), min(W, int(np.ceil(pu.max())) + 3)
+                    r0, r1 = max(0, int(np.floor(pv.min())) - 2), min(H, int(np.ceil(pv.max())) + 3)
+                    if c0 >= c1 or r0 >= r1:
+                        continue
+                win = (slice(r0, r1), slice(c0, c1))
+                dxw, dyw, dzw, bw = dx[win], dy[win], dz[win], best[win]
+                t0x, t1x = (lo[0] - org[0]) / dxw, (hi[0] - org[0]) / dxw
+                t0y, t1y = (lo[1] - org[1]) / dyw, (hi[1] - org[1]) / dyw
+                t0z, t1z = (lo[2] - org[2]) / dzw, (hi[2] - org[2]) / dzw
+                tn = np.maximum(np.maximum(np.minimum(t0x, t1x), np.minimum(t0y, t1y)), np.minimum(t0z, t1z))
+                tf = np.minimum(np.minimum(np.maximum(t0x, t1x), np.maximum(t0y, t1y)), np.maximum(t0z, t1z))
+                ok = (tn <= tf) & (tn > 0) & (tn < bw)
+                best[win] = np.where(ok, tn, bw)
+                albedo[win] = np.where(ok, b[5], albedo[win])
+    hit = np.isfinite(best) & (best * 1.0 < scene.max_depth * sc)
+    tt = np.where(hit, best, 0.0)
+    wx = org[0] + tt * dx
+    wy = org[1] + tt * dy
+    wz = org[2] + tt * dz
+    cell = (np.floor(wx / sc + 1000.0) + np.floor(wy / sc + 1000.0) + np.floor(wz / sc + 1000.0)).astype(np.int64)
+    chk = np.where(cell & 1, scene.checker, -scene.checker)
+    pix = (np.arange(H * W, dtype=np.uint32)).reshape(H, W)
+    salt = scene.seed * 2654435761 + tl * 40503
+    n_int = synth._uniform01(pix, salt + 1) * scene.intensity_noise
+    img = np.where(hit, albedo + chk + n_int, 200.0 + n_int)
+    image = np.clip(np.floor(img), 0, 255).astype(np.uint8)
+    n_d = synth._uniform01(pix, salt + 2) - 0.5
+    depth = tt * (1.0 + scene.depth_noise * n_d)
+    holes = synth._uniform01(pix, salt + 3) < scene.hole_fraction
+    return image, np.where(hit & ~holes, depth, 0.0).astype(np.float32)
+
+
+def render_periods(cam, scenes, period, threads):
+    """[scene][i] -> (image, depth) of frames 0 .. period - 1 of every scene (render_frame on a pool of threads: numpy
+    drops the GIL inside its array operations).  In memory: nothing is read from or left for another run."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        frames = list(ex.map(lambda j: render_frame(cam, scenes[j // period], j % period), range(len(scenes) * period)))
+    return [frames[s * period:(s + 1) * period] for s in range(len(scenes))]
+
+
 def canon_bytes(a: np.ndarray) -> bytes:
     """the bytes of a surfel array with every NaN replaced by one canonical NaN (the reference's arithmetic does not
     define a NaN's sign or payload; everything else is compared bit for bit)"""
@@ -277,7 +380,7 @@ def oracle_replay_worker(spec_json):
     cam = getattr(synth, spec["camera"])
     scene = synth.Scene(seed=spec["seed"], frames_per_period=spec["period"])
     per = spec["period"]
-    frames = synth.render_many([(cam, scene, i) for i in range(per)], workers=1)  # (rendered and cached by the parent already)
+    frames = render_periods(cam, [scene], per, 1)[0]
     orc, lo = PortOracle(cam), np.zeros(0, O_DTYPE)
     for t in range(spec["frames"]):  # (keyframe indices count from the subsequence's first frame; `phase` = where in the scene it starts)
         img, dep = frames[(t + spec["phase"]) % per]
@@ -432,11 +535,13 @@ def open_group(args, world, rank, local_rank):
     one_device = os.environ.get("DSM_BENCH_ONE_DEVICE", "0") == "1"
     device = 0 if (world == 1 or one_device) else local_rank
     torch.cuda.set_device(device)
-    # At --gpus 1 too (a group of one on a loopback port): the merge of the final clouds then goes through RCCL on the one GPU
-    # -- ncclCommInitRank, the all-gather of the counts, the all-gather of the padded cloud -- exactly as it does on a node;
-    # nothing of it is inside the timed region.
+    # At --gpus 1 --full too (a group of one on a loopback port): the merge of the final clouds then goes through RCCL on the
+    # one GPU -- ncclCommInitRank, the all-gather of the counts, the all-gather of the padded cloud -- exactly as it does on a
+    # node; nothing of it is inside the timed region.
     dist, group_error = None, None
-    if world > 1 or not args.no_rccl_world1:
+    if world == 1 and not args.full:
+        group_error = "the merge of the final clouds through RCCL at --gpus 1 runs with --full"
+    elif world > 1 or not args.no_rccl_world1:
         from densesurfelmapping_amd.replay import init_collective
         try:
             with stdout_to_stderr():
@@ -627,18 +732,23 @@ def main():
                     help="host threads enqueueing graph replays (each drives streams/threads handles)")
     ap.add_argument("--pipeline-depth", type=int, default=int(os.environ.get("DSM_BENCH_PIPELINE_DEPTH", "0")),
                     help="frames of one subsequence whose superpixel stages may be in flight (0 = 1: the B subsequences already fill the queues)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the legs beside the headline (drop-in, configs 4 and 5, node)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the check of the timed form against the CPU oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures or checks beside the headline: per-kernel and roofline figures, the legs "
+                         "beside the headline, the CPU baseline, the check of the timed run against the CPU oracle and the RCCL merge of "
+                         "the final clouds at --gpus 1 (each can be left out with the --no-* options below).  Without "
+                         "it a run sets up, warms up, times its steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-kernel and roofline figures")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the legs beside the headline (drop-in, configs 4 and 5, node)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the check of the timed form against the CPU oracle")
     ap.add_argument("--legs", default=os.environ.get("DSM_BENCH_LEGS", "all"),
-                    help="comma-separated legs beside the headline to run (single_sequence, dropin, fullhd, live, node, kitti_like, "
+                    help="--full: comma-separated legs beside the headline to run (single_sequence, dropin, fullhd, live, node, kitti_like, "
                          "streamed, sharded_replay, bounded_map, tum_like); default all")
     ap.add_argument("--workload", choices=("headline", "sharded"), default=os.environ.get("DSM_BENCH_WORKLOAD", "headline"),
                     help="headline: BASELINE configs[1], batched resident subsequences (weak scaling); sharded: BASELINE configs[2] itself -- ONE "
                          "subsequence per GPU streamed from page-locked host memory through replay.HipEngine, all-gather of the final clouds")
     ap.add_argument("--no-rccl-world1", action="store_true",
-                    help="--gpus 1: do not create the process group of one through which the final cloud merge runs on RCCL")
+                    help="--full --gpus 1: do not create the process group of one through which the final cloud merge runs on RCCL")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps write the final maps they left (rank 0: a fixed sample of its subsequences) as "
                          "DIR/map_s<b>.npy, float32 (n, 11) in SURFEL_DTYPE field order with NaN / inf as 0, and "
@@ -649,6 +759,8 @@ def main():
         sys.exit("bench.py: --steps must be >= 1")
     if args.frames_per_step <= 0:
         args.frames_per_step = 48 if args.workload == "sharded" else 32
+    if not args.full:  # the headline alone (a multi-rank run keeps its process group: barriers and the slowest rank's time)
+        args.no_cpu_baseline = args.no_roofline = args.no_dropin = args.no_verify = args.no_rccl_world1 = True
 
     if args.oracle_replay_worker:
         oracle_replay_worker(args.oracle_replay_worker)
@@ -674,7 +786,8 @@ def main():
     legs = set(args.legs.split(","))
     leg_on = lambda name: extras and ("all" in legs or name in legs)  # noqa: E731
 
-    # ---- all synthetic frames first, on worker processes (fresh interpreters, clean environment; cached in /tmp)
+    # ---- all synthetic frames first: the headline's on a pool of threads, in memory; those of the legs beside it (--full) on
+    # worker processes (fresh interpreters, clean environment; cached in /tmp)
     from densesurfelmapping_amd import synth
     cam = synth.KITTI_1226
     n_seed = (cam.width // 8) * (cam.height // 8)
@@ -685,7 +798,7 @@ def main():
     scenes = [synth.Scene(seed=12345 + 1000 * rank + 17 * b, frames_per_period=period) for b in range(n_scene)]
     scene_of = [b % n_scene for b in range(B)]
     phase_of = [(b // n_scene) * (period // 2) % period for b in range(B)]
-    jobs = [(cam, scenes[b], i) for b in range(n_scene) for i in range(period)]
+    jobs = []
     cam_v, scene_v = synth.VGA_RGBD, synth.Scene(seed=5, scale=0.12, step=0.05, frames_per_period=30)
     cam_h, scene_h = synth.FULLHD, synth.Scene(seed=12345, frames_per_period=10)
     # the reference's own kind of input (kitti_publisher/scripts/publisher.py:37-40): depth = bf / quantised disparity, +inf where
@@ -706,14 +819,14 @@ def main():
     n_before_t = len(jobs)
     if tum_on:
         jobs += [(cam_v, sc_, i) for sc_ in scenes_t + scenes_ts for i in range(period_t)]
-    workers = max(1, min(48, (os.cpu_count() or 2) // (2 * max(world, 1))))
+    cpus = max(1, host_cpus() // max(world, 1))  # (the ranks of a node render at the same time)
     t_r = time.perf_counter()
-    frames_all = synth.render_many(jobs, workers)
+    rendered = render_periods(cam, scenes, period, cpus)
+    frames_all = synth.render_many(jobs, cpus) if jobs else []
     render_s = time.perf_counter() - t_r
-    rendered = [frames_all[b * period:(b + 1) * period] for b in range(n_scene)]
-    frames_v = frames_all[n_scene * period:n_scene * period + 30] if extras else []
-    frames_h = frames_all[n_scene * period + 30:n_scene * period + 40] if extras else []
-    rendered_k = [frames_all[n_scene * period + 40 + b * period:n_scene * period + 40 + (b + 1) * period] for b in range(n_scene_k)] if extras else []
+    frames_v = frames_all[:30] if extras else []
+    frames_h = frames_all[30:40] if extras else []
+    rendered_k = [frames_all[40 + b * period:40 + (b + 1) * period] for b in range(n_scene_k)] if extras else []
     rendered_t = [frames_all[n_before_t + b * period_t:n_before_t + (b + 1) * period_t] for b in range(2 * n_scene_k)] if tum_on else []
 
     # The checker of the timed region, started now so that it runs beside everything below: the CPU oracle replays one

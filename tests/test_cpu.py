@@ -1079,6 +1079,28 @@ def test_bench_dump_encoding_is_finite_and_lossless(tmp_path):
         assert np.load(tmp_path / "a" / f).tobytes() == np.load(tmp_path / "b" / f).tobytes(), f
 
 
+def test_bench_render_frame_matches_synth():
+    """bench.py renders the headline's frames itself (render_frame: every box intersected only where its rays can land):
+    bit for bit synth.render's frames -- the scenes of rank 0 and rank 1 of the headline across their period, frames where a
+    box lies beside or behind the camera included, and a scene at another scale and camera."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from densesurfelmapping_amd import synth
+    cases = [(synth.KITTI_1226, synth.Scene(seed=12345 + 1000 * rank + 17 * b, frames_per_period=50), t)
+             for rank, b, t in ((0, 0, 0), (0, 0, 49), (0, 2, 48), (0, 5, 17), (0, 15, 33), (1, 3, 7), (1, 11, 25))]
+    cases.append((synth.VGA_RGBD, synth.Scene(seed=5, scale=0.12, step=0.05, frames_per_period=30), 11))
+    for cam, scene, t in cases:
+        image, depth = bench.render_frame(cam, scene, t)
+        ref_image, ref_depth, _ = synth.render(cam, scene, t)
+        assert image.dtype == np.uint8 and depth.dtype == np.float32 and image.shape == depth.shape == (cam.height, cam.width)
+        assert image.tobytes() == ref_image.tobytes() and depth.tobytes() == ref_depth.tobytes(), (cam, scene.seed, t)
+    with pytest.raises(ValueError):
+        bench.render_frame(synth.KITTI_1226, synth.Scene(stereo=True), 0)
+    frames = bench.render_periods(synth.TINY, [synth.Scene(seed=1, frames_per_period=3), synth.Scene(seed=2, frames_per_period=3)], 3, 2)
+    assert [len(f) for f in frames] == [3, 3]
+    assert frames[1][2][1].tobytes() == synth.render(synth.TINY, synth.Scene(seed=2, frames_per_period=3), 2)[1].tobytes()
+
+
 def test_bench_gpus_flag_fails_loudly_without_devices():
     """`python bench.py --gpus 2` where two GPUs are not visible (this container: none) exits non-zero and prints no result
     line -- round 2's bench ran ONE rank and reported n_gpus 1 (missing #1)."""

@@ -1224,7 +1224,7 @@ def test_bench_ranks_on_one_gpu(world, workload):
         extra = ["--workload", "sharded", "--steps", "3", "--warmup", "1", "--frames-per-step", "24" if world == 2 else "13", "--no-roofline"]
     # (at most three ranks: with the test process and torch.distributed.run's agent that stays within the six processes
     # a shared machine lets hold one GPU)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world)] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full"] + extra,
                        env=env, capture_output=True, text=True, timeout=900)
     out = _bench_line(r)
     assert out["n_gpus"] == world and out["scaling"] == "weak" and out["value"] > 0
@@ -1309,7 +1309,7 @@ def test_merge_clouds_through_rccl_on_one_gpu(tmp_path):
     head = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert head["backend"] == "nccl" and head["merged_surfels"] == head["surfels"] > 0 and head["counts"] == [head["surfels"]]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--streams", "8", "--batches", "1",
-                        "--frames-per-step", "8", "--no-roofline", "--no-dropin", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--frames-per-step", "8", "--full", "--no-roofline", "--no-dropin", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     out = _bench_line(r)
     mg = out["multi_gpu"]
     assert mg["backend"] == "nccl" and mg["world_size_seen_by_backend"] == 1 and mg["final_cloud_all_gather_ms"] > 0, mg
@@ -1343,7 +1343,7 @@ def test_bench_sharded_workload_one_gpu():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DSM_BENCH_ONE_DEVICE", "DSM_BENCH_BACKEND")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "sharded", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "sharded", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     out = _bench_line(r)
     assert out["config"]["workload"].startswith("BASELINE configs[2]") and out["config"]["timed_frames_per_rank"] == 144
@@ -1383,6 +1383,35 @@ def test_bench_dump_outputs_are_repeatable(tmp_path):
         assert dumps[0][f].tobytes() == dumps[1][f].tobytes(), f
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py` without --full measures the headline and nothing else: its line has the headline's fields and none of what
+    --full adds (per-kernel and roofline figures, the legs, the CPU baseline, the oracle's verdict, the merge at --gpus 1),
+    and its dumped maps are those of a --full run with the same arguments."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DSM_BENCH_ONE_DEVICE", "DSM_BENCH_BACKEND")}
+    args = ["--steps", "2", "--warmup", "1", "--streams", "8", "--batches", "2", "--frames-per-step", "4"]
+    lines = {}
+    for mode in ("plain", "full"):
+        extra = [] if mode == "plain" else ["--full", "--no-roofline", "--no-dropin", "--no-cpu-baseline"]
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra + ["--dump-outputs", str(tmp_path / mode)],
+                           env=env, capture_output=True, text=True, timeout=900)
+        lines[mode] = _bench_line(r)
+    out = lines["plain"]
+    assert out["metric"] == "depth frames fused/sec @ KITTI 1226x370" and out["unit"] == "frames/s" and out["dtype"] == "f32"
+    assert out["higher_is_better"] is True and out["value"] > 0 and out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    extras = {"roofline", "kernel_us", "cpu_baseline", "verification", "verified", "single_sequence", "dropin_pcie_inclusive",
+              "fullhd_2M", "kitti_like", "tum_like", "streamed_input", "bounded_map"}
+    assert not extras & out.keys(), extras & out.keys()
+    assert out["multi_gpu"]["backend"] is None and "--full" in out["multi_gpu"]["note"]
+    full = lines["full"]
+    assert full["verified"] is True and full["multi_gpu"]["backend"] == "nccl"
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files and files == sorted(os.listdir(tmp_path / "full"))
+    for f in files:
+        assert np.load(tmp_path / "plain" / f).tobytes() == np.load(tmp_path / "full" / f).tobytes(), f
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """`python bench.py --gpus N` on a box with fewer than N devices must fail loudly -- not run one GPU and print n_gpus 1."""
     import subprocess
@@ -1413,7 +1442,7 @@ def test_bench_two_gpus_rccl():
     if not two:
         env.update(DSM_BENCH_BACKEND="gloo", DSM_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--streams", "8",
-                        "--batches", "1", "--frames-per-step", "8", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--batches", "1", "--frames-per-step", "8", "--full", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
     out = _bench_line(r)
     mg = out["multi_gpu"]
     assert out["n_gpus"] == 2 and mg["backend"] == ("nccl" if two else "gloo") and mg["world_size_seen_by_backend"] == 2

@@ -21,7 +21,7 @@ for n in 1 2 4; do
 done
 for v in shipped lanes; do
   cp /tmp/wl_$v.so $L
-  python bench.py --steps 6 --warmup 2 --legs single_sequence --no-cpu-baseline --no-roofline --no-verify --no-rccl-world1 2>/dev/null | python -c "
+  python bench.py --steps 6 --warmup 2 --full --legs single_sequence --no-cpu-baseline --no-roofline --no-verify --no-rccl-world1 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline())
 print('| one sequence, frame groups: depth 16 = groups of 4, 24 / 32 = groups of 8 (lane forms either way) | $v |', d['single_sequence']['frames_per_s_by_pipeline_depth'], '|')"
