@@ -237,7 +237,9 @@ class FusionFunctions:
 
     # fusion_functions.h:84-87; the keyword arguments are what an HBM-resident engine adds
     def initialize(self, width, height, fx, fy, cx, cy, far_dist, near_dist, *, rgbd=False, device=0,
-                   surfel_capacity=0, frame_slots=0, flags=0, pipeline_depth=0):
+                   surfel_capacity=0, frame_slots=0, flags=0, pipeline_depth=0, constants=None):
+        """constants: (huber_range, baseline, disparity_error, min_tolerate_diff) in place of the set `rgbd` selects
+        (struct dsm_config, include/dsm.h); None keeps that set."""
         self.close()
         cfg = _Config()
         rc = self._lib.dsm_config_init(C.byref(cfg), width, height, fx, fy, cx, cy, far_dist, near_dist,
@@ -246,6 +248,8 @@ class FusionFunctions:
             raise DsmError(rc, "dsm_config_init")
         cfg.device, cfg.surfel_capacity, cfg.frame_slots, cfg.flags = device, surfel_capacity, frame_slots, flags
         cfg.pipeline_depth = pipeline_depth
+        if constants is not None:
+            cfg.huber_range, cfg.baseline, cfg.disparity_error, cfg.min_tolerate_diff = (float(v) for v in constants)
         h = _vp()
         rc = self._lib.dsm_create(C.byref(cfg), C.byref(h))
         if rc:

@@ -196,7 +196,9 @@ class RefOracle(_Base):
 class PortOracle(_Base):
     prefix = "dsmo_"
 
-    def __init__(self, cam, threads=1):
+    def __init__(self, cam, threads=1, constants=None, eigen33=False):
+        """constants: (huber_range, baseline, disparity_error, min_tolerate_diff) in place of the camera's set;
+        eigen33: the 3x3 * 3x1 products in Eigen >= 3.3's order (the product's DSM_FLAG_EIGEN33_PRODUCTS)."""
         lib = C.CDLL(os.path.join(HERE, "liboracle_port.so"))
         lib.dsmo_set_constants.argtypes = [_vp, C.c_double, C.c_double, C.c_double, C.c_double]
         lib.dsmo_fuse_initialize_map_inv.restype = C.c_int
@@ -207,6 +209,11 @@ class PortOracle(_Base):
         super().__init__(lib, cam)
         if cam.rgbd:
             lib.dsmo_set_constants(self.h_, 0.05, 0.08, 1.0, 0.05)  # fusion_functions.h:17-21
+        if constants is not None:
+            lib.dsmo_set_constants(self.h_, *(float(v) for v in constants))
+        if eigen33:
+            lib.dsmo_set_eigen33_products.argtypes = [_vp, C.c_int]
+            lib.dsmo_set_eigen33_products(self.h_, 1)
 
 
 class RefSurfelMap:

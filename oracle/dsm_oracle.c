@@ -21,6 +21,7 @@ struct dsmo_ctx {
     int w, h, gw, gh, n_seed;
     float fx, fy, cx, cy, far_d, near_d;
     double huber, baseline, disp_err, min_tol;
+    int e33; /* 3x3 * 3x1 products in Eigen >= 3.3's order, dsmo_set_eigen33_products */
     const uint8_t *img;
     size_t img_step;
     const float *dep;
@@ -71,6 +72,8 @@ void dsmo_destroy(dsmo_ctx *c) {
 void dsmo_set_constants(dsmo_ctx *c, double huber, double baseline, double disparity_error, double min_tolerate) {
     c->huber = huber; c->baseline = baseline; c->disp_err = disparity_error; c->min_tol = min_tolerate;
 }
+
+void dsmo_set_eigen33_products(dsmo_ctx *c, int on) { c->e33 = on != 0; }
 
 void dsmo_set_frame(dsmo_ctx *c, const uint8_t *img, size_t img_step, const float *depth, size_t depth_step) {
     c->img = img; c->img_step = img_step; c->dep = depth; c->dep_step = depth_step;
@@ -407,6 +410,16 @@ static inline void xform_point(const float *m, const float *p, float *o) { /* 4x
 static inline void xform_dir(const float *m, const float *v, float *o) { /* block<3,3> * v, FF.cpp:228 */
     for (int i = 0; i < 3; i++) o[i] = (m[i] * v[0] + m[4 + i] * v[1]) + m[8 + i] * v[2];
 }
+/* The same product as Eigen >= 3.3 evaluates it: a fixed 3x3 * 3x1 coefficient is the redux of lhs.row(i) .* rhs, split at
+ * 1 -- a0*b0 + (a1*b1 + a2*b2); Eigen 3.2 (xform_dir) accumulates left to right.  Checked against the fixtures recorded from
+ * the reference built with an Eigen >= 3.3 stand-in (tests/golden/eigen33_golden.json). */
+static inline void xform_dir_e33(const float *m, const float *v, float *o) {
+    for (int i = 0; i < 3; i++) o[i] = m[i] * v[0] + (m[4 + i] * v[1] + m[8 + i] * v[2]);
+}
+static inline void xform_dir_of(const dsmo_ctx *c, const float *m, const float *v, float *o) {
+    if (c->e33) xform_dir_e33(m, v, o);
+    else xform_dir(m, v, o);
+}
 static inline float depth_weight(float d) { /* FF.cpp:99-102 */
     double w = 1.0 / (double)d / (double)d;
     return (float)(1.0 < w ? 1.0 : w); /* std::min(w, 1.0): a NaN w is returned as is */
@@ -421,7 +434,7 @@ static void fuse_local(dsmo_ctx *c, int ref_idx, const float *pose, const float 
         float pw[3] = {e->px, e->py, e->pz}, pc[3], nw[3] = {e->nx, e->ny, e->nz}, nc[3];
         xform_point(inv, pw, pc);
         if (pc[2] < c->near_d || pc[2] > c->far_d) continue;
-        xform_dir(inv, nw, nc);
+        xform_dir_of(c, inv, nw, nc);
         float u = pc[0] * c->fx / pc[2] + c->cx, v = pc[1] * c->fy / pc[2] + c->cy; /* FF.cpp:85-89 */
         double ud = (double)u + 0.5, vd = (double)v + 0.5;
         /* int(x) of NaN/out-of-range is INT_MIN on x86-64; either way the bounds test below rejects */
@@ -447,7 +460,7 @@ static void fuse_local(dsmo_ctx *c, int ref_idx, const float *pose, const float 
         double len = (double)sqrtf(fn[0] * fn[0] + fn[1] * fn[1] + fn[2] * fn[2]);
         fn[0] = (float)((double)fn[0] / len); fn[1] = (float)((double)fn[1] / len); fn[2] = (float)((double)fn[2] / len);
         float fw[3];
-        xform_dir(pose, fn, fw);
+        xform_dir_of(c, pose, fn, fw);
         e->px = fpx; e->py = fpy; e->pz = fpz;
         e->nx = fw[0]; e->ny = fw[1]; e->nz = fw[2];
         e->weight = ws;
@@ -471,7 +484,7 @@ static int spawn_surfels(dsmo_ctx *c, int ref_idx, const float *pose, dsmo_surfe
         if (sd->norm_x == 0 && sd->norm_y == 0 && sd->norm_z == 0) continue;
         float pc[3] = {sd->posi_x, sd->posi_y, sd->posi_z}, nc[3] = {sd->norm_x, sd->norm_y, sd->norm_z}, pw[3], nw[3];
         xform_point(pose, pc, pw);
-        xform_dir(pose, nc, nw);
+        xform_dir_of(c, pose, nc, nw);
         float cam_f = (float)((double)(fabsf(c->fx) + fabsf(c->fy)) / 2.0);
         if (k >= cap) return -1;
         dsmo_surfel *e = &out[k++];

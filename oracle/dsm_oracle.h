@@ -50,6 +50,8 @@ dsmo_ctx *dsmo_create(int w, int h, float fx, float fy, float cx, float cy, floa
 void dsmo_destroy(dsmo_ctx *c);
 /* fusion_functions.h:13-21: HUBER_RANGE, BASELINE, DISPARITY_ERROR, MIN_TOLERATE_DIFF */
 void dsmo_set_constants(dsmo_ctx *c, double huber, double baseline, double disparity_error, double min_tolerate);
+/* the normals' 3x3 * 3x1 products in Eigen >= 3.3's order (a reference built against a current Eigen); default off */
+void dsmo_set_eigen33_products(dsmo_ctx *c, int on);
 
 int dsmo_fuse_initialize_map(dsmo_ctx *c, int ref_idx, const uint8_t *img, size_t img_step, const float *depth,
                              size_t depth_step, const float *pose16, dsmo_surfel *local, int n_local,

@@ -468,6 +468,20 @@ void *emu_create(int w, int h, float fx, float fy, float cx, float cy, float far
     return e;
 }
 void emu_destroy(void *p) { delete (Emu *)p; }
+// a caller's own constant set (struct dsm_config's huber_range, baseline, disparity_error, min_tolerate_diff)
+void emu_set_constants(void *p, double huber, double baseline, double disp_err, double min_tol) {
+    Emu &e = *(Emu *)p;
+    e.huber = huber; e.baseline = baseline; e.disp_err = disp_err; e.min_tol = min_tol;
+}
+// which form of fuse_depth_tolerance this configuration takes: 1 = the fp32 form, 0 = the reference's double expression
+int emu_tolerance_is_fp32(void *p) {
+    Emu &e = *(Emu *)p;
+    FuseConst fc;
+    fc.k = e.K; fc.far_d = e.far_d; fc.near_d = e.near_d;
+    fc.baseline = e.baseline; fc.disp_err = e.disp_err; fc.min_tol = e.min_tol; fc.w = e.w; fc.h = e.h;
+    fuse_const_prepare(fc);
+    return fc.tol32 ? 1 : 0;
+}
 void emu_set_order_salt(void *p, int salt) { ((Emu *)p)->order_salt = salt; }
 void emu_cert_stats(void *p, long long *out) { for (int i = 0; i < 3; i++) out[i] = ((Emu *)p)->cert_stats[i]; }
 void emu_exact_sum_stats(void *p, long long *out) { for (int i = 0; i < 5; i++) out[i] = ((Emu *)p)->exact_stats[i]; out[5] = ((Emu *)p)->exact_operand_pass; }
