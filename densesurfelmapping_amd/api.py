@@ -63,6 +63,9 @@ ABI_SYMBOLS = (
     # sensor-native uint16 depth, converted on the device
     "dsm_frame_upload_u16", "dsm_frame_upload_device_u16", "dsm_frame_upload_async_u16", "dsm_frames_upload_async_u16",
     "dsm_replay_enqueue_host_u16", "dsm_host_pack_frames_u16", "dsm_debug_get_frame",
+    # colour camera images converted to grey on the device, and the format descriptor for both halves of a frame
+    "dsm_frame_format_init", "dsm_frame_upload_fmt", "dsm_frame_upload_device_fmt", "dsm_frame_upload_async_fmt",
+    "dsm_frames_upload_async_fmt", "dsm_replay_enqueue_host_fmt", "dsm_host_pack_frames_fmt", "dsm_debug_frame_planes",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -82,6 +85,58 @@ def depth_from_u16(u, scale, op="divide") -> np.ndarray:
     s = np.float32(scale)
     with np.errstate(over="ignore"):
         return (u / s if depth_op_code(op) == DEPTH_U16_DIVIDE else u * s).astype(np.float32)
+
+
+# dsm_frame_format (include/dsm.h): image formats, and the grey weights (wr, wg, wb, shift) of
+# grey = (R * wr + G * wg + B * wb + (1 << (shift - 1))) >> shift
+IMAGE_MONO8, IMAGE_RGB8, IMAGE_BGR8, IMAGE_RGBA8, IMAGE_BGRA8 = 0, 1, 2, 3, 4
+IMAGE_FORMATS = {"mono8": IMAGE_MONO8, "rgb8": IMAGE_RGB8, "bgr8": IMAGE_BGR8, "rgba8": IMAGE_RGBA8, "bgra8": IMAGE_BGRA8}
+IMAGE_CHANNELS = {IMAGE_MONO8: 1, IMAGE_RGB8: 3, IMAGE_BGR8: 3, IMAGE_RGBA8: 4, IMAGE_BGRA8: 4}
+DEPTH_F32, DEPTH_U16 = 0, 1
+GRAY_OPENCV_14BIT = (4899, 9617, 1868, 14)   # OpenCV 2.4 / 3.x RGB2Gray<uchar> (as remembered from its source: not checked against a build); the default
+GRAY_OPENCV_15BIT = (9798, 19235, 3735, 15)  # OpenCV 4.x 8-bit path (likewise)
+GRAY_PIL_L = (19595, 38470, 7471, 16)        # Pillow's convert("L") (checked against Pillow by tests/test_cpu_color.py)
+
+
+def image_format_code(fmt) -> int:
+    """'rgb8' & co. (or the IMAGE_* code itself) -> the code; an unknown code is passed on for the library to refuse"""
+    return IMAGE_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+
+
+def image_channels(fmt) -> int:
+    return IMAGE_CHANNELS[image_format_code(fmt)]
+
+
+class _FrameFormat(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("image_format", C.c_int32), ("gray_wr", C.c_int32), ("gray_wg", C.c_int32),
+                ("gray_wb", C.c_int32), ("gray_shift", C.c_int32), ("depth_format", C.c_int32), ("depth_scale", C.c_float),
+                ("depth_op", C.c_int32)]
+
+
+def frame_format(image_format="mono8", weights=None, depth_u16=None) -> _FrameFormat:
+    """a dsm_frame_format: image_format 'mono8' / 'rgb8' / 'bgr8' / 'rgba8' / 'bgra8' (or an IMAGE_* code), weights = (wr, wg, wb,
+    shift) or None = GRAY_OPENCV_14BIT, depth_u16 = (scale, op) or None = float depth.  Nothing is checked here: the library does."""
+    wr, wg, wb, shift = GRAY_OPENCV_14BIT if weights is None else weights
+    f = _FrameFormat(C.sizeof(_FrameFormat), image_format_code(image_format), int(wr), int(wg), int(wb), int(shift), DEPTH_F32, 1.0, DEPTH_U16_DIVIDE)
+    if depth_u16 is not None:
+        f.depth_format, f.depth_scale, f.depth_op = DEPTH_U16, float(depth_u16[0]), depth_op_code(depth_u16[1])
+    return f
+
+
+def gray_from_color(image, encoding, weights=None) -> np.ndarray:
+    """Host reference of the device conversion: image uint8 [..., 3 or 4] in `encoding` ('rgb8', 'bgr8', 'rgba8', 'bgra8') ->
+    uint8 [...] grey = (R * wr + G * wg + B * wb + (1 << (shift - 1))) >> shift in exact integer arithmetic; alpha is ignored."""
+    code = image_format_code(encoding)
+    ch = IMAGE_CHANNELS[code]
+    image = np.asarray(image)
+    if ch == 1 or image.dtype != np.uint8 or image.shape[-1] != ch:
+        raise ValueError("gray_from_color: a uint8 [..., %d] image in a colour encoding" % ch)
+    wr, wg, wb, shift = (int(v) for v in (GRAY_OPENCV_14BIT if weights is None else weights))
+    if min(wr, wg, wb) < 0 or not 1 <= shift <= 22 or wr + wg + wb > (1 << shift):
+        raise ValueError("gray_from_color: weights >= 0, 1 <= shift <= 22, sum <= 1 << shift")
+    first, second, third = (image[..., k].astype(np.int64) for k in range(3))
+    r, b = (third, first) if code in (IMAGE_BGR8, IMAGE_BGRA8) else (first, third)
+    return ((r * wr + second * wg + b * wb + (1 << (shift - 1))) >> shift).astype(np.uint8)
 
 
 # dsm_cloud_compose's map part (include/dsm.h dsm_cloud_select)
@@ -203,6 +258,17 @@ def load_library():
                                                 C.c_float, C.c_int32]
     lib.dsm_host_pack_frames_u16.argtypes = [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t]
     lib.dsm_debug_get_frame.argtypes = [_vp, C.c_int, _vp, _vp]
+    lib.dsm_debug_frame_planes.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp]
+    _ff = C.POINTER(_FrameFormat)
+    lib.dsm_frame_format_init.argtypes = [_ff]
+    lib.dsm_frame_format_init.restype = None
+    lib.dsm_frame_upload_fmt.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _ff]
+    lib.dsm_frame_upload_device_fmt.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _ff]
+    lib.dsm_frame_upload_async_fmt.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _ff]
+    lib.dsm_frames_upload_async_fmt.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _ff]
+    lib.dsm_replay_enqueue_host_fmt.argtypes = [_vp, C.c_int32, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _ff]
+    lib.dsm_host_pack_frames_fmt.argtypes = [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t,
+                                             C.c_size_t, _ff]
     _lib = lib
     return lib
 
@@ -475,6 +541,10 @@ class FusionFunctions:
         one transfer per plane for all of them -- of a block with tight rows too (PinnedFrames(..., tight=True))"""
         assert 0 <= first and first + n <= pinned.n and (pinned.h, pinned.w) == (self.height, self.width) and pinned.pitch in (self.frame_pitch(), self.width)
         img, dep = pinned.image(first), pinned.depth(first)
+        if pinned.fmt is not None:  # colour images (with float or uint16 depth): PinnedFrames(..., image_format=...)
+            self._check(self._lib.dsm_frames_upload_async_fmt(self._h, slot0, n, _ptr(img), img.strides[0], pinned._bytes_img,
+                                                              _ptr(dep), dep.strides[0], pinned._bytes_dep, C.byref(pinned.fmt)))
+            return
         if pinned.depth_u16 is not None:  # uint16 depth: converted on the device (PinnedFrames(..., depth_u16=(scale, op)))
             self._check(self._lib.dsm_frames_upload_async_u16(self._h, slot0, n, _ptr(img), img.strides[0], pinned.pitch * pinned.h,
                                                               _ptr(dep), dep.strides[0], pinned.pitch * pinned.h * 2, *pinned.depth_u16_args))
@@ -515,12 +585,60 @@ class FusionFunctions:
         self._check(self._lib.dsm_frame_upload_async_u16(self._h, slot, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0],
                                                          scale, depth_op_code(op)))
 
+    def _frame_args_fmt(self, image, depth, fmt):
+        image = np.asarray(image)
+        depth = np.asarray(depth)
+        ch = IMAGE_CHANNELS.get(fmt.image_format, 1)
+        ddt = np.dtype(np.uint16 if fmt.depth_format == DEPTH_U16 else np.float32)
+        if image.dtype != np.uint8 or depth.dtype != ddt:
+            raise TypeError("image must be uint8 and depth %s" % ddt)
+        if image.shape != ((self.height, self.width) if ch == 1 else (self.height, self.width, ch)) or depth.shape != (self.height, self.width):
+            raise ValueError("image/depth shape does not match initialize() and the format")
+        if image.strides[1] != ch or (ch > 1 and image.strides[2] != 1) or image.strides[0] < self.width * ch:
+            image = np.ascontiguousarray(image)
+        if depth.strides[1] != ddt.itemsize or depth.strides[0] < self.width * ddt.itemsize:
+            depth = np.ascontiguousarray(depth)
+        return image, depth
+
+    def frame_upload_fmt(self, slot, image, depth, fmt):
+        """dsm_frame_upload_fmt: image uint8 [H,W] (mono8) or [H,W,3|4] (colour: converted to grey on the device, gray_from_color byte
+        for byte), depth float32 or uint16 [H,W], as `fmt` (frame_format(...)) says; row strides are passed on as they are"""
+        image, depth = self._frame_args_fmt(image, depth, fmt)
+        self._check(self._lib.dsm_frame_upload_fmt(self._h, slot, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0], C.byref(fmt)))
+
+    def frame_upload_device_fmt(self, slot, image_ptr, img_step, depth_ptr, depth_step, fmt):
+        self._check(self._lib.dsm_frame_upload_device_fmt(self._h, slot, _vp(image_ptr), img_step, _vp(depth_ptr), depth_step, C.byref(fmt)))
+
+    def frame_upload_async_fmt(self, slot, image, depth, fmt):
+        """dsm_frame_upload_async_fmt: views of PAGE-LOCKED memory (PinnedFrames(..., image_format=...)), untouched until
+        frame_uploads_wait()"""
+        ch = IMAGE_CHANNELS.get(fmt.image_format, 1)
+        if image.dtype != np.uint8 or image.shape[:2] != (self.height, self.width) or depth.shape != (self.height, self.width):
+            raise TypeError("image must be uint8 [H,W] or [H,W,C], depth [H,W]")
+        if image.strides[1] != ch or depth.strides[1] != depth.dtype.itemsize:
+            raise ValueError("rows must be contiguous")
+        self._check(self._lib.dsm_frame_upload_async_fmt(self._h, slot, _ptr(image), image.strides[0], _ptr(depth), depth.strides[0], C.byref(fmt)))
+
     def frame(self, slot):
         """debug tap (dsm_debug_get_frame): (image uint8 [H,W], depth float32 [H,W]) of a frame slot as the kernels read them"""
         img = np.zeros((self.height, self.width), np.uint8)
         dep = np.zeros((self.height, self.width), np.float32)
         self._check(self._lib.dsm_debug_get_frame(self._h, slot, _ptr(img), _ptr(dep)))
         return img, dep
+
+    def frame_planes(self, slot, image=None, depth=None):
+        """debug tap (dsm_debug_frame_planes): the whole pitched planes of a slot, pad columns included.  With no argument: read,
+        (image uint8 [H,pitch], depth float32 [H,pitch]); with image and / or depth of those shapes: the planes are overwritten."""
+        pitch = self.frame_pitch()
+        if image is None and depth is None:
+            img = np.zeros((self.height, pitch), np.uint8)
+            dep = np.zeros((self.height, pitch), np.float32)
+            self._check(self._lib.dsm_debug_frame_planes(self._h, slot, 0, _ptr(img), _ptr(dep)))
+            return img, dep
+        image = None if image is None else np.ascontiguousarray(image, np.uint8).reshape(self.height, pitch)
+        depth = None if depth is None else np.ascontiguousarray(depth, np.float32).reshape(self.height, pitch)
+        self._check(self._lib.dsm_debug_frame_planes(self._h, slot, 1, None if image is None else _ptr(image), None if depth is None else _ptr(depth)))
+        return None
 
     def frame_uploads_wait(self):
         self._check(self._lib.dsm_frame_uploads_wait(self._h))
@@ -565,6 +683,11 @@ class FusionFunctions:
             inv = _ptr(inv_poses_cm)
         ref_idx = np.ascontiguousarray(ref_idx, np.int32)
         poses_cm = np.ascontiguousarray(poses_cm, np.float32).reshape(n, 16)
+        if pinned.fmt is not None:
+            self._check(self._lib.dsm_replay_enqueue_host_fmt(self._h, n, _ptr(img), img.strides[0], pinned._bytes_img, _ptr(dep),
+                                                              dep.strides[0], pinned._bytes_dep, _ptr(ref_idx), _ptr(poses_cm), inv,
+                                                              C.byref(pinned.fmt)))
+            return
         if pinned.depth_u16 is not None:
             self._check(self._lib.dsm_replay_enqueue_host_u16(self._h, n, _ptr(img), img.strides[0], pinned.pitch * pinned.h, _ptr(dep),
                                                               dep.strides[0], pinned.pitch * pinned.h * 2, _ptr(ref_idx), _ptr(poses_cm), inv,
@@ -668,14 +791,27 @@ class PinnedFrames:
     """n frames in page-locked host memory (dsm_host_alloc), rows laid out with a handle's slot pitch, pad columns zero:
     image(i) / depth(i) are [H,W] views that dsm_frame_upload_async moves in one transfer per plane."""
 
-    def __init__(self, ff, n: int, tight: bool = False, depth_u16=None):
+    @staticmethod
+    def layout(height, width, tight=False, depth_u16=None, image_format=None):
+        """(pitch in pixels, bytes per image pixel, image bytes per frame, depth bytes per frame) of a block: host arithmetic only"""
+        pitch = int(width) if tight else (int(width) + 63) // 64 * 64
+        ch = 1 if image_format in (None, "mono8", IMAGE_MONO8) else image_channels(image_format)
+        return pitch, ch, pitch * int(height) * ch, pitch * int(height) * (4 if depth_u16 is None else 2)
+
+    def __init__(self, ff, n: int, tight: bool = False, depth_u16=None, image_format=None, gray_weights=None):
         """ff: a FusionFunctions (its slot layout), or a (height, width) pair -- the pitch is then the library's rule,
         ceil(width / 64) * 64 elements per row, and frames_upload_async checks it against the handle's.  tight=True: rows
         `width` elements apart, frames back to back (`pitch` = width) -- the asynchronous uploads then move no pad bytes over
         the link and set the rows to the slots' pitch on the device.  depth_u16=(scale, op): the depth planes hold the sensor's
         uint16 (2 bytes a pixel), and frames_upload_async / replay_enqueue_host send them to the *_u16 entry points, which
-        convert on the device (depth_from_u16)."""
+        convert on the device (depth_from_u16).  image_format='rgb8' / 'bgr8' / 'rgba8' / 'bgra8' (gray_weights = (wr, wg, wb, shift),
+        None = GRAY_OPENCV_14BIT): the image planes hold the camera's packed colour pixels, image(i) is a [H,W,3|4] view, rows
+        3 or 4 x pitch bytes apart, and the uploads go to the *_fmt entry points, which convert to grey on the device
+        (gray_from_color) -- together with float or uint16 depth."""
         self._lib = load_library()
+        self.image_format = None if image_format in (None, "mono8", IMAGE_MONO8) else image_format
+        self.channels = 1 if self.image_format is None else image_channels(self.image_format)
+        self.fmt = None if self.image_format is None else frame_format(self.image_format, gray_weights, depth_u16)
         self.depth_u16 = None if depth_u16 is None else (float(depth_u16[0]), depth_u16[1])
         self.depth_u16_args = None if depth_u16 is None else (self.depth_u16[0], depth_op_code(self.depth_u16[1]))
         de = 4 if depth_u16 is None else 2
@@ -686,7 +822,7 @@ class PinnedFrames:
             self.n, self.h, self.w, self.pitch = n, ff.height, ff.width, ff.frame_pitch()
         if tight:
             self.pitch = self.w
-        self._bytes_img, self._bytes_dep = self.pitch * self.h, self.pitch * self.h * de
+        self._bytes_img, self._bytes_dep = self.pitch * self.h * self.channels, self.pitch * self.h * de
         p = _vp()
         rc = self._lib.dsm_host_alloc(C.byref(p), n * (self._bytes_img + self._bytes_dep))
         if rc:
@@ -694,7 +830,7 @@ class PinnedFrames:
         self._p = p
         raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n * (self._bytes_img + self._bytes_dep),))
         raw[:] = 0
-        self._img = raw[: n * self._bytes_img].reshape(n, self.h, self.pitch)
+        self._img = raw[: n * self._bytes_img].reshape((n, self.h, self.pitch) if self.channels == 1 else (n, self.h, self.pitch, self.channels))
         self._dep = raw[n * self._bytes_img:].view(np.float32 if de == 4 else np.uint16).reshape(n, self.h, self.pitch)
 
     def image(self, i):
@@ -717,10 +853,11 @@ class PinnedFrames:
             raise ValueError("frames out of range")
         keep = []
         dt = self._dep.dtype
+        ch = self.channels
         for im, dp in zip(images, depths):
-            im = im if (im.dtype == np.uint8 and im.strides[1] == 1) else np.ascontiguousarray(im, np.uint8)
+            im = im if (im.dtype == np.uint8 and im.strides[1] == ch and (ch == 1 or im.strides[2] == 1)) else np.ascontiguousarray(im, np.uint8)
             dp = dp if (dp.dtype == dt and dp.strides[1] == dt.itemsize) else np.ascontiguousarray(dp, dt)
-            if im.shape != (self.h, self.w) or dp.shape != (self.h, self.w):
+            if im.shape != ((self.h, self.w) if ch == 1 else (self.h, self.w, ch)) or dp.shape != (self.h, self.w):
                 raise ValueError("frame size")
             keep.append((im, dp))
         ip = (C.c_void_p * n)(*[k[0].ctypes.data for k in keep])
@@ -728,9 +865,12 @@ class PinnedFrames:
         ist = (C.c_size_t * n)(*[k[0].strides[0] for k in keep])
         dst = (C.c_size_t * n)(*[k[1].strides[0] for k in keep])
         pack = self._lib.dsm_host_pack_frames if dt == np.float32 else self._lib.dsm_host_pack_frames_u16
+        more = ()
+        if self.fmt is not None:
+            pack, more = self._lib.dsm_host_pack_frames_fmt, (C.byref(self.fmt),)
         rc = pack(n, self.w, self.h, ip, ist, dp_, dst,
-                  C.c_void_p(self._img[first].ctypes.data), C.c_size_t(self.pitch), C.c_size_t(self._bytes_img),
-                  C.c_void_p(self._dep[first].ctypes.data), C.c_size_t(self.pitch * dt.itemsize), C.c_size_t(self._bytes_dep))
+                  C.c_void_p(self._img[first].ctypes.data), C.c_size_t(self.pitch * ch), C.c_size_t(self._bytes_img),
+                  C.c_void_p(self._dep[first].ctypes.data), C.c_size_t(self.pitch * dt.itemsize), C.c_size_t(self._bytes_dep), *more)
         if rc:
             raise DsmError(rc, self._lib.dsm_last_error(None).decode())
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "dsm_device.h"
+#include "dsm_frame_format.h"
 
 using namespace dsm;
 
@@ -180,6 +181,10 @@ struct dsm_handle {
     // plane is written only by uploads into slot s and read by their conversion kernel, on the same stream right behind the copy:
     // the rules that order uploads into a slot against the frames that read it cover it as well
     uint16_t *d_stage_u16 = nullptr;
+    // the *_fmt uploads of colour images: packed pixels per frame slot ([n_slots][pitch * h * 4] bytes, allocated at the handle's first
+    // colour call).  The bytes of slots [s, s + n) belong to an upload into those slots (its frames lie in them one behind the other,
+    // 3 or 4 bytes a pixel) and are read by its conversion kernel on the same stream right behind the copy, like d_stage_u16
+    uint8_t *d_stage_gray = nullptr;
     // DSM_FLAG_UPLOAD_STREAM: frames go up on a stream of their own, so that the upload of the next frame overlaps the
     // kernels of the current one; ev_slot[s] = the last frame submitted by dsm_fuse_frame_resident that reads slot s
     // has finished (recorded on the map stream).  Otherwise up_stream == stream.
@@ -556,11 +561,56 @@ int upload_depth_u16(dsm_handle *h, int slot0, int n, const void *depth, size_t 
     return DSM_OK;
 }
 
+// a colour image format and its grey weights (the *_fmt entry points of include/dsm.h; checked by dsm_fmt::parse)
+using ImageGray = dsm_fmt::Gray;
+
+// n frames of packed colour pixels (frame i at image + i * frame_step bytes, rows `step` bytes apart) converted into the grey image
+// planes of slots slot0 .. slot0 + n - 1, on `st`: the rows go into the slots' colour staging -- rows at the slot pitch and frames a
+// slot apart, or tight rows and frames back to back, as one transfer; any other layout frame by frame, row by row, at the pitch -- and
+// ONE kernel converts all n behind the copy.  Device memory is read where it is.
+int upload_image_gray(dsm_handle *h, int slot0, int n, const void *image, size_t step, size_t frame_step, hipMemcpyKind kind, const ImageGray &g,
+                      hipStream_t st) {
+    if (!h->d_stage_gray && kind != hipMemcpyDeviceToDevice) { // (no memset behind the allocation: it would race the first copy, which is on another stream)
+        void *p = nullptr;
+        HIP_TRY(h, hipMalloc(&p, (size_t)h->hc.n_slots * (size_t)h->hc.slot_elems * 4 + 256));
+        h->allocs.push_back(p);
+        h->d_stage_gray = (uint8_t *)p;
+    }
+    const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
+    const size_t ch = (size_t)g.ch, plane = (size_t)h->hc.slot_elems, tight = (size_t)w * (size_t)hh;
+    uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot0 * h->hc.slot_elems;
+    uint8_t *sg = h->d_stage_gray ? h->d_stage_gray + (size_t)slot0 * plane * 4 : nullptr;
+    const uint8_t *src = sg;
+    int64_t src_row = (int64_t)((size_t)pitch * ch), src_frame = (int64_t)(plane * ch);
+    const bool flat = step == (size_t)pitch * ch, tight_rows = step == (size_t)w * ch;
+    if (kind == hipMemcpyDeviceToDevice) {
+        src = (const uint8_t *)image;
+        src_row = (int64_t)step;
+        src_frame = n == 1 ? 0 : (int64_t)frame_step;
+    } else if (flat && (n == 1 || frame_step == plane * ch)) {
+        HIP_TRY(h, hipMemcpyAsync(sg, image, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * ch, kind, st));
+    } else if (tight_rows && (n == 1 || frame_step == tight * ch)) {
+        HIP_TRY(h, hipMemcpyAsync(sg, image, tight * (size_t)n * ch, kind, st)); // (n tight frames fit the n slots' staging)
+        src_row = (int64_t)((size_t)w * ch);
+        src_frame = (int64_t)(tight * ch);
+    } else {
+        for (int i = 0; i < n; i++) {
+            const char *fs = (const char *)image + (size_t)i * frame_step;
+            if (flat) HIP_TRY(h, hipMemcpyAsync(sg + (size_t)i * plane * ch, fs, ((size_t)pitch * (size_t)(hh - 1) + (size_t)w) * ch, kind, st));
+            else HIP_TRY(h, hipMemcpy2DAsync(sg + (size_t)i * plane * ch, (size_t)pitch * ch, fs, step, (size_t)w * ch, (size_t)hh, kind, st));
+        }
+    }
+    const hipError_t e = launch_gray_u8(di, pitch, h->hc.slot_elems, src, src_row, src_frame, w, hh, n, g.ch, g.swap, g.wr, g.wg, g.wb, g.shift, st);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "colour to grey conversion: %s", hipGetErrorString(e));
+    return DSM_OK;
+}
+
 struct HostFrames {
-    const uint8_t *image = nullptr;
+    const uint8_t *image = nullptr; // grey, or packed colour pixels with gray set
     const void *depth = nullptr; // float, or uint16 with u16 set
     size_t img_step = 0, img_frame_step = 0, depth_step = 0, depth_frame_step = 0;
     const DepthU16 *u16 = nullptr;
+    const ImageGray *gray = nullptr;
 };
 // frames [first, first + n) of `f0` into the frame slots slot_base + first ..., on `st` (u16 depth: converted right behind its copy)
 int upload_host_frames(dsm_handle *h, const HostFrames &f0, int slot_base, int first, int n, hipStream_t st) {
@@ -574,7 +624,9 @@ int upload_host_frames(dsm_handle *h, const HostFrames &f0, int slot_base, int f
     float *dd = (float *)h->hc.depth_base + (int64_t)slot0 * h->hc.slot_elems;
     const size_t plane = (size_t)pitch * (size_t)hh;
     const bool img_flat = f.img_step == (size_t)pitch, dep_flat = f.depth_step == (size_t)pitch * 4;
-    if (img_flat && (n == 1 || f.img_frame_step == plane)) {
+    if (f.gray) {
+        if (int rc = upload_image_gray(h, slot0, n, f.image, f.img_step, f.img_frame_step, hipMemcpyHostToDevice, *f.gray, st)) return rc;
+    } else if (img_flat && (n == 1 || f.img_frame_step == plane)) {
         HIP_TRY(h, hipMemcpyAsync(di, f.image, plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w, hipMemcpyHostToDevice, st));
     } else {
         for (int i = 0; i < n; i++) {
@@ -1019,11 +1071,11 @@ int sync_and_fetch_counts(dsm_handle *h) {
 
 // u16: the depth is uint16, converted into the slot on the upload's stream (the call returns when the conversion is done)
 int upload_frame(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
-                 hipMemcpyKind kind, const DepthU16 *u16 = nullptr) {
+                 hipMemcpyKind kind, const DepthU16 *u16 = nullptr, const ImageGray *gray = nullptr) {
     if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth");
     if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
     const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    if (img_step < (size_t)w || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (img_step < (size_t)w * (gray ? (size_t)gray->ch : 1) || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
     hipStream_t up = h->up_stream;
@@ -1036,11 +1088,13 @@ int upload_frame(dsm_handle *h, int slot, const void *image, size_t img_step, co
         if (h->slot_used[(size_t)slot]) HIP_TRY(h, hipStreamWaitEvent(up, h->ev_slot[(size_t)slot], 0)); // frames still reading this slot
     }
     // tightly packed rows (the usual case): one 1-D copy each, then a repack into the pitched slot on the device
-    const bool img_tight = img_step == (size_t)w, dep_tight = !u16 && depth_step == (size_t)w * 4;
+    const bool img_tight = !gray && img_step == (size_t)w, dep_tight = !u16 && depth_step == (size_t)w * 4;
     const size_t n = (size_t)w * (size_t)hh;
     const uint8_t *s_img = nullptr;
     const float *s_dep = nullptr;
-    if (img_tight) {
+    if (gray) {
+        if (int rc = upload_image_gray(h, slot, 1, image, img_step, 0, kind, *gray, up)) return rc;
+    } else if (img_tight) {
         if (kind == hipMemcpyDeviceToDevice) s_img = (const uint8_t *)image;
         else {
             HIP_TRY(h, hipMemcpyAsync(h->d_stage_img, image, n, kind, up));
@@ -1375,14 +1429,15 @@ void dsm_host_free(void *p) {
 // The caller's frames (one pointer + row step each: n cv::Mat pairs) into page-locked memory laid out like frame slots, by a
 // few host threads of the library (process-wide, made at the first call; the caller's thread takes part): one core copies
 // ~10 GB/s of 1226-pixel rows, a replay at fifteen thousand frames a second needs 35.
-// (depth_elem: bytes per depth pixel, 4 or 2)
+// (depth_elem: bytes per depth pixel, 4 or 2; img_elem: bytes per image pixel, 1, 3 or 4)
 static int host_pack_frames(int32_t n, int32_t width, int32_t height, const uint8_t *const *images, const size_t *image_steps,
                             const void *const *depths, const size_t *depth_steps, uint8_t *dst_image, size_t dst_img_step,
-                            size_t dst_img_frame_step, void *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step, size_t depth_elem) {
+                            size_t dst_img_frame_step, void *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step, size_t depth_elem,
+                            size_t img_elem = 1) {
     if (n < 0 || width <= 0 || height <= 0) return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: negative count or empty image");
     if (n == 0) return DSM_OK;
     if (!images || !image_steps || !depths || !depth_steps || !dst_image || !dst_depth) return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: null argument");
-    const size_t row_i = (size_t)width, row_d = (size_t)width * depth_elem;
+    const size_t row_i = (size_t)width * img_elem, row_d = (size_t)width * depth_elem;
     if (dst_img_step < row_i || dst_depth_step < row_d) return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: destination row step smaller than a row");
     if (n > 1 && (dst_img_frame_step < dst_img_step * (size_t)height || dst_depth_frame_step < dst_depth_step * (size_t)height))
         return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames: destination frame step smaller than a frame");
@@ -1396,16 +1451,18 @@ static int host_pack_frames(int32_t n, int32_t width, int32_t height, const uint
         const unsigned hw = std::thread::hardware_concurrency();
         pool = new HostPool(hw >= 32 ? 7 : hw >= 8 ? 3 : 1);
     }
-    // a task = the image plane of a frame, or a quarter of its depth plane's rows (equal bytes)
-    constexpr int kParts = 5;
+    // a task = the image plane of a frame (a colour one: one of img_elem runs of its rows), or a quarter of its depth plane's rows
+    // (about equal bytes)
+    const int kImg = (int)img_elem, kParts = kImg + 4;
     pool->run(n * kParts, [&](int t) {
         const int i = t / kParts, part = t % kParts;
-        if (part == 0) {
+        if (part < kImg) {
+            const int y0 = (int)((int64_t)height * part / kImg), y1 = (int)((int64_t)height * (part + 1) / kImg);
             const uint8_t *src = images[i];
             uint8_t *dst = dst_image + (size_t)i * dst_img_frame_step;
-            for (int y = 0; y < height; y++) memcpy(dst + (size_t)y * dst_img_step, src + (size_t)y * image_steps[i], row_i);
+            for (int y = y0; y < y1; y++) memcpy(dst + (size_t)y * dst_img_step, src + (size_t)y * image_steps[i], row_i);
         } else {
-            const int y0 = (int)((int64_t)height * (part - 1) / 4), y1 = (int)((int64_t)height * part / 4);
+            const int y0 = (int)((int64_t)height * (part - kImg) / 4), y1 = (int)((int64_t)height * (part - kImg + 1) / 4);
             const char *src = (const char *)depths[i];
             char *dst = (char *)dst_depth + (size_t)i * dst_depth_frame_step;
             for (int y = y0; y < y1; y++) memcpy(dst + (size_t)y * dst_depth_step, src + (size_t)y * depth_steps[i], row_d);
@@ -1426,6 +1483,31 @@ int dsm_host_pack_frames_u16(int32_t n, int32_t width, int32_t height, const uin
                              size_t dst_img_frame_step, uint16_t *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step) {
     return host_pack_frames(n, width, height, images, image_steps, (const void *const *)depths, depth_steps, dst_image, dst_img_step,
                             dst_img_frame_step, dst_depth, dst_depth_step, dst_depth_frame_step, 2);
+}
+
+int dsm_host_pack_frames_fmt(int32_t n, int32_t width, int32_t height, const void *const *images, const size_t *image_steps,
+                             const void *const *depths, const size_t *depth_steps, void *dst_image, size_t dst_img_step,
+                             size_t dst_img_frame_step, void *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step,
+                             const dsm_frame_format *fmt) {
+    // (the planes are copied as they are: only the element sizes matter, the weights and the depth scale are not looked at)
+    if (!fmt || fmt->struct_size != (uint32_t)sizeof(dsm_frame_format)) return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames_fmt: null format or wrong struct_size");
+    const int ch = dsm_fmt::image_channels(fmt->image_format);
+    if (!ch || (fmt->depth_format != DSM_DEPTH_F32 && fmt->depth_format != DSM_DEPTH_U16))
+        return fail(nullptr, DSM_E_INVALID, "dsm_host_pack_frames_fmt: unknown image_format %d / depth_format %d", (int)fmt->image_format, (int)fmt->depth_format);
+    return host_pack_frames(n, width, height, (const uint8_t *const *)images, image_steps, depths, depth_steps, (uint8_t *)dst_image, dst_img_step,
+                            dst_img_frame_step, dst_depth, dst_depth_step, dst_depth_frame_step, fmt->depth_format == DSM_DEPTH_U16 ? 2 : 4, (size_t)ch);
+}
+
+void dsm_frame_format_init(dsm_frame_format *f) {
+    if (!f) return;
+    const int32_t w[4] = DSM_GRAY_OPENCV_14BIT;
+    memset(f, 0, sizeof *f);
+    f->struct_size = (uint32_t)sizeof(dsm_frame_format);
+    f->image_format = DSM_IMAGE_MONO8;
+    f->gray_wr = w[0]; f->gray_wg = w[1]; f->gray_wb = w[2]; f->gray_shift = w[3];
+    f->depth_format = DSM_DEPTH_F32;
+    f->depth_scale = 1.0f;
+    f->depth_op = DSM_DEPTH_U16_DIVIDE;
 }
 
 int dsm_seed_count(const dsm_handle *h) { return h ? h->hc.n_seed : DSM_E_INVALID; }
@@ -1952,6 +2034,44 @@ int dsm_frame_upload_device_u16(dsm_handle *h, int slot, const void *image_dev, 
     return upload_frame(h, slot, image_dev, img_step, depth_dev, depth_step, hipMemcpyDeviceToDevice, &u);
 }
 
+// The *_fmt entry points: the descriptor is taken apart and checked first (DSM_E_INVALID before any device work), then the call is
+// the plain one (mono8 + f32), the *_u16 one (mono8 + u16), or either with the image converted from colour behind its copy.
+struct FrameFmt {
+    dsm_fmt::Parsed p;
+    DepthU16 u = {1.0f, DSM_DEPTH_U16_DIVIDE};
+    const DepthU16 *u16() const { return p.u16 ? &u : nullptr; }
+    const ImageGray *gray() const { return p.color ? &p.gray : nullptr; }
+};
+#define FRAME_FMT_PARSE(h, fmt, ff)                                                                                             \
+    FrameFmt ff;                                                                                                                 \
+    do {                                                                                                                         \
+        if (const char *e_ = dsm_fmt::parse(fmt, &ff.p)) return fail(h, DSM_E_INVALID, "dsm_frame_format: %s", e_);              \
+        ff.u = {ff.p.depth_scale, ff.p.depth_op};                                                                                \
+    } while (0)
+
+static int frame_upload_fmt(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
+                            const dsm_frame_format *fmt, hipMemcpyKind kind) {
+    if (!h) return DSM_E_INVALID;
+    FRAME_FMT_PARSE(h, fmt, ff);
+    if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth"); // (upload_frame checks these too: here, before any device call)
+    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
+    if (img_step < (size_t)h->hc.w * (size_t)ff.p.gray.ch || depth_step < (size_t)h->hc.w * (size_t)ff.p.depth_elem)
+        return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    int rc = bind_device(h);
+    if (rc) return rc;
+    return upload_frame(h, slot, image, img_step, depth, depth_step, kind, ff.u16(), ff.gray());
+}
+
+int dsm_frame_upload_fmt(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
+                         const dsm_frame_format *fmt) {
+    return frame_upload_fmt(h, slot, image, img_step, depth, depth_step, fmt, hipMemcpyHostToDevice);
+}
+
+int dsm_frame_upload_device_fmt(dsm_handle *h, int slot, const void *image_dev, size_t img_step, const void *depth_dev, size_t depth_step,
+                                const dsm_frame_format *fmt) {
+    return frame_upload_fmt(h, slot, image_dev, img_step, depth_dev, depth_step, fmt, hipMemcpyDeviceToDevice);
+}
+
 int dsm_frame_pitch(const dsm_handle *h, int32_t *pitch) {
     if (!h || !pitch) return DSM_E_INVALID;
     *pitch = h->hc.pitch;
@@ -1964,12 +2084,12 @@ int dsm_frame_upload_async(dsm_handle *h, int slot, const uint8_t *image, size_t
 
 // dsm_frames_upload_async and its u16 form (u16 != nullptr: `depth` is uint16, converted on the upload stream before the event)
 static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
-                               const void *depth, size_t depth_step, size_t depth_frame_step, const DepthU16 *u16) {
+                               const void *depth, size_t depth_step, size_t depth_frame_step, const DepthU16 *u16, const ImageGray *gray = nullptr) {
     if (!h) return DSM_E_INVALID;
     if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth");
     if (n < 1 || slot0 < 0 || slot0 + n > h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slots [%d,%d) out of range [0,%d)", slot0, slot0 + n, h->hc.n_slots);
     const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    if (img_step < (size_t)w || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (img_step < (size_t)w * (gray ? (size_t)gray->ch : 1) || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
     if (n > 1 && (img_frame_step < img_step * (size_t)hh || depth_frame_step < depth_step * (size_t)hh)) return fail(h, DSM_E_INVALID, "frame step smaller than a frame");
     // A handle that advances with a batch and whose own stream has carried nothing since the batch last ordered itself
     // behind it (`touched` false: only batch calls since): whatever may still read these slots is covered by the batch's
@@ -2019,7 +2139,7 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
     // frames out at the pitch.)
     const bool img_flat = img_step == (size_t)pitch, dep_flat = depth_step == (size_t)pitch * 4;
     const size_t tight = (size_t)w * (size_t)hh;
-    const bool img_tight = !img_flat && img_step == (size_t)w && (n == 1 || img_frame_step == tight);
+    const bool img_tight = !gray && !img_flat && img_step == (size_t)w && (n == 1 || img_frame_step == tight);
     const bool dep_tight = !u16 && !dep_flat && depth_step == (size_t)w * 4 && (n == 1 || depth_frame_step == tight * 4);
     if ((img_tight || dep_tight) && n > h->stage_frames_cap) {
         HIP_TRY(h, hipStreamSynchronize(up)); // (an earlier call's repack may still read the old buffers)
@@ -2037,7 +2157,9 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
                                                   dep_tight ? h->d_stage_frames_depth : nullptr, w, hh, n, up);
         if (e != hipSuccess) return fail(h, DSM_E_HIP, "frame repack: %s", hipGetErrorString(e));
     }
-    if (img_tight) { // (already on its way)
+    if (gray) {
+        if (int rc = upload_image_gray(h, slot0, n, image, img_step, img_frame_step, hipMemcpyHostToDevice, *gray, up)) return rc;
+    } else if (img_tight) { // (already on its way)
     } else if (img_flat && (n == 1 || img_frame_step == plane)) {
         HIP_TRY(h, hipMemcpyAsync(di, image, plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w, hipMemcpyHostToDevice, up));
     } else {
@@ -2080,7 +2202,7 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
     e.lo = slot0;
     e.hi = slot0 + n;
     e.pending = ~0ull;
-    HIP_TRY(h, hipEventRecord(e.ev, up)); // (behind the u16 conversion: the upload has landed when its float plane is there)
+    HIP_TRY(h, hipEventRecord(e.ev, up)); // (behind the u16 / colour conversions: the upload has landed when the slot's planes are there)
     return DSM_OK;
 }
 
@@ -2100,6 +2222,18 @@ int dsm_frames_upload_async_u16(dsm_handle *h, int slot0, int n, const uint8_t *
     DEPTH_U16_CHECK(h, depth_scale, depth_op);
     const DepthU16 u = {depth_scale, depth_op};
     return frames_upload_async(h, slot0, n, image, img_step, img_frame_step, depth, depth_step, depth_frame_step, &u);
+}
+
+int dsm_frame_upload_async_fmt(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
+                               const dsm_frame_format *fmt) {
+    return dsm_frames_upload_async_fmt(h, slot, 1, image, img_step, 0, depth, depth_step, 0, fmt);
+}
+
+int dsm_frames_upload_async_fmt(dsm_handle *h, int slot0, int n, const void *image, size_t img_step, size_t img_frame_step,
+                                const void *depth, size_t depth_step, size_t depth_frame_step, const dsm_frame_format *fmt) {
+    if (!h) return DSM_E_INVALID;
+    FRAME_FMT_PARSE(h, fmt, ff);
+    return frames_upload_async(h, slot0, n, (const uint8_t *)image, img_step, img_frame_step, depth, depth_step, depth_frame_step, ff.u16(), ff.gray());
 }
 
 int dsm_frame_uploads_wait(dsm_handle *h) {
@@ -2139,12 +2273,12 @@ int dsm_replay_enqueue(dsm_handle *h, int32_t n, const int32_t *slots, const int
 // dsm_replay_enqueue_host and its u16 form (u16 != nullptr: `depth` is uint16, each group's converted right behind its copy)
 static int replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, size_t img_step, size_t img_frame_step, const void *depth,
                                size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16, const float *inv_poses16,
-                               const DepthU16 *u16) {
+                               const DepthU16 *u16, const ImageGray *gray = nullptr) {
     if (!h) return DSM_E_INVALID;
     if (n < 0 || (n > 0 && (!image || !depth || !ref_idx || !poses16))) return fail(h, DSM_E_INVALID, "null/negative argument");
     if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
     if (h->hc.n_slots < h->n_pipe) return fail(h, DSM_E_INVALID, "dsm_replay_enqueue_host keeps a frame in the slot of its pipeline: %d frame slots for pipeline_depth %d", h->hc.n_slots, h->n_pipe);
-    if (img_step < (size_t)h->hc.w || depth_step < (size_t)h->hc.w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (img_step < (size_t)h->hc.w * (gray ? (size_t)gray->ch : 1) || depth_step < (size_t)h->hc.w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
     if (n > 1 && (img_frame_step < img_step * (size_t)h->hc.h || depth_frame_step < depth_step * (size_t)h->hc.h)) return fail(h, DSM_E_INVALID, "frame step smaller than a frame");
     int rc = bind_device(h);
     if (rc) return rc;
@@ -2155,6 +2289,7 @@ static int replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, s
     HostFrames hf;
     hf.img_step = img_step; hf.img_frame_step = img_frame_step; hf.depth_step = depth_step; hf.depth_frame_step = depth_frame_step;
     hf.u16 = u16;
+    hf.gray = gray;
     for (int i = 0; i < n;) {
         int m = 0;
         if ((rc = stage_params_batch(h, n - i, slots.data() + i, ref_idx + i, poses16 + 16 * (size_t)i,
@@ -2197,6 +2332,15 @@ int dsm_replay_enqueue_host_u16(dsm_handle *h, int32_t n, const uint8_t *image, 
     DEPTH_U16_CHECK(h, depth_scale, depth_op);
     const DepthU16 u = {depth_scale, depth_op};
     return replay_enqueue_host(h, n, image, img_step, img_frame_step, depth, depth_step, depth_frame_step, ref_idx, poses16, inv_poses16, &u);
+}
+
+int dsm_replay_enqueue_host_fmt(dsm_handle *h, int32_t n, const void *image, size_t img_step, size_t img_frame_step, const void *depth,
+                                size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16, const float *inv_poses16,
+                                const dsm_frame_format *fmt) {
+    if (!h) return DSM_E_INVALID;
+    FRAME_FMT_PARSE(h, fmt, ff);
+    return replay_enqueue_host(h, n, (const uint8_t *)image, img_step, img_frame_step, depth, depth_step, depth_frame_step, ref_idx, poses16, inv_poses16,
+                               ff.u16(), ff.gray());
 }
 
 int dsm_replay_wait(dsm_handle *h, int32_t calls_back) {
@@ -2435,6 +2579,25 @@ int dsm_debug_get_frame(dsm_handle *h, int slot, uint8_t *image, float *depth) {
     const size_t w = (size_t)h->hc.w, hh = (size_t)h->hc.h, pitch = (size_t)h->hc.pitch;
     if (image) HIP_TRY(h, hipMemcpy2D(image, w, (const uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems, pitch, w, hh, hipMemcpyDeviceToHost));
     if (depth) HIP_TRY(h, hipMemcpy2D(depth, w * 4, (const float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems, pitch * 4, w * 4, hh, hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
+// debug tap: the whole pitched planes of a slot, pad columns included, read or (write != 0) overwritten
+int dsm_debug_frame_planes(dsm_handle *h, int slot, int write, uint8_t *image, float *depth) {
+    if (!h) return DSM_E_INVALID;
+    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
+    int rc = bind_device(h);
+    if (rc) return rc;
+    {
+        const ReadSlots reads(h, slot, slot + 1);
+        if ((rc = wait_uploads(h, h->stream, kSerialBit))) return rc;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t plane = (size_t)h->hc.pitch * (size_t)h->hc.h;
+    uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems;
+    float *dd = (float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
+    if (image) HIP_TRY(h, write ? hipMemcpy(di, image, plane, hipMemcpyHostToDevice) : hipMemcpy(image, di, plane, hipMemcpyDeviceToHost));
+    if (depth) HIP_TRY(h, write ? hipMemcpy(dd, depth, plane * 4, hipMemcpyHostToDevice) : hipMemcpy(depth, dd, plane * 4, hipMemcpyDeviceToHost));
     return DSM_OK;
 }
 

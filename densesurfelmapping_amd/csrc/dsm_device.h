@@ -173,6 +173,11 @@ hipError_t launch_repack(uint8_t *d_img, float *d_depth, int pitch, const uint8_
 // d_depth + f * slot_elems: op = DSM_DEPTH_U16_DIVIDE (u / s) or DSM_DEPTH_U16_MULTIPLY (u * s), one launch, grid.y = frame
 hipError_t launch_depth_u16(float *d_depth, int pitch, int64_t slot_elems, const uint16_t *src, int64_t src_row, int64_t src_frame, int w, int h,
                             int frames, float s, int op, hipStream_t st);
+// packed colour pixels (`channels` = 3 or 4 bytes each, swap_rb: the first byte is B) of `frames` frames (rows src_row BYTES apart, frames
+// src_frame bytes apart) converted into the pitched image planes d_img + f * slot_elems: grey = (R wr + G wg + B wb + (1 << (shift - 1)))
+// >> shift (k_gray_u8), one launch, grid.y = frame.  The caller has checked the weights (dsm_frame_format's rules).
+hipError_t launch_gray_u8(uint8_t *d_img, int pitch, int64_t slot_elems, const uint8_t *src, int64_t src_row, int64_t src_frame, int w, int h,
+                          int frames, int channels, int swap_rb, int wr, int wg, int wb, int shift, hipStream_t st);
 hipError_t launch_extract_marked(const DeviceCtx &ctx, dsm_surfel *out, int cap, float4 *cloud_out, hipStream_t st);
 hipError_t launch_extract(const DeviceCtx &ctx, int key, dsm_surfel *out, int cap, int n_upper, hipStream_t st);
 hipError_t launch_append_count(const DeviceCtx &ctx, int n, hipStream_t st);

@@ -896,6 +896,94 @@ hipError_t launch_depth_u16(float *d_depth, int pitch, int64_t slot_elems, const
     return hipGetLastError();
 }
 
+// Colour camera images (the *_fmt uploads): packed 3- or 4-byte pixels -> the grey byte of the slot's pitched image plane, the
+// fixed-point weighted sum cv_bridge's toCvCopy(msg, MONO8) leaves to OpenCV's RGB2Gray<uchar>, in exact integer arithmetic:
+// grey = (R * wr + G * wg + B * wb + (1 << (shift - 1))) >> shift.  The caller's checks (weights >= 0, sum <= 1 << shift, shift <= 22)
+// keep the sum below 2^31 and the result below 256: no saturation.  SWAP: the first byte of a pixel is B (bgr8 / bgra8); a fourth
+// byte (alpha) is ignored.  Only the w pixels of a row are written, as by the mono8 copy.
+struct GrayWeights {
+    uint32_t wr, wg, wb, half, shift;
+};
+// px = byte0 | byte1 << 8 | byte2 << 16 of a pixel
+template <bool SWAP> __device__ __forceinline__ uint32_t gray_from_px(uint32_t px, const GrayWeights &g) {
+    const uint32_t c0 = px & 0xffu, c1 = (px >> 8) & 0xffu, c2 = (px >> 16) & 0xffu;
+    return ((SWAP ? c2 : c0) * g.wr + c1 * g.wg + (SWAP ? c0 : c2) * g.wb + g.half) >> g.shift;
+}
+struct alignas(4) Px3x4 {
+    uint32_t a, b, c; // four 3-byte pixels
+};
+// Source rows src_row BYTES apart, frames src_frame bytes apart, grid.y = frame.  VEC (rows, frames and base a multiple of 16 bytes
+// apart for 4-byte pixels, of 4 bytes for 3-byte ones: the colour staging of the slots at their own pitch): a lane takes FOUR
+// pixels -- one 16-byte load (CH 4: lane i at base + 16 i, the widest coalesced access) or one 12-byte load (CH 3: a wave reads 768
+// contiguous bytes) and one dword store of grey (the slot rows are 64-byte aligned); the last partial group of a row goes pixel by
+// pixel and reads nothing past CH * w bytes of the row.  Otherwise (tight rows of an odd width, odd steps, a caller's device
+// buffer at an odd address) a lane takes one pixel with byte loads.
+template <int CH, bool SWAP, bool VEC>
+__global__ __launch_bounds__(256) void k_gray_u8(uint8_t *__restrict__ dst, int pitch, int64_t dst_frame, const uint8_t *__restrict__ src,
+                                                 int64_t src_row, int64_t src_frame, int w, int h, GrayWeights g) {
+    const uint8_t *sf = src + (int64_t)blockIdx.y * src_frame;
+    uint8_t *df = dst + (int64_t)blockIdx.y * dst_frame;
+    if (VEC) {
+        const int gpr = (w + 3) >> 2, n = gpr * h;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+            const int y = i / gpr, x = (i - y * gpr) << 2;
+            const uint8_t *sp = sf + (int64_t)y * src_row + (int64_t)x * CH;
+            uint8_t *dp = df + (int64_t)y * pitch + x;
+            if (x + 4 <= w) {
+                uint32_t p0, p1, p2, p3;
+                if (CH == 4) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(sp);
+                    p0 = v.x; p1 = v.y; p2 = v.z; p3 = v.w;
+                } else {
+                    const Px3x4 v = *reinterpret_cast<const Px3x4 *>(sp);
+                    p0 = v.a;
+                    p1 = (v.a >> 24) | (v.b << 8);
+                    p2 = (v.b >> 16) | (v.c << 16);
+                    p3 = v.c >> 8;
+                }
+                *reinterpret_cast<uint32_t *>(dp) = gray_from_px<SWAP>(p0, g) | (gray_from_px<SWAP>(p1, g) << 8) |
+                                                    (gray_from_px<SWAP>(p2, g) << 16) | (gray_from_px<SWAP>(p3, g) << 24);
+            } else {
+                for (int k = 0; k < w - x; k++)
+                    dp[k] = (uint8_t)gray_from_px<SWAP>((uint32_t)sp[k * CH] | ((uint32_t)sp[k * CH + 1] << 8) | ((uint32_t)sp[k * CH + 2] << 16), g);
+            }
+        }
+    } else {
+        const int n = w * h;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+            const int y = i / w, x = i - y * w;
+            const uint8_t *sp = sf + (int64_t)y * src_row + (int64_t)x * CH;
+            df[(int64_t)y * pitch + x] = (uint8_t)gray_from_px<SWAP>((uint32_t)sp[0] | ((uint32_t)sp[1] << 8) | ((uint32_t)sp[2] << 16), g);
+        }
+    }
+}
+template <int CH, bool SWAP>
+static void launch_gray_u8_form(bool vec, dim3 grid, hipStream_t st, uint8_t *d_img, int pitch, int64_t slot_elems, const uint8_t *src, int64_t src_row,
+                                int64_t src_frame, int w, int h, const GrayWeights &g) {
+    if (vec) hipLaunchKernelGGL((k_gray_u8<CH, SWAP, true>), grid, dim3(256), 0, st, d_img, pitch, slot_elems, src, src_row, src_frame, w, h, g);
+    else hipLaunchKernelGGL((k_gray_u8<CH, SWAP, false>), grid, dim3(256), 0, st, d_img, pitch, slot_elems, src, src_row, src_frame, w, h, g);
+}
+hipError_t launch_gray_u8(uint8_t *d_img, int pitch, int64_t slot_elems, const uint8_t *src, int64_t src_row, int64_t src_frame, int w, int h,
+                          int frames, int channels, int swap_rb, int wr, int wg, int wb, int shift, hipStream_t st) {
+    if ((channels != 3 && channels != 4) || shift < 1 || shift > 22 || wr < 0 || wg < 0 || wb < 0) return hipErrorInvalidValue;
+    const int64_t a = channels == 4 ? 16 : 4; // what the vector form's loads need
+    const bool vec = src_row % a == 0 && src_frame % a == 0 && ((uintptr_t)src & (uintptr_t)(a - 1)) == 0 &&
+                     pitch % 4 == 0 && slot_elems % 4 == 0 && ((uintptr_t)d_img & 3) == 0; // (and the dword stores)
+    const int n = vec ? ((w + 3) >> 2) * h : w * h;
+    int blocks = (n + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    const dim3 grid(blocks, frames);
+    const GrayWeights g = {(uint32_t)wr, (uint32_t)wg, (uint32_t)wb, 1u << (shift - 1), (uint32_t)shift};
+    if (channels == 4) {
+        if (swap_rb) launch_gray_u8_form<4, true>(vec, grid, st, d_img, pitch, slot_elems, src, src_row, src_frame, w, h, g);
+        else launch_gray_u8_form<4, false>(vec, grid, st, d_img, pitch, slot_elems, src, src_row, src_frame, w, h, g);
+    } else {
+        if (swap_rb) launch_gray_u8_form<3, true>(vec, grid, st, d_img, pitch, slot_elems, src, src_row, src_frame, w, h, g);
+        else launch_gray_u8_form<3, false>(vec, grid, st, d_img, pitch, slot_elems, src, src_row, src_frame, w, h, g);
+    }
+    return hipGetLastError();
+}
+
 // Timed replays only: keep the GPU busy for `ticks` of the 100 MHz wall clock while the host enqueues
 // the whole frame, so that the events between kernels do not measure host launch latency.
 __global__ void k_delay(long long ticks) {

@@ -9,6 +9,7 @@
 // definitions: 4x4 product with left-to-right accumulation, 4x4 inverse by the adjugate closed form,
 // Quaterniond <-> rotation matrix (Eigen/src/Geometry/Quaternion.h), Vector3f normalize / cross.
 #include "dsm_surfel_map_node.h"
+#include "dsm_frame_format.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,6 +31,10 @@
 // the engine for tests), and dsm_surfel_map_depth_input_u16 refuses its input there.
 extern "C" int dsm_frame_upload_u16(dsm_handle *h, int slot, const uint8_t *image, size_t img_step, const uint16_t *depth, size_t depth_step,
                                     float depth_scale, int32_t depth_op) __attribute__((weak));
+
+// ... and so is its format-described upload, which dsm_surfel_map_image_input_color needs
+extern "C" int dsm_frame_upload_fmt(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
+                                    const dsm_frame_format *fmt) __attribute__((weak));
 
 namespace {
 
@@ -327,7 +332,19 @@ int synchronize_msgs(dsm_surfel_map *m) {
     // two frame slots in turn: this frame goes up (on the engine's upload stream) while the previous one is still being fused
     const int slot = (int)(m->frames_fused & 1);
     const Frame &dep = m->depth_buffer.front();
-    if (dep.u16_scale > 0) // a sensor's uint16 frame: converted to metres on the device, into the slot (dsm_surfel_map_depth_input_u16)
+    const Frame &img = m->image_buffer.front();
+    if (img.image_format != DSM_IMAGE_MONO8) { // a colour camera's frame: converted to grey on the device, into the slot (dsm_surfel_map_image_input_color)
+        dsm_frame_format fmt;
+        memset(&fmt, 0, sizeof fmt);
+        fmt.struct_size = (uint32_t)sizeof fmt;
+        fmt.image_format = img.image_format;
+        fmt.gray_wr = img.gray[0]; fmt.gray_wg = img.gray[1]; fmt.gray_wb = img.gray[2]; fmt.gray_shift = img.gray[3];
+        fmt.depth_format = dep.u16_scale > 0 ? DSM_DEPTH_U16 : DSM_DEPTH_F32;
+        fmt.depth_scale = dep.u16_scale > 0 ? dep.u16_scale : 1.0f;
+        fmt.depth_op = dep.u16_op;
+        const size_t ch = dsm_fmt::image_channels(img.image_format);
+        ENGINE_TRY(m, dsm_frame_upload_fmt(m->engine, slot, img.bytes, (size_t)w * ch, dep.bytes, (size_t)w * (dep.u16_scale > 0 ? 2 : 4), &fmt));
+    } else if (dep.u16_scale > 0) // a sensor's uint16 frame: converted to metres on the device, into the slot (dsm_surfel_map_depth_input_u16)
         ENGINE_TRY(m, dsm_frame_upload_u16(m->engine, slot, m->image_buffer.front().bytes, (size_t)w, (const uint16_t *)dep.bytes, (size_t)w * 2,
                                            dep.u16_scale, dep.u16_op));
     else
@@ -346,7 +363,8 @@ int synchronize_msgs(dsm_surfel_map *m) {
 }
 
 int copy_frame(dsm_surfel_map *m, std::list<Frame> &buffer, FramePool &pool, dsm_stamp stamp, int32_t width,
-               int32_t height, size_t step, const void *data, size_t elem, float u16_scale = 0, int32_t u16_op = 0) {
+               int32_t height, size_t step, const void *data, size_t elem, float u16_scale = 0, int32_t u16_op = 0,
+               int32_t image_format = DSM_IMAGE_MONO8, const int32_t *gray = nullptr) {
     if (!data) return fail(m, DSM_E_INVALID, "null image data");
     if (width != m->cfg.cam_width || height != m->cfg.cam_height)
         return fail(m, DSM_E_INVALID, "image is %dx%d, the node was configured for %dx%d", width, height, m->cfg.cam_width, m->cfg.cam_height);
@@ -356,6 +374,8 @@ int copy_frame(dsm_surfel_map *m, std::list<Frame> &buffer, FramePool &pool, dsm
     f.pool = &pool;
     f.u16_scale = u16_scale;
     f.u16_op = u16_op;
+    f.image_format = image_format;
+    if (gray) memcpy(f.gray, gray, sizeof f.gray);
     f.bytes = pool.take((size_t)width * (size_t)height * elem, &f.pinned);
     if (!f.bytes) return fail(m, DSM_E_HIP, "no host memory for a frame");
     for (int y = 0; y < height; y++) memcpy(f.bytes + (size_t)y * width * elem, (const uint8_t *)data + (size_t)y * step, (size_t)width * elem);
@@ -367,7 +387,7 @@ int copy_frame(dsm_surfel_map *m, std::list<Frame> &buffer, FramePool &pool, dsm
     const size_t keep = lim > 0 ? (size_t)lim : lim == 0 ? (size_t)5000 : (size_t)-1;
     while (buffer.size() > keep) {
         fprintf(stderr, "dsm_surfel_map: more than %zu %s frames wait for a pose; dropping the one stamped %.6f (its pose will be skipped)\n",
-                keep, elem == 1 ? "image" : "depth", to_sec(buffer.front().stamp));
+                keep, &buffer == &m->image_buffer ? "image" : "depth", to_sec(buffer.front().stamp));
         m->frames_dropped++;
         pool.release(buffer.front());
         buffer.pop_front();
@@ -460,6 +480,8 @@ void dsm_surfel_map_destroy(dsm_surfel_map *m) {
     m->image_pool.drain();
     m->depth_pool.drain();
     m->depth16_pool.drain();
+    m->color3_pool.drain();
+    m->color4_pool.drain();
     if (m->release_publish) m->release_publish(m);
     delete m;
 }
@@ -483,6 +505,24 @@ int dsm_surfel_map_depth_input(dsm_surfel_map *m, dsm_stamp stamp, int32_t width
     if (!encoding || strcmp(encoding, "32FC1") != 0)
         return fail(m, DSM_E_INVALID, "depth encoding '%s': only 32FC1 is taken", encoding ? encoding : "(null)");
     const int rc = copy_frame(m, m->depth_buffer, m->depth_pool, stamp, width, height, step, data, 4);
+    return rc ? rc : synchronize_msgs(m);
+}
+
+int dsm_surfel_map_image_input_color(dsm_surfel_map *m, dsm_stamp stamp, int32_t width, int32_t height, size_t step, const char *encoding,
+                                     const void *data, const int32_t *gray_weights4) {
+    if (!m) return DSM_E_INVALID;
+    if (m->failed) return fail(m, DSM_E_STATE, "the node failed half-way through a state change earlier and takes no more input");
+    const int32_t format = !encoding ? -1 : !strcmp(encoding, "rgb8") ? DSM_IMAGE_RGB8 : !strcmp(encoding, "bgr8") ? DSM_IMAGE_BGR8
+                           : !strcmp(encoding, "rgba8") ? DSM_IMAGE_RGBA8 : !strcmp(encoding, "bgra8") ? DSM_IMAGE_BGRA8 : -1;
+    if (format < 0)
+        return fail(m, DSM_E_INVALID, "image encoding '%s': dsm_surfel_map_image_input_color takes rgb8 / bgr8 / rgba8 / bgra8", encoding ? encoding : "(null)");
+    if (!dsm_frame_upload_fmt) return fail(m, DSM_E_STATE, "this engine has no colour image upload");
+    // (checked here, not first at the upload: a frame that cannot be converted must not wait for its pose)
+    const int32_t preset[4] = DSM_GRAY_OPENCV_14BIT;
+    const int32_t *g = gray_weights4 ? gray_weights4 : preset;
+    if (const char *e = dsm_fmt::gray_weights_error(g[0], g[1], g[2], g[3])) return fail(m, DSM_E_INVALID, "gray_weights4 = {%d, %d, %d, %d}: %s", g[0], g[1], g[2], g[3], e);
+    const int ch = dsm_fmt::image_channels(format);
+    const int rc = copy_frame(m, m->image_buffer, ch == 3 ? m->color3_pool : m->color4_pool, stamp, width, height, step, data, (size_t)ch, 0, 0, format, g);
     return rc ? rc : synchronize_msgs(m);
 }
 

@@ -57,6 +57,8 @@ struct Frame {
     FramePool *pool;       // the pool the bytes came from (release them there)
     float u16_scale = 0;   // > 0: a uint16 depth frame (dsm_surfel_map_depth_input_u16), converted on upload with u16_op
     int32_t u16_op = 0;
+    int32_t image_format = 0; // != DSM_IMAGE_MONO8: a colour image frame (dsm_surfel_map_image_input_color), 3 or 4 bytes a pixel,
+    int32_t gray[4] = {0, 0, 0, 0}; // converted to grey on upload with these weights (wr, wg, wb, shift)
 };
 
 // Frames wait for their pose in page-locked memory so that the upload of a frame is one DMA -- but only the first
@@ -123,6 +125,7 @@ struct dsm_surfel_map {
     dsm_handle *engine = nullptr;
     std::list<Frame> image_buffer, depth_buffer;                                 // surfel_map.h:96-97
     FramePool image_pool, depth_pool, depth16_pool;                              // where the buffered frames' bytes live (depth16: uint16 frames)
+    FramePool color3_pool, color4_pool;                                          // colour image frames, 3 and 4 bytes a pixel
     std::list<std::tuple<dsm_stamp, dsm_pose_msg, int>> pose_reference_buffer; // :98
     std::vector<PoseElement> poses_database;                                     // :120
     std::set<int> local_surfels_indexs;                                          // :122

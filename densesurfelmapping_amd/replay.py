@@ -204,14 +204,19 @@ class HipEngine:
     them there (`pinned_run`).  `fuse` is the frame-at-a-time form of the same thing (SurfelMap::fuse_map,
     surfel_map.cpp:1060-1113).  There is no other engine in this package: without a gfx950 device the constructor raises
     (DSM_E_NO_DEVICE).  depth_u16=(scale, op): the source's frames() yield the sensor's uint16 depth, which is packed and streamed
-    at 2 bytes a pixel and converted to metres on the device (dsm_replay_enqueue_host_u16; api.depth_from_u16 says how)."""
+    at 2 bytes a pixel and converted to metres on the device (dsm_replay_enqueue_host_u16; api.depth_from_u16 says how).
+    image_format='rgb8' / 'bgr8' / 'rgba8' / 'bgra8' (gray_weights = (wr, wg, wb, shift), None = api.GRAY_OPENCV_14BIT): the source's
+    frames() yield the camera's colour images [H,W,3|4], packed and streamed at 3 or 4 bytes a pixel and converted to grey on the
+    device (dsm_replay_enqueue_host_fmt; api.gray_from_color says how), with float or uint16 depth."""
 
     BLOCKS = 4  # page-locked blocks of `chunk` frames the prefetch thread fills in turn (one being filled, up to three in flight)
 
-    def __init__(self, cam, device=0, capacity=0, pipeline_depth=24, chunk=48, depth_u16=None):
+    def __init__(self, cam, device=0, capacity=0, pipeline_depth=24, chunk=48, depth_u16=None, image_format=None, gray_weights=None):
         from . import api
         self._api = api
         self.depth_u16 = depth_u16
+        self.image_format = None if image_format in (None, "mono8") else image_format
+        self.gray_weights = gray_weights
         self.chunk = max(1, int(chunk))
         self.depth = int(pipeline_depth) if pipeline_depth else 4
         self.ff = api.FusionFunctions.from_camera(cam, device=device, frame_slots=max(self.depth, 2), surfel_capacity=capacity,
@@ -223,7 +228,9 @@ class HipEngine:
 
     def fuse(self, image, depth, pose, ref_idx):  # one frame: blocking upload into a slot, one enqueue
         slot = self.n % max(self.depth, 2)
-        if self.depth_u16 is not None:
+        if self.image_format is not None:
+            self.ff.frame_upload_fmt(slot, image, depth, self._api.frame_format(self.image_format, self.gray_weights, self.depth_u16))
+        elif self.depth_u16 is not None:
             self.ff.frame_upload_u16(slot, image, depth, *self.depth_u16)
         else:
             self.ff.frame_upload(slot, image, depth)
@@ -241,12 +248,12 @@ class HipEngine:
         n_total = b - a
         chunks = [(a + c0, min(C, n_total - c0)) for c0 in range(0, n_total, C)]  # (first frame, frames)
         # (a source's own page-locked blocks hold float depth)
-        zero_copy = self.depth_u16 is None and getattr(source, "pinned_run", None) is not None and source.pinned_run(api, a, 1) is not None
+        zero_copy = self.depth_u16 is None and self.image_format is None and getattr(source, "pinned_run", None) is not None and source.pinned_run(api, a, 1) is not None
         ready = queue.Queue()
         free = threading.Semaphore(self.BLOCKS)
         stop = threading.Event()
         if not zero_copy and self._pins is None:
-            self._pins = [api.PinnedFrames(ff, C, depth_u16=self.depth_u16) for _ in range(self.BLOCKS)]
+            self._pins = [api.PinnedFrames(ff, C, depth_u16=self.depth_u16, image_format=self.image_format, gray_weights=self.gray_weights) for _ in range(self.BLOCKS)]
 
         def produce():  # decode / render / copy chunk k into page-locked block k mod BLOCKS, as soon as that block is free
             try:
@@ -303,7 +310,8 @@ class HipEngine:
         self.n += n_total
         dt = time.perf_counter() - t_start
         self.stats = {"frames": n_total, "seconds": dt, "chunk_frames": C, "zero_copy": bool(zero_copy),
-                      "bytes_per_frame": int(ff.frame_pitch() * ff.height * (3 if self.depth_u16 is not None else 5))}
+                      "bytes_per_frame": int(ff.frame_pitch() * ff.height * ((1 if self.image_format is None else api.image_channels(self.image_format))
+                                                                              + (2 if self.depth_u16 is not None else 4)))}
         return n_total
 
     def cloud(self):

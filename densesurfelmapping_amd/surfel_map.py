@@ -21,7 +21,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_engine", "dsm_surfel_map_frames_fused", "dsm_surfel_map_dropped_poses", "dsm_surfel_map_pose_count",
     "dsm_surfel_map_get_pose", "dsm_surfel_map_get_links", "dsm_surfel_map_get_attached",
     "dsm_surfel_map_get_inactive_cloud", "dsm_surfel_map_get_cloud", "dsm_surfel_map_get_cloud_device", "dsm_surfel_map_set_publish",
-    "dsm_surfel_map_depth_input_u16",
+    "dsm_surfel_map_depth_input_u16", "dsm_surfel_map_image_input_color",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -64,6 +64,7 @@ def _bind(lib):
         lib.dsm_surfel_map_last_error.restype = C.c_char_p
         lib.dsm_surfel_map_image_input.argtypes = [_vp, _Stamp, C.c_int32, C.c_int32, C.c_size_t, C.c_char_p, _vp]
         lib.dsm_surfel_map_depth_input.argtypes = [_vp, _Stamp, C.c_int32, C.c_int32, C.c_size_t, C.c_char_p, _vp]
+        lib.dsm_surfel_map_image_input_color.argtypes = [_vp, _Stamp, C.c_int32, C.c_int32, C.c_size_t, C.c_char_p, _vp, _vp]
         lib.dsm_surfel_map_depth_input_u16.argtypes = [_vp, _Stamp, C.c_int32, C.c_int32, C.c_size_t, C.c_char_p, _vp, C.c_float, C.c_int32]
         lib.dsm_surfel_map_orb_results_input.argtypes = [_vp, _Stamp, _vp, C.c_int32, _vp, C.c_int32, _Stamp, _vp, _vp]
         for name in ("save_cloud", "save_mesh", "save_map"):
@@ -139,6 +140,16 @@ class SurfelMap:
         d = np.ascontiguousarray(depth, dtype=np.float32)
         self._check(self._lib.dsm_surfel_map_depth_input(self._h, _Stamp(*stamp), d.shape[1], d.shape[0], d.strides[0],
                                                          encoding.encode(), _ptr(d)))
+
+    def image_input_color(self, stamp, image, encoding: str, weights=None):
+        """a colour camera's image, uint8 [H,W,3] ('rgb8' / 'bgr8') or [H,W,4] ('rgba8' / 'bgra8'), converted to grey on the device at
+        upload: api.gray_from_color(image, encoding, weights); weights = (wr, wg, wb, shift), None = api.GRAY_OPENCV_14BIT"""
+        im = np.ascontiguousarray(image, dtype=np.uint8)
+        if im.ndim != 3:
+            raise ValueError("image_input_color takes a [H,W,C] image")
+        w4 = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32).reshape(4)
+        self._check(self._lib.dsm_surfel_map_image_input_color(self._h, _Stamp(*stamp), im.shape[1], im.shape[0], im.strides[0],
+                                                               encoding.encode(), _ptr(im), None if w4 is None else _ptr(w4)))
 
     def depth_input_u16(self, stamp, depth, scale, op="divide", encoding: str = "16UC1"):
         """a sensor's uint16 depth (16UC1), converted to metres on the device at upload: api.depth_from_u16(depth, scale, op)"""

@@ -324,10 +324,73 @@ int dsm_replay_enqueue_host_u16(dsm_handle *h, int32_t n, const uint8_t *image, 
 int dsm_host_pack_frames_u16(int32_t n, int32_t width, int32_t height, const uint8_t *const *images, const size_t *image_steps,
                              const uint16_t *const *depths, const size_t *depth_steps, uint8_t *dst_image, size_t dst_img_step,
                              size_t dst_img_frame_step, uint16_t *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step);
+
+/* ---- colour camera images, and one descriptor for both halves of a sensor's frame.  The reference takes whatever encoding the
+ * camera driver publishes: SurfelMap::image_input runs cv_bridge::toCvCopy(msg, MONO8) (surfel_map.cpp:86), which for rgb8 / bgr8 /
+ * rgba8 / bgra8 is OpenCV's 8-bit colour-to-grey -- a fixed-point weighted sum, computed here on the device in exact integer
+ * arithmetic (alpha is ignored):
+ *     grey = (R * gray_wr + G * gray_wg + B * gray_wb + (1 << (gray_shift - 1))) >> gray_shift
+ * The weights are an input because cv_bridge's result depends on the OpenCV it was built with (as the pose inverse depends on the
+ * caller's Eigen).  The presets restate OpenCV's and Pillow's constants; the two OpenCV rows are written from OpenCV's source as
+ * remembered, including which version uses which, and are NOT checked against an OpenCV build; the Pillow
+ * row is checked against Pillow by the test suite.  A caller with another OpenCV passes its own weights.
+ * Rules (DSM_E_INVALID before any device work): struct_size == sizeof(dsm_frame_format); image_format and depth_format known; for a
+ * colour format weights >= 0, 1 <= gray_shift <= 22 and gray_wr + gray_wg + gray_wb <= 1 << gray_shift (the result stays <= 255 and
+ * the sum inside int32: no saturation); for DSM_DEPTH_U16 the rules of the *_u16 calls; image step in BYTES >= channels * width,
+ * depth step in bytes >= 4 (2) * width.  mono8 + f32 does exactly what the plain calls do, mono8 + u16 what the *_u16 calls do.
+ * Colour rows go up into a staging area of the handle (4 * pitch * height bytes per slot, allocated at the handle's first colour
+ * call) and ONE kernel per call writes the grey bytes of the w pixels of each row into the slots' image planes, on the stream of
+ * the copy, before whatever says the upload has landed.  Rows at the slot pitch (img_step = channels * dsm_frame_pitch) are the
+ * fast layout; tight rows (channels * width) are taken too, any other step goes row by row; a device pointer is read in place. ---- */
+#define DSM_IMAGE_MONO8 0
+#define DSM_IMAGE_RGB8 1
+#define DSM_IMAGE_BGR8 2
+#define DSM_IMAGE_RGBA8 3
+#define DSM_IMAGE_BGRA8 4
+#define DSM_DEPTH_F32 0
+#define DSM_DEPTH_U16 1
+/* gray_wr, gray_wg, gray_wb, gray_shift (initialisers of an int32_t[4]) */
+#define DSM_GRAY_OPENCV_14BIT {4899, 9617, 1868, 14}   /* OpenCV 2.4 / 3.x RGB2Gray<uchar>: R2Y, G2Y, B2Y, yuv_shift, CV_DESCALE (ROS Kinetic / Melodic: the reference's era); the default */
+#define DSM_GRAY_OPENCV_15BIT {9798, 19235, 3735, 15}  /* OpenCV 4.x 8-bit path */
+#define DSM_GRAY_PIL_L {19595, 38470, 7471, 16}        /* Pillow's convert("L") */
+typedef struct dsm_frame_format {
+    uint32_t struct_size;   /* sizeof(dsm_frame_format) */
+    int32_t image_format;   /* DSM_IMAGE_MONO8, _RGB8, _BGR8, _RGBA8, _BGRA8 */
+    int32_t gray_wr, gray_wg, gray_wb, gray_shift;
+    int32_t depth_format;   /* DSM_DEPTH_F32, DSM_DEPTH_U16 */
+    float depth_scale;      /* DSM_DEPTH_U16: as the *_u16 calls */
+    int32_t depth_op;
+} dsm_frame_format;
+/* mono8 + f32, DSM_GRAY_OPENCV_14BIT, depth_scale 1 / DSM_DEPTH_U16_DIVIDE */
+void dsm_frame_format_init(dsm_frame_format *f);
+/* the *_u16 calls' signatures with `const void *` planes, steps in bytes and the format in place of (scale, op) */
+int dsm_frame_upload_fmt(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
+                         const dsm_frame_format *fmt);
+int dsm_frame_upload_device_fmt(dsm_handle *h, int slot, const void *image_dev, size_t img_step, const void *depth_dev, size_t depth_step,
+                                const dsm_frame_format *fmt);
+int dsm_frame_upload_async_fmt(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
+                               const dsm_frame_format *fmt);
+int dsm_frames_upload_async_fmt(dsm_handle *h, int slot0, int n, const void *image, size_t img_step, size_t img_frame_step,
+                                const void *depth, size_t depth_step, size_t depth_frame_step, const dsm_frame_format *fmt);
+/* each group's colour rows are converted on the stream that runs its superpixel stages, right behind their copy */
+int dsm_replay_enqueue_host_fmt(dsm_handle *h, int32_t n, const void *image, size_t img_step, size_t img_frame_step, const void *depth,
+                                size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16,
+                                const float *inv_poses16 /* may be NULL */, const dsm_frame_format *fmt);
+/* dsm_host_pack_frames for any format: the planes are copied as they are (channels * width image bytes and 4 or 2 * width depth
+ * bytes of each row); the weights are not looked at */
+int dsm_host_pack_frames_fmt(int32_t n, int32_t width, int32_t height, const void *const *images, const size_t *image_steps,
+                             const void *const *depths, const size_t *depth_steps, void *dst_image, size_t dst_img_step,
+                             size_t dst_img_frame_step, void *dst_depth, size_t dst_depth_step, size_t dst_depth_frame_step,
+                             const dsm_frame_format *fmt);
+
 /* debug tap: the planes of frame slot `slot` as the kernels read them, tight rows (image: height * width bytes, depth: height *
  * width floats); either output may be NULL.  Comes behind everything enqueued for the handle and the uploads that wrote the slot
  * (synchronises). */
 int dsm_debug_get_frame(dsm_handle *h, int slot, uint8_t *image, float *depth);
+/* debug tap: the WHOLE planes of frame slot `slot`, rows dsm_frame_pitch elements apart with their pad columns (image: pitch * height
+ * bytes, depth: pitch * height floats; either may be NULL), read -- or, with write != 0, overwritten: a test fills a slot with a
+ * pattern, uploads, and looks at what the upload left alone.  Ordered like dsm_debug_get_frame (synchronises). */
+int dsm_debug_frame_planes(dsm_handle *h, int slot, int write, uint8_t *image, float *depth);
 
 /* enqueue SurfelMap::fuse_map for the frame in `slot` against the resident map */
 int dsm_fuse_frame_resident(dsm_handle *h, int slot, int reference_frame_index, const float *pose16);

@@ -74,6 +74,14 @@ const char *dsm_surfel_map_last_error(const dsm_surfel_map *m);
  * converts with cv_bridge; other encodings are refused here).  The pixels are copied. */
 int dsm_surfel_map_image_input(dsm_surfel_map *m, dsm_stamp stamp, int32_t width, int32_t height, size_t step,
                                const char *encoding, const uint8_t *data);
+/* The same for a colour camera's image: rgb8, bgr8, rgba8 or bgra8 (anything else: DSM_E_INVALID), converted to grey on the device
+ * as dsm_frame_upload_fmt does -- what the reference's cv_bridge::toCvCopy(msg, MONO8) computes on the host (include/dsm.h:
+ * dsm_frame_format).  gray_weights4 = {wr, wg, wb, shift}, NULL = DSM_GRAY_OPENCV_14BIT; they are checked here (weights >= 0,
+ * 1 <= shift <= 22, sum <= 1 << shift).  step is in bytes (>= channels * width).  The frame waits for its pose at 3 or 4 bytes a
+ * pixel (beyond the page-locked pool: in pageable memory) and goes up together with a depth_input or a depth_input_u16 frame.
+ * DSM_E_STATE on an engine without dsm_frame_upload_fmt.  dsm_surfel_map_image_input itself keeps refusing colour. */
+int dsm_surfel_map_image_input_color(dsm_surfel_map *m, dsm_stamp stamp, int32_t width, int32_t height, size_t step,
+                                     const char *encoding, const void *data, const int32_t *gray_weights4 /* [4], may be NULL */);
 /* SurfelMap::depth_input (:93-101): TYPE_32FC1, metres, 0 = invalid. */
 int dsm_surfel_map_depth_input(dsm_surfel_map *m, dsm_stamp stamp, int32_t width, int32_t height, size_t step,
                                const char *encoding, const void *data);

@@ -136,10 +136,23 @@ class SurfelMap {
     SurfelMap &operator=(const SurfelMap &) = delete;
     ~SurfelMap() { dsm_surfel_map_destroy(m_); }
 
+    // a colour camera's message (rgb8 / bgr8 / rgba8 / bgra8) goes to dsm_surfel_map_image_input_color, which converts it to grey
+    // on the device with the weights of set_gray_weights -- what cv_bridge::toCvCopy(msg, MONO8) does on the reference's callback
+    // thread (surfel_map.cpp:86); mono8, and anything else (refused), goes to dsm_surfel_map_image_input as before
     template <typename ImagePtr> int image_input(const ImagePtr &image_input) {
+        const std::string &enc = image_input->encoding;
+        if (enc == "rgb8" || enc == "bgr8" || enc == "rgba8" || enc == "bgra8")
+            return check(dsm_surfel_map_image_input_color(m_, stamp_of(image_input->header.stamp), (int32_t)image_input->width,
+                                                          (int32_t)image_input->height, (size_t)image_input->step, enc.c_str(),
+                                                          image_input->data.data(), gray_weights_));
         return check(dsm_surfel_map_image_input(m_, stamp_of(image_input->header.stamp), (int32_t)image_input->width,
                                                 (int32_t)image_input->height, (size_t)image_input->step,
                                                 image_input->encoding.c_str(), image_input->data.data()));
+    }
+    // the grey weights of colour images: {wr, wg, wb, shift} of include/dsm.h's dsm_frame_format (DSM_GRAY_OPENCV_14BIT by default;
+    // DSM_GRAY_OPENCV_15BIT for a cv_bridge built against OpenCV 4.x); a bad set is refused when the next colour image arrives
+    void set_gray_weights(int32_t wr, int32_t wg, int32_t wb, int32_t shift) {
+        gray_weights_[0] = wr; gray_weights_[1] = wg; gray_weights_[2] = wb; gray_weights_[3] = shift;
     }
     template <typename ImagePtr> int depth_input(const ImagePtr &depth_input) {
         return check(dsm_surfel_map_depth_input(m_, stamp_of(depth_input->header.stamp), (int32_t)depth_input->width,
@@ -224,6 +237,7 @@ class SurfelMap {
         return rc; // (with DSM_WITH_ROS the callbacks report and carry on, as the reference's void callbacks do)
     }
     dsm_surfel_map *m_ = nullptr;
+    int32_t gray_weights_[4] = DSM_GRAY_OPENCV_14BIT;
     std::unique_ptr<PublishFn> publish_; // the callback: outlives the map (the destructor body destroys the map first)
 };
 
@@ -255,6 +269,7 @@ class SurfelMap {
 
     void image_input(const sensor_msgs::ImageConstPtr &image_input) { report(impl_.image_input(image_input), "image_input"); }
     void depth_input(const sensor_msgs::ImageConstPtr &image_input) { report(impl_.depth_input(image_input), "depth_input"); }
+    void set_gray_weights(int32_t wr, int32_t wg, int32_t wb, int32_t shift) { impl_.set_gray_weights(wr, wg, wb, shift); }
     void depth_input_u16(const sensor_msgs::ImageConstPtr &image_input, float scale, int op = DSM_DEPTH_U16_DIVIDE) {
         report(impl_.depth_input_u16(image_input, scale, op), "depth_input_u16");
     }
