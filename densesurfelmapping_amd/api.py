@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
     # colour camera images converted to grey on the device, and the format descriptor for both halves of a frame
     "dsm_frame_format_init", "dsm_frame_upload_fmt", "dsm_frame_upload_device_fmt", "dsm_frame_upload_async_fmt",
     "dsm_frames_upload_async_fmt", "dsm_replay_enqueue_host_fmt", "dsm_host_pack_frames_fmt", "dsm_debug_frame_planes",
+    # the hexagon mesh as vertex and index buffers
+    "dsm_mesh_compose", "dsm_mesh_indices",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -142,6 +144,9 @@ def gray_from_color(image, encoding, weights=None) -> np.ndarray:
 # dsm_cloud_compose's map part (include/dsm.h dsm_cloud_select)
 CLOUD_SELECT_NONE, CLOUD_SELECT_MATURE, CLOUD_SELECT_NONZERO = 0, 1, 2
 CLOUD_TILE = 1024  # records per workgroup of the map compaction (dsm_device.h kCloudTile)
+# dsm_mesh_compose's vertex layouts (include/dsm.h dsm_mesh_vertex_layout) and their bytes per surfel (six vertices)
+MESH_VERTEX_REF6, MESH_VERTEX_XYZ_RGBA8 = 0, 1
+MESH_SURFEL_BYTES = {MESH_VERTEX_REF6: 144, MESH_VERTEX_XYZ_RGBA8: 96}
 
 
 class DsmError(RuntimeError):
@@ -218,6 +223,8 @@ def load_library():
     lib.dsm_store_download.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
     lib.dsm_cloud_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, _vp, C.c_int, C.c_int32, _vp]
     lib.dsm_frame_cloud.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int32, _vp]
+    lib.dsm_mesh_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int32, _vp]
+    lib.dsm_mesh_indices.argtypes = [_vp, C.c_int32, _vp, C.c_int]
     lib.dsm_frame_upload.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_upload_device.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_pitch.argtypes = [_vp, _vp]
@@ -503,6 +510,34 @@ class FusionFunctions:
         out = np.zeros((max(cap, 1), 4), np.float32)
         self._check(self._lib.dsm_cloud_compose(self._h, select, len(seg), _ptr(b), _ptr(c), _ptr(out), 0, cap, C.byref(n)))
         return out[: n.value].copy()
+
+    # ---- the hexagon mesh (surfel_map.cpp:1176-1280) -----------------------------------------------
+    def mesh_compose(self, select=CLOUD_SELECT_MATURE, segments=(), layout=MESH_VERTEX_REF6, dst_ptr=None, cap=None):
+        """dsm_mesh_compose: six hexagon vertices per surfel -- the store's record runs `segments` [(begin, count), ...] first,
+        then the map records that pass `select` (save_mesh's order).  Returns an (n, 36) float32 array (MESH_VERTEX_REF6:
+        6 x (x y z c c c)) or an (n, 24) one (MESH_VERTEX_XYZ_RGBA8: 6 x (x y z rgba), the fourth the bytes r g b 255) -- or,
+        with dst_ptr (device memory of cap surfels), n."""
+        seg = np.ascontiguousarray(np.asarray(segments, np.int32).reshape(-1, 2))
+        b = np.ascontiguousarray(seg[:, 0]) if len(seg) else np.zeros(1, np.int32)
+        c = np.ascontiguousarray(seg[:, 1]) if len(seg) else np.zeros(1, np.int32)
+        n = C.c_int32(0)
+        if dst_ptr is not None:
+            self._check(self._lib.dsm_mesh_compose(self._h, select, len(seg), _ptr(b), _ptr(c), layout, _vp(dst_ptr), 1, cap, C.byref(n)))
+            return n.value
+        if cap is None:  # size it from the bound: the runs plus the map records
+            cap = (self.map_size() if select != CLOUD_SELECT_NONE else 0) + int(seg[:, 1].sum() if len(seg) else 0)
+        out = np.zeros((max(cap, 1), MESH_SURFEL_BYTES[layout] // 4), np.float32)
+        self._check(self._lib.dsm_mesh_compose(self._h, select, len(seg), _ptr(b), _ptr(c), layout, _ptr(out), 0, cap, C.byref(n)))
+        return out[: n.value].copy()
+
+    def mesh_indices(self, n_surfels, dst_ptr=None):
+        """dsm_mesh_indices: the (n_surfels * 4, 3) uint32 triangles of n_surfels hexagons -- or, with dst_ptr, into device memory."""
+        if dst_ptr is not None:
+            self._check(self._lib.dsm_mesh_indices(self._h, n_surfels, _vp(dst_ptr), 1))
+            return n_surfels
+        out = np.zeros((max(n_surfels, 1) * 4, 3), np.uint32)
+        self._check(self._lib.dsm_mesh_indices(self._h, n_surfels, _ptr(out), 0))
+        return out[: n_surfels * 4].copy()
 
     def frame_cloud(self, slot, pose7, dst_ptr=None, cap=None):
         """dsm_frame_cloud: publish_raw_pointcloud of the frame in `slot`; pose7 = px py pz qx qy qz qw (geometry_msgs/Pose).

@@ -1937,6 +1937,74 @@ int dsm_cloud_compose(dsm_handle *h, int select, int32_t n_segments, const int32
     return DSM_OK;
 }
 
+// the store's record runs first, then the map part: SurfelMap::save_mesh's order (SM.cpp:1226-1248)
+int dsm_mesh_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, int vertex_layout,
+                     void *dst, int dst_on_device, int32_t cap, int32_t *n) {
+    if (!h || !n || cap < 0) return DSM_E_INVALID;
+    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
+    if (vertex_layout != kMeshRef6 && vertex_layout != kMeshXyzRgba8) return fail(h, DSM_E_INVALID, "mesh vertex layout %d", vertex_layout);
+    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
+    if (cap > 0 && !dst) return fail(h, DSM_E_INVALID, "null output");
+    if (dst_on_device && ((uintptr_t)dst & 3)) return fail(h, DSM_E_INVALID, "device output not 4-byte aligned");
+    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
+    // the runs, checked before anything reaches the device; empty ones are dropped
+    std::vector<int32_t> seg;
+    int64_t runs_total = 0;
+    for (int32_t s = 0; s < n_segments; s++) {
+        const int32_t b = store_begin[s], c = store_count[s];
+        if (b < 0 || c < 0 || (int64_t)b + c > h->store_n)
+            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, c, h->store_n);
+        if (!c) continue;
+        seg.push_back(b);
+        seg.push_back(c);
+        seg.push_back((int32_t)runs_total);
+        runs_total += c;
+    }
+    const int n_upper = select == kCloudNone ? 0 : h->map_upper;
+    const int64_t bound = (int64_t)n_upper + runs_total;
+    if (bound > INT32_MAX) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)bound);
+    int rc = bind_device(h);
+    if (rc) return rc;
+    const size_t tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    const size_t rec_bytes = (size_t)mesh_surfel_bytes(vertex_layout);
+    // where the vertices go: the caller's device memory, or staging for a host destination (no more than there can be)
+    const int32_t dev_cap = (int32_t)(bound < cap ? bound : cap);
+    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), dst_on_device ? 0 : (size_t)dev_cap * (rec_bytes / sizeof(float4))))) return rc;
+    if (dst_on_device && (rc = pub_order_dst(h))) return rc;
+    void *out = dst_on_device ? dst : (void *)h->d_pub_out;
+    int32_t *d_total = h->d_pub, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
+    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    hipError_t e = launch_mesh_gather(h->d_store, d_seg, (int)(seg.size() / 3), (int)runs_total, vertex_layout, out, dev_cap, h->stream);
+    if (e == hipSuccess)
+        e = launch_mesh_map(h->hc.local, h->hc.n_local, n_upper, select, d_tiles, d_total, vertex_layout, out, (int)runs_total, dev_cap, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "mesh launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const int64_t total = (int64_t)h->h_scalars[5] + runs_total;
+    *n = (int32_t)total;
+    if (total > cap) return fail(h, DSM_E_CAPACITY, "%lld surfels exceed the caller's capacity %d", (long long)total, cap);
+    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)total * rec_bytes, hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
+int dsm_mesh_indices(dsm_handle *h, int32_t n_surfels, void *dst, int dst_on_device) {
+    if (!h || n_surfels < 0) return DSM_E_INVALID;
+    if (n_surfels > 715827882) return fail(h, DSM_E_INVALID, "%d surfels: vertex indices pass 32 bits", n_surfels);
+    if (n_surfels > 0 && !dst) return fail(h, DSM_E_INVALID, "null output");
+    if (dst_on_device && ((uintptr_t)dst & 3)) return fail(h, DSM_E_INVALID, "device output not 4-byte aligned");
+    if (n_surfels == 0) return DSM_OK;
+    int rc = bind_device(h);
+    if (rc) return rc;
+    if (!dst_on_device && (rc = pub_reserve(h, 0, (size_t)n_surfels * 3))) return rc;
+    if (dst_on_device && (rc = pub_order_dst(h))) return rc;
+    uint32_t *out = dst_on_device ? (uint32_t *)dst : (uint32_t *)h->d_pub_out;
+    const hipError_t e = launch_mesh_indices(out, n_surfels, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "mesh index launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!dst_on_device) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)n_surfels * 48, hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
 int dsm_frame_cloud(dsm_handle *h, int slot, const double *pose7, void *dst, int dst_on_device, int32_t cap, int32_t *n) {
     if (!h || !n || cap < 0) return DSM_E_INVALID;
     if (!pose7) return fail(h, DSM_E_INVALID, "null pose");

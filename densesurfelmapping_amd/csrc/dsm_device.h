@@ -206,4 +206,17 @@ hipError_t launch_cloud_gather(const float4 *src, const int32_t *seg, int n_seg,
 hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, int w, int h, const RawCloudParams &p, bool eigen33, float4 *out,
                             hipStream_t st);
 
+// ---- the hexagon mesh (dsm_k_mesh.h)
+constexpr int kMeshRef6 = 0, kMeshXyzRgba8 = 1; // dsm_mesh_vertex_layout of include/dsm.h
+constexpr int mesh_surfel_bytes(int layout) { return layout == kMeshRef6 ? 144 : 96; }
+// the six vertices of every record [0, min(*n_ptr, n_upper)) that passes `select`, in map order, as records base, base + 1, ...
+// of `out` (4-byte aligned; faster when 16-byte aligned), none at or beyond record cap; total[0] = how many passed.
+// tile_cnt: ceil(n_upper / 1024) ints of scratch
+hipError_t launch_mesh_map(const dsm_surfel *rec, const int32_t *n_ptr, int n_upper, int select, int32_t *tile_cnt, int32_t *total, int layout,
+                           void *out, int base, int cap, hipStream_t st);
+// runs of the records src (seg: launch_cloud_gather's table; `total` records in all) as records 0, 1, ... of `out`, below cap
+hipError_t launch_mesh_gather(const dsm_surfel *src, const int32_t *seg, int n_seg, int total, int layout, void *out, int cap, hipStream_t st);
+// 12 indices per surfel: 6 i + {0,1,2, 1,3,2, 2,3,4, 4,3,5}
+hipError_t launch_mesh_indices(uint32_t *out, int n, hipStream_t st);
+
 } // namespace dsm

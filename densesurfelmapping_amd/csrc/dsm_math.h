@@ -775,6 +775,44 @@ template <bool E33 = false> DSM_HD Surfel spawn_surfel(const Intrinsics &k, int 
     return e;
 }
 
+// ---------------------------------------------------------------- the hexagon of a surfel, SM.cpp:1176-1216
+// (SM.cpp = surfel_fusion/src/surfel_map.cpp.)  (int)color as the reference's x86 build converts it: cvttss2si gives
+// INT_MIN ("integer indefinite") for a NaN and for every value outside int.  The device's convert saturates instead
+// (0 for a NaN, INT_MAX above), hence the explicit range test.  Every float below -2^31 is also below -2^31 - 1.
+DSM_HD int surfel_color_int(float color) {
+    return (color >= -2147483648.0f && color < 2147483648.0f) ? (int)color : (-2147483647 - 1);
+}
+// the colour byte of the PLY's uchar properties: the int colour clamped to 0..255
+DSM_HD uint32_t surfel_color_byte(int surfel_color) {
+    return surfel_color < 0 ? 0u : surfel_color > 255 ? 255u : (uint32_t)surfel_color;
+}
+// SurfelMap::push_a_surfel: the six corners of a hexagon of circumradius `size` in the surfel's plane, in the order the
+// reference pushes them, and the int colour.  S = dsm_surfel (or Surfel): px..pz, nx..nz, size, color.
+template <typename S> DSM_HD void surfel_hexagon(const S &s, float pt[6][3], int &surfel_color) {
+    surfel_color = surfel_color_int(s.color);
+    const float pos[3] = {s.px, s.py, s.pz}, nrm[3] = {s.nx, s.ny, s.nz};
+    float x_dir[3] = {-1 * s.ny, s.nx, 0};
+    // Vector3f::normalize(): divide by sqrt(squaredNorm) when that is positive (Eigen 3.3); the three squares of a
+    // fixed-size 3-vector are summed as a0 + (a1 + a2)
+    const float z = x_dir[0] * x_dir[0] + (x_dir[1] * x_dir[1] + x_dir[2] * x_dir[2]);
+    if (z > 0.f) {
+        const float nn = sqrtf(z);
+        for (int i = 0; i < 3; i++) x_dir[i] = x_dir[i] / nn;
+    }
+    const float y_dir[3] = {nrm[1] * x_dir[2] - nrm[2] * x_dir[1], nrm[2] * x_dir[0] - nrm[0] * x_dir[2], nrm[0] * x_dir[1] - nrm[1] * x_dir[0]};
+    const float radius = s.size;
+    const float h_r = (float)(radius * 0.5);
+    const float t_r = (float)(radius * 0.86603);
+    for (int i = 0; i < 3; i++) {
+        pt[0][i] = (pos[i] - x_dir[i] * h_r) - y_dir[i] * t_r;
+        pt[1][i] = (pos[i] + x_dir[i] * h_r) - y_dir[i] * t_r;
+        pt[2][i] = pos[i] - x_dir[i] * radius;
+        pt[3][i] = pos[i] + x_dir[i] * radius;
+        pt[4][i] = (pos[i] - x_dir[i] * h_r) + y_dir[i] * t_r;
+        pt[5][i] = (pos[i] + x_dir[i] * h_r) + y_dir[i] * t_r;
+    }
+}
+
 // worker k's [begin,end) over n items, FF.cpp:198-202 / 392-396 / 471-475
 DSM_HD int chunk_of(int n, int i) {
     int step = n / kWorkers;

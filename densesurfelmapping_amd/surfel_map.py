@@ -22,6 +22,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_get_pose", "dsm_surfel_map_get_links", "dsm_surfel_map_get_attached",
     "dsm_surfel_map_get_inactive_cloud", "dsm_surfel_map_get_cloud", "dsm_surfel_map_get_cloud_device", "dsm_surfel_map_set_publish",
     "dsm_surfel_map_depth_input_u16", "dsm_surfel_map_image_input_color",
+    "dsm_surfel_map_get_mesh", "dsm_surfel_map_get_mesh_device", "dsm_surfel_map_save_mesh_binary",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -88,6 +89,10 @@ def _bind(lib):
             lib.dsm_surfel_map_get_cloud.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
             lib.dsm_surfel_map_get_cloud_device.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
             lib.dsm_surfel_map_set_publish.argtypes = [_vp, C.c_uint32, _PublishFn, _vp]
+        if hasattr(lib, "dsm_surfel_map_get_mesh"):  # (nor the device mesh)
+            lib.dsm_surfel_map_get_mesh.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
+            lib.dsm_surfel_map_get_mesh_device.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
+            lib.dsm_surfel_map_save_mesh_binary.argtypes = [_vp, C.c_char_p]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -183,6 +188,27 @@ class SurfelMap:
         self._check(self._lib.dsm_surfel_map_save_mesh(self._h, path.encode()))
 
     save_map = save_mesh  # surfel_map.cpp:75-81
+
+    # ---- the mesh as a device product (dsm_mesh_compose)
+    def get_mesh(self, layout=api.MESH_VERTEX_REF6, dst_ptr=None, cap=None):
+        """save_mesh's hexagons as a vertex buffer built on the GPU: the attached surfels keyframe by keyframe, then the active
+        ones with update_times >= 5.  (n, 36) float32 for api.MESH_VERTEX_REF6 (6 x (x y z c c c)), (n, 24) for
+        api.MESH_VERTEX_XYZ_RGBA8 (6 x (x y z rgba)) -- or, with dst_ptr (device memory of cap surfels), n.  Triangles:
+        FusionFunctions.mesh_indices / dsm_mesh_indices."""
+        n = C.c_int32()
+        if dst_ptr is not None:
+            self._check(self._lib.dsm_surfel_map_get_mesh_device(self._h, layout, _vp(dst_ptr), cap, C.byref(n)))
+            return n.value
+        rc = self._lib.dsm_surfel_map_get_mesh(self._h, layout, None, 0, C.byref(n))  # the count (DSM_E_CAPACITY unless empty)
+        if rc not in (0, api.DSM_E_CAPACITY):
+            self._check(rc)
+        out = np.zeros((max(n.value, 1), api.MESH_SURFEL_BYTES[layout] // 4), dtype=np.float32)
+        self._check(self._lib.dsm_surfel_map_get_mesh(self._h, layout, _ptr(out), n.value, C.byref(n)))
+        return out[: n.value]
+
+    def save_mesh_binary(self, path: str):
+        """save_mesh's mesh as a binary little-endian PLY (15-byte vertices, 13-byte faces), streamed from the GPU in chunks"""
+        self._check(self._lib.dsm_surfel_map_save_mesh_binary(self._h, path.encode()))
 
     # ---- taps
     @property

@@ -253,6 +253,26 @@ int dsm_cloud_compose(dsm_handle *h, int select, int32_t n_segments, const int32
  * device destination is ordered like dsm_cloud_compose's. */
 int dsm_frame_cloud(dsm_handle *h, int slot, const double *pose7, void *dst, int dst_on_device, int32_t cap, int32_t *n);
 
+/* ---- the hexagon mesh (the reference's save_mesh, surfel_map.cpp:1176-1280): six vertices per surfel -- the corners of a
+ * hexagon of circumradius `size` in the surfel's plane, exactly push_a_surfel's arithmetic -- and four triangles ---- */
+typedef enum {
+    DSM_MESH_VERTEX_REF6 = 0,      /* x y z c c c as six floats, c = (float)(int)color: the reference's `vertexs`; 144 bytes per surfel */
+    DSM_MESH_VERTEX_XYZ_RGBA8 = 1  /* x y z as floats, then the bytes r g b 255 with r = g = b = (int)color clamped to 0..255: a
+                                      vertex buffer; 96 bytes per surfel */
+} dsm_mesh_vertex_layout;
+/* The vertices of the store's RECORD runs [store_begin[s], +store_count[s]) for s < n_segments, in list order, THEN those of
+ * the map part chosen by `select` (dsm_cloud_select), in map order: save_mesh's order, the REVERSE of dsm_cloud_compose's (map
+ * part first).  cap_surfels and *n_surfels count surfels (six vertices each); dst holds cap_surfels * 144 or * 96 bytes, host
+ * memory (dst_on_device = 0) or device memory (4-byte aligned; 16-byte alignment is faster).  (int)color of a NaN or of a
+ * value outside int is INT_MIN, as the reference's x86 conversion gives.  Everything else as dsm_cloud_compose: a bad run is
+ * DSM_E_INVALID before any device work; more than cap_surfels: DSM_E_CAPACITY, *n_surfels = the count needed, nothing written
+ * past cap_surfels; a device destination is written behind the work enqueued on the null stream so far.  Synchronises. */
+int dsm_mesh_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                     int vertex_layout, void *dst, int dst_on_device, int32_t cap_surfels, int32_t *n_surfels);
+/* The index buffer of n_surfels hexagons: 12 uint32 each, 6 i + {0,1,2, 1,3,2, 2,3,4, 4,3,5} (the faces of :1274-1277), into
+ * host or device memory (n_surfels * 48 bytes; at most 715827882 surfels: the vertex index is 32 bits).  Synchronises. */
+int dsm_mesh_indices(dsm_handle *h, int32_t n_surfels, void *dst, int dst_on_device);
+
 /* Copy a frame into frame slot `slot` (0 .. frame_slots-1 of the config) and return when it is there (the host
  * buffers may be reused).  By default the copy is ordered behind everything enqueued so far.  With
  * DSM_FLAG_UPLOAD_STREAM it runs on the handle's upload stream instead: it waits only for the enqueued frames that

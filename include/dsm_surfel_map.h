@@ -142,6 +142,22 @@ typedef void (*dsm_surfel_map_publish_fn)(void *user, const dsm_surfel_map_publi
  * default; no extra work, no synchronisation). */
 int dsm_surfel_map_set_publish(dsm_surfel_map *m, uint32_t kinds_mask, dsm_surfel_map_publish_fn fn, void *user);
 
+/* ---- the hexagon mesh of save_mesh as vertex buffers, built on the GPU (dsm_mesh_compose of dsm.h) ----
+ * Six vertices per surfel in `vertex_layout` (dsm_mesh_vertex_layout: 144 or 96 bytes per surfel), in save_mesh's order
+ * (:1226-1248): the attached surfels keyframe by keyframe in poses_database order (not store order), then the active surfels
+ * with update_times >= 5.  Triangles: dsm_mesh_indices.  DSM_E_STATE before the first fuse; more than cap_surfels:
+ * DSM_E_CAPACITY with *n_surfels = the count needed.  Synchronises. */
+int dsm_surfel_map_get_mesh(dsm_surfel_map *m, int vertex_layout, void *out, int32_t cap_surfels, int32_t *n_surfels);
+/* the same into device memory of the node's GPU (4-byte aligned; 16-byte alignment is faster) */
+int dsm_surfel_map_get_mesh_device(dsm_surfel_map *m, int vertex_layout, void *dst_device, int32_t cap_surfels, int32_t *n_surfels);
+/* save_mesh's mesh as `format binary_little_endian 1.0`: the same elements and properties as the ASCII file, a vertex = three
+ * floats and three uchar (the int colour clamped to 0..255), a face = the uchar 3 and three int.  The vertices come from the
+ * GPU in chunks: the attached surfels 256 Ki at a time (24 MiB of page-locked memory at most), the active surfels in ONE piece
+ * -- the engine composes the map part whole, so that piece is bounded by the surfel capacity (96 bytes per mature active
+ * surfel, on the host and in device staging).  Unlike save_mesh (which returns silently, as the reference does) an unopenable
+ * path is DSM_E_INVALID; the file is opened after the last call that can fail without it, and removed if a later one fails. */
+int dsm_surfel_map_save_mesh_binary(dsm_surfel_map *m, const char *path);
+
 /* ---- taps (what the publish_* methods read) ---- */
 dsm_handle *dsm_surfel_map_engine(dsm_surfel_map *m); /* active map: dsm_map_size / dsm_map_download */
 int64_t dsm_surfel_map_frames_fused(const dsm_surfel_map *m);

@@ -187,6 +187,21 @@ class SurfelMap {
     int save_cloud(const std::string &save_path_name) { return check(dsm_surfel_map_save_cloud(m_, save_path_name.c_str())); }
     int save_mesh(const std::string &save_path_name) { return check(dsm_surfel_map_save_mesh(m_, save_path_name.c_str())); }
 
+    // save_mesh's hexagons as a vertex buffer built on the GPU: six vertices per surfel in `layout` (36 floats per surfel for
+    // DSM_MESH_VERTEX_REF6, 24 for DSM_MESH_VERTEX_XYZ_RGBA8 whose fourth is the bytes r g b 255); triangles: dsm_mesh_indices
+    int get_mesh(dsm_mesh_vertex_layout layout, std::vector<float> &vertices) {
+        const size_t per = layout == DSM_MESH_VERTEX_REF6 ? 36 : 24;
+        int32_t n = 0;
+        int rc = dsm_surfel_map_get_mesh(m_, layout, nullptr, 0, &n);
+        while (rc == DSM_E_CAPACITY) {
+            vertices.resize((size_t)n * per);
+            rc = dsm_surfel_map_get_mesh(m_, layout, vertices.data(), n, &n);
+        }
+        if (rc == DSM_OK) vertices.resize((size_t)n * per);
+        return check(rc);
+    }
+    int save_mesh_binary(const std::string &save_path_name) { return check(dsm_surfel_map_save_mesh_binary(m_, save_path_name.c_str())); }
+
     // the point-cloud topics (publish_*_pointcloud, surfel_map.cpp:1115-1151, 1283-1454): xyzi = 4 floats per point
     int get_cloud(dsm_cloud_kind kind, std::vector<float> &xyzi) {
         int32_t n = 0;
