@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "dsm_device.h"
+#include "dsm_frame_copy.h"
 #include "dsm_frame_format.h"
 
 using namespace dsm;
@@ -501,10 +502,6 @@ int capture(dsm_handle *h, const DeviceCtx &ctx, bool with_compaction, int lo, i
     return DSM_OK;
 }
 
-// Frames that come with the enqueue call (dsm_replay_enqueue_host): `n` frames in page-locked host memory, frame i at
-// image + i * img_frame_step / depth + i * depth_frame_step.  They go up ON THE STREAM THAT RUNS THEIR SUPERPIXEL STAGES, right
-// in front of them, into the frame slots of the pipelines that take them (slot = pipeline): no upload stream, no event between
-// an upload and its consumer, and a transfer holds up only the hardware queue of the work that waits for it anyway.
 // uint16 depth and how it becomes metres (the *_u16 entry points of include/dsm.h)
 struct DepthU16 {
     float scale;
@@ -520,9 +517,49 @@ bool depth_u16_ok(float scale, int op) {
                                           "DSM_DEPTH_U16_DIVIDE or DSM_DEPTH_U16_MULTIPLY", (double)(scale), (int)(op));          \
     } while (0)
 
+// a colour image format and its grey weights (the *_fmt entry points of include/dsm.h; checked by dsm_fmt::parse)
+using ImageGray = dsm_fmt::Gray;
+// bytes per pixel of the planes a call brings
+size_t image_elem(const ImageGray *g) { return g ? (size_t)g->ch : 1; }
+size_t depth_elem(const DepthU16 *u) { return u ? 2 : 4; }
+
+struct HostFrames {
+    const uint8_t *image = nullptr; // grey, or packed colour pixels with gray set
+    const void *depth = nullptr; // float, or uint16 with u16 set
+    size_t img_step = 0, img_frame_step = 0, depth_step = 0, depth_frame_step = 0;
+    const DepthU16 *u16 = nullptr;
+    const ImageGray *gray = nullptr;
+};
+// What a call that brings n frames checks of them, in this order: the pointers and the slot (kOneSlot) or slots [slot0, slot0 + n)
+// (kSlotRange) -- neither with kNoSlots: dsm_replay_enqueue_host has its own pointer check and picks the slots itself --, then the steps.
+enum FrameSlots { kNoSlots, kOneSlot, kSlotRange };
+int check_frames(dsm_handle *h, FrameSlots form, int slot0, int n, const HostFrames &f) {
+    if (form != kNoSlots && (!f.image || !f.depth)) return fail(h, DSM_E_INVALID, "null image/depth");
+    if (form == kOneSlot && (slot0 < 0 || slot0 >= h->hc.n_slots)) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot0, h->hc.n_slots);
+    if (form == kSlotRange && (n < 1 || slot0 < 0 || slot0 + n > h->hc.n_slots)) return fail(h, DSM_E_INVALID, "frame slots [%d,%d) out of range [0,%d)", slot0, slot0 + n, h->hc.n_slots);
+    const size_t w = (size_t)h->hc.w, hh = (size_t)h->hc.h;
+    if (f.img_step < w * image_elem(f.gray) || f.depth_step < w * depth_elem(f.u16)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (n > 1 && (f.img_frame_step < f.img_step * hh || f.depth_frame_step < f.depth_step * hh)) return fail(h, DSM_E_INVALID, "frame step smaller than a frame");
+    return DSM_OK;
+}
+
+// The plan (dsm_frame_copy.h) for n planes of the handle's frame size at `elem` bytes a pixel into a destination laid out like the
+// slots -- rows at the pitch, frames a slot apart -- and its transfers, in order, on `st`.
+dsm_copy::Plan slot_plan(const dsm_handle *h, int n, size_t elem, size_t step, size_t frame_step, bool pack_tight) {
+    return dsm_copy::plan({n, (size_t)h->hc.h, (size_t)h->hc.w * elem, step, frame_step, (size_t)h->hc.pitch * elem, (size_t)h->hc.slot_elems * elem, pack_tight});
+}
+int copy_planes(dsm_handle *h, void *dst, const void *src, const dsm_copy::Plan &p, hipMemcpyKind kind, hipStream_t st) {
+    for (int i = 0; i < p.transfers; i++) {
+        char *d = (char *)dst + (size_t)i * p.dst_advance;
+        const char *s = (const char *)src + (size_t)i * p.src_advance;
+        if (p.two_d) HIP_TRY(h, hipMemcpy2DAsync(d, p.dst_step, s, p.src_step, p.row_bytes, p.rows, kind, st));
+        else HIP_TRY(h, hipMemcpyAsync(d, s, p.bytes, kind, st));
+    }
+    return DSM_OK;
+}
+
 // n frames of uint16 depth (frame i at depth + i * frame_step bytes, rows `step` bytes apart) converted into the float depth planes of
-// slots slot0 .. slot0 + n - 1, on `st`: the rows go into the slots' u16 staging -- rows at the slot pitch and frames a slot apart, or
-// tight rows and frames back to back, as one transfer; any other layout frame by frame (row by row unless at the pitch) at the pitch --
+// slots slot0 .. slot0 + n - 1, on `st`: the rows go into the slots' u16 staging as the plan says (the kernel takes tight rows too),
 // and ONE kernel converts all n behind the copy.  Device memory with even pointer and steps is read where it is.
 int upload_depth_u16(dsm_handle *h, int slot0, int n, const void *depth, size_t step, size_t frame_step, hipMemcpyKind kind, const DepthU16 &u,
                      hipStream_t st) {
@@ -532,42 +569,28 @@ int upload_depth_u16(dsm_handle *h, int slot0, int n, const void *depth, size_t 
         h->allocs.push_back(p);
         h->d_stage_u16 = (uint16_t *)p;
     }
-    const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    const size_t plane = (size_t)h->hc.slot_elems, tight = (size_t)w * (size_t)hh;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot0 * h->hc.slot_elems;
-    uint16_t *sg = h->d_stage_u16 + (size_t)slot0 * plane;
+    uint16_t *sg = h->d_stage_u16 + (size_t)slot0 * (size_t)h->hc.slot_elems;
     const uint16_t *src = sg;
-    int64_t src_row = pitch, src_frame = (int64_t)plane;
-    const bool flat = step == (size_t)pitch * 2, tight_rows = step == (size_t)w * 2;
+    int64_t src_row, src_frame;
     if (kind == hipMemcpyDeviceToDevice && step % 2 == 0 && ((uintptr_t)depth & 1) == 0 && (n == 1 || frame_step % 2 == 0)) {
         src = (const uint16_t *)depth;
         src_row = (int64_t)(step / 2);
         src_frame = n == 1 ? 0 : (int64_t)(frame_step / 2);
-    } else if (flat && (n == 1 || frame_step == plane * 2)) {
-        HIP_TRY(h, hipMemcpyAsync(sg, depth, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 2, kind, st));
-    } else if (tight_rows && (n == 1 || frame_step == tight * 2)) {
-        HIP_TRY(h, hipMemcpyAsync(sg, depth, tight * (size_t)n * 2, kind, st)); // (n tight frames fit the n slots' planes)
-        src_row = w;
-        src_frame = (int64_t)tight;
     } else {
-        for (int i = 0; i < n; i++) {
-            const char *fs = (const char *)depth + (size_t)i * frame_step;
-            if (flat) HIP_TRY(h, hipMemcpyAsync(sg + (size_t)i * plane, fs, ((size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 2, kind, st));
-            else HIP_TRY(h, hipMemcpy2DAsync(sg + (size_t)i * plane, (size_t)pitch * 2, fs, step, (size_t)w * 2, (size_t)hh, kind, st));
-        }
+        const dsm_copy::Plan p = slot_plan(h, n, 2, step, frame_step, true);
+        if (int rc = copy_planes(h, sg, depth, p, kind, st)) return rc;
+        src_row = (int64_t)(p.out_step / 2);
+        src_frame = (int64_t)(p.out_frame_step / 2);
     }
-    const hipError_t e = launch_depth_u16(dd, pitch, h->hc.slot_elems, src, src_row, src_frame, w, hh, n, u.scale, u.op, st);
+    const hipError_t e = launch_depth_u16(dd, h->hc.pitch, h->hc.slot_elems, src, src_row, src_frame, h->hc.w, h->hc.h, n, u.scale, u.op, st);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "u16 depth conversion: %s", hipGetErrorString(e));
     return DSM_OK;
 }
 
-// a colour image format and its grey weights (the *_fmt entry points of include/dsm.h; checked by dsm_fmt::parse)
-using ImageGray = dsm_fmt::Gray;
-
 // n frames of packed colour pixels (frame i at image + i * frame_step bytes, rows `step` bytes apart) converted into the grey image
-// planes of slots slot0 .. slot0 + n - 1, on `st`: the rows go into the slots' colour staging -- rows at the slot pitch and frames a
-// slot apart, or tight rows and frames back to back, as one transfer; any other layout frame by frame, row by row, at the pitch -- and
-// ONE kernel converts all n behind the copy.  Device memory is read where it is.
+// planes of slots slot0 .. slot0 + n - 1, on `st`: the rows go into the slots' colour staging as the plan says, and ONE kernel
+// converts all n behind the copy.  Device memory is read where it is.
 int upload_image_gray(dsm_handle *h, int slot0, int n, const void *image, size_t step, size_t frame_step, hipMemcpyKind kind, const ImageGray &g,
                       hipStream_t st) {
     if (!h->d_stage_gray && kind != hipMemcpyDeviceToDevice) { // (no memset behind the allocation: it would race the first copy, which is on another stream)
@@ -576,76 +599,41 @@ int upload_image_gray(dsm_handle *h, int slot0, int n, const void *image, size_t
         h->allocs.push_back(p);
         h->d_stage_gray = (uint8_t *)p;
     }
-    const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    const size_t ch = (size_t)g.ch, plane = (size_t)h->hc.slot_elems, tight = (size_t)w * (size_t)hh;
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot0 * h->hc.slot_elems;
-    uint8_t *sg = h->d_stage_gray ? h->d_stage_gray + (size_t)slot0 * plane * 4 : nullptr;
-    const uint8_t *src = sg;
-    int64_t src_row = (int64_t)((size_t)pitch * ch), src_frame = (int64_t)(plane * ch);
-    const bool flat = step == (size_t)pitch * ch, tight_rows = step == (size_t)w * ch;
-    if (kind == hipMemcpyDeviceToDevice) {
-        src = (const uint8_t *)image;
-        src_row = (int64_t)step;
-        src_frame = n == 1 ? 0 : (int64_t)frame_step;
-    } else if (flat && (n == 1 || frame_step == plane * ch)) {
-        HIP_TRY(h, hipMemcpyAsync(sg, image, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * ch, kind, st));
-    } else if (tight_rows && (n == 1 || frame_step == tight * ch)) {
-        HIP_TRY(h, hipMemcpyAsync(sg, image, tight * (size_t)n * ch, kind, st)); // (n tight frames fit the n slots' staging)
-        src_row = (int64_t)((size_t)w * ch);
-        src_frame = (int64_t)(tight * ch);
-    } else {
-        for (int i = 0; i < n; i++) {
-            const char *fs = (const char *)image + (size_t)i * frame_step;
-            if (flat) HIP_TRY(h, hipMemcpyAsync(sg + (size_t)i * plane * ch, fs, ((size_t)pitch * (size_t)(hh - 1) + (size_t)w) * ch, kind, st));
-            else HIP_TRY(h, hipMemcpy2DAsync(sg + (size_t)i * plane * ch, (size_t)pitch * ch, fs, step, (size_t)w * ch, (size_t)hh, kind, st));
-        }
+    const uint8_t *src = (const uint8_t *)image;
+    int64_t src_row = (int64_t)step, src_frame = n == 1 ? 0 : (int64_t)frame_step;
+    if (kind != hipMemcpyDeviceToDevice) {
+        uint8_t *sg = h->d_stage_gray + (size_t)slot0 * (size_t)h->hc.slot_elems * 4;
+        const dsm_copy::Plan p = slot_plan(h, n, (size_t)g.ch, step, frame_step, true);
+        if (int rc = copy_planes(h, sg, image, p, kind, st)) return rc;
+        src = sg;
+        src_row = (int64_t)p.out_step;
+        src_frame = (int64_t)p.out_frame_step;
     }
-    const hipError_t e = launch_gray_u8(di, pitch, h->hc.slot_elems, src, src_row, src_frame, w, hh, n, g.ch, g.swap, g.wr, g.wg, g.wb, g.shift, st);
+    const hipError_t e = launch_gray_u8(di, h->hc.pitch, h->hc.slot_elems, src, src_row, src_frame, h->hc.w, h->hc.h, n, g.ch, g.swap, g.wr, g.wg, g.wb, g.shift, st);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "colour to grey conversion: %s", hipGetErrorString(e));
     return DSM_OK;
 }
 
-struct HostFrames {
-    const uint8_t *image = nullptr; // grey, or packed colour pixels with gray set
-    const void *depth = nullptr; // float, or uint16 with u16 set
-    size_t img_step = 0, img_frame_step = 0, depth_step = 0, depth_frame_step = 0;
-    const DepthU16 *u16 = nullptr;
-    const ImageGray *gray = nullptr;
-};
-// frames [first, first + n) of `f0` into the frame slots slot_base + first ..., on `st` (u16 depth: converted right behind its copy)
+// Frames that come with the enqueue call (dsm_replay_enqueue_host): `n` frames in page-locked host memory, frame i at
+// image + i * img_frame_step / depth + i * depth_frame_step.  They go up ON THE STREAM THAT RUNS THEIR SUPERPIXEL STAGES, right
+// in front of them, into the frame slots of the pipelines that take them (slot = pipeline): no upload stream, no event between
+// an upload and its consumer, and a transfer holds up only the hardware queue of the work that waits for it anyway.
+// Frames [first, first + n) of `f0` into the frame slots slot_base + first ..., on `st` (u16 depth and colour: converted right behind
+// their copies); mono8 and float planes go straight into the slots, tight rows row by row.
 int upload_host_frames(dsm_handle *h, const HostFrames &f0, int slot_base, int first, int n, hipStream_t st) {
     if (n <= 0) return DSM_OK;
-    HostFrames f = f0;
-    f.image = f0.image + (size_t)first * f0.img_frame_step;
-    f.depth = (const char *)f0.depth + (size_t)first * f0.depth_frame_step;
+    const uint8_t *image = f0.image + (size_t)first * f0.img_frame_step;
+    const void *depth = (const char *)f0.depth + (size_t)first * f0.depth_frame_step;
     const int slot0 = slot_base + first;
-    const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot0 * h->hc.slot_elems;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot0 * h->hc.slot_elems;
-    const size_t plane = (size_t)pitch * (size_t)hh;
-    const bool img_flat = f.img_step == (size_t)pitch, dep_flat = f.depth_step == (size_t)pitch * 4;
-    if (f.gray) {
-        if (int rc = upload_image_gray(h, slot0, n, f.image, f.img_step, f.img_frame_step, hipMemcpyHostToDevice, *f.gray, st)) return rc;
-    } else if (img_flat && (n == 1 || f.img_frame_step == plane)) {
-        HIP_TRY(h, hipMemcpyAsync(di, f.image, plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w, hipMemcpyHostToDevice, st));
-    } else {
-        for (int i = 0; i < n; i++) {
-            const uint8_t *src = f.image + (size_t)i * f.img_frame_step;
-            if (img_flat) HIP_TRY(h, hipMemcpyAsync(di + (size_t)i * plane, src, (size_t)pitch * (size_t)(hh - 1) + (size_t)w, hipMemcpyHostToDevice, st));
-            else HIP_TRY(h, hipMemcpy2DAsync(di + (size_t)i * plane, (size_t)pitch, src, f.img_step, (size_t)w, (size_t)hh, hipMemcpyHostToDevice, st));
-        }
-    }
-    if (f.u16) {
-        if (int rc = upload_depth_u16(h, slot0, n, f.depth, f.depth_step, f.depth_frame_step, hipMemcpyHostToDevice, *f.u16, st)) return rc;
-    } else if (dep_flat && (n == 1 || f.depth_frame_step == plane * 4)) {
-        HIP_TRY(h, hipMemcpyAsync(dd, f.depth, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 4, hipMemcpyHostToDevice, st));
-    } else {
-        for (int i = 0; i < n; i++) {
-            const float *src = (const float *)((const char *)f.depth + (size_t)i * f.depth_frame_step);
-            if (dep_flat) HIP_TRY(h, hipMemcpyAsync(dd + (size_t)i * plane, src, ((size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 4, hipMemcpyHostToDevice, st));
-            else HIP_TRY(h, hipMemcpy2DAsync(dd + (size_t)i * plane, (size_t)pitch * 4, src, f.depth_step, (size_t)w * 4, (size_t)hh, hipMemcpyHostToDevice, st));
-        }
-    }
+    if (f0.gray) {
+        if (int rc = upload_image_gray(h, slot0, n, image, f0.img_step, f0.img_frame_step, hipMemcpyHostToDevice, *f0.gray, st)) return rc;
+    } else if (int rc = copy_planes(h, di, image, slot_plan(h, n, 1, f0.img_step, f0.img_frame_step, false), hipMemcpyHostToDevice, st)) return rc;
+    if (f0.u16) {
+        if (int rc = upload_depth_u16(h, slot0, n, depth, f0.depth_step, f0.depth_frame_step, hipMemcpyHostToDevice, *f0.u16, st)) return rc;
+    } else if (int rc = copy_planes(h, dd, depth, slot_plan(h, n, 4, f0.depth_step, f0.depth_frame_step, false), hipMemcpyHostToDevice, st)) return rc;
     return DSM_OK;
 }
 
@@ -1069,13 +1057,25 @@ int sync_and_fetch_counts(dsm_handle *h) {
     return check_status(h);
 }
 
+// One mono8 / float plane of a synchronous upload, `elem` bytes a pixel.  Tightly packed rows (the usual case): one 1-D copy into
+// `stage` -- device memory stays where it is -- and *tight = what launch_repack then sets to the slot's pitch.  Any other rows go
+// straight into the slot, row by row (the pad columns stay as they are); in one piece only where the slot has none (w == pitch).
+int upload_plane(dsm_handle *h, void *slot_plane, void *stage, const void *src, size_t elem, size_t step, hipMemcpyKind kind, hipStream_t up, const void **tight) {
+    dsm_copy::Plan p = slot_plan(h, 1, elem, step, 0, true);
+    if (h->hc.w < h->hc.pitch) p.two_d = !p.packed;
+    if (!p.packed) return copy_planes(h, slot_plane, src, p, kind, up);
+    if (kind == hipMemcpyDeviceToDevice) {
+        *tight = src;
+        return DSM_OK;
+    }
+    *tight = stage;
+    return copy_planes(h, stage, src, p, kind, up);
+}
+
 // u16: the depth is uint16, converted into the slot on the upload's stream (the call returns when the conversion is done)
 int upload_frame(dsm_handle *h, int slot, const void *image, size_t img_step, const void *depth, size_t depth_step,
                  hipMemcpyKind kind, const DepthU16 *u16 = nullptr, const ImageGray *gray = nullptr) {
-    if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth");
-    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
-    const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    if (img_step < (size_t)w * (gray ? (size_t)gray->ch : 1) || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
+    if (int rc = check_frames(h, kOneSlot, slot, 1, {(const uint8_t *)image, depth, img_step, 0, depth_step, 0, u16, gray})) return rc;
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
     hipStream_t up = h->up_stream;
@@ -1087,33 +1087,15 @@ int upload_frame(dsm_handle *h, int slot, const void *image, size_t img_step, co
         }
         if (h->slot_used[(size_t)slot]) HIP_TRY(h, hipStreamWaitEvent(up, h->ev_slot[(size_t)slot], 0)); // frames still reading this slot
     }
-    // tightly packed rows (the usual case): one 1-D copy each, then a repack into the pitched slot on the device
-    const bool img_tight = !gray && img_step == (size_t)w, dep_tight = !u16 && depth_step == (size_t)w * 4;
-    const size_t n = (size_t)w * (size_t)hh;
-    const uint8_t *s_img = nullptr;
-    const float *s_dep = nullptr;
+    const void *s_img = nullptr, *s_dep = nullptr;
     if (gray) {
         if (int rc = upload_image_gray(h, slot, 1, image, img_step, 0, kind, *gray, up)) return rc;
-    } else if (img_tight) {
-        if (kind == hipMemcpyDeviceToDevice) s_img = (const uint8_t *)image;
-        else {
-            HIP_TRY(h, hipMemcpyAsync(h->d_stage_img, image, n, kind, up));
-            s_img = h->d_stage_img;
-        }
-    } else
-        HIP_TRY(h, hipMemcpy2DAsync(di, (size_t)pitch, image, img_step, (size_t)w, (size_t)hh, kind, up));
+    } else if (int rc = upload_plane(h, di, h->d_stage_img, image, 1, img_step, kind, up, &s_img)) return rc;
     if (u16) {
         if (int rc = upload_depth_u16(h, slot, 1, depth, depth_step, 0, kind, *u16, up)) return rc;
-    } else if (dep_tight) {
-        if (kind == hipMemcpyDeviceToDevice) s_dep = (const float *)depth;
-        else {
-            HIP_TRY(h, hipMemcpyAsync(h->d_stage_depth, depth, n * 4, kind, up));
-            s_dep = h->d_stage_depth;
-        }
-    } else
-        HIP_TRY(h, hipMemcpy2DAsync(dd, (size_t)pitch * 4, depth, depth_step, (size_t)w * 4, (size_t)hh, kind, up));
+    } else if (int rc = upload_plane(h, dd, h->d_stage_depth, depth, 4, depth_step, kind, up, &s_dep)) return rc;
     if (s_img || s_dep) {
-        const hipError_t e = launch_repack(di, dd, pitch, s_img, s_dep, w, hh, up);
+        const hipError_t e = launch_repack(di, dd, h->hc.pitch, (const uint8_t *)s_img, (const float *)s_dep, h->hc.w, h->hc.h, up);
         if (e != hipSuccess) return fail(h, DSM_E_HIP, "frame repack: %s", hipGetErrorString(e));
     }
     HIP_TRY(h, hipStreamSynchronize(up)); // the frame is in its slot, the caller may reuse its buffers
@@ -2081,11 +2063,8 @@ int dsm_frame_upload_u16(dsm_handle *h, int slot, const uint8_t *image, size_t i
     if (!h) return DSM_E_INVALID;
     DEPTH_U16_CHECK(h, depth_scale, depth_op);
     const DepthU16 u = {depth_scale, depth_op};
-    if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth"); // (upload_frame checks these too: here, before any device call)
-    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
-    if (img_step < (size_t)h->hc.w || depth_step < (size_t)h->hc.w * 2) return fail(h, DSM_E_INVALID, "row step smaller than a row");
-    int rc = bind_device(h);
-    if (rc) return rc;
+    int rc = check_frames(h, kOneSlot, slot, 1, {image, depth, img_step, 0, depth_step, 0, &u}); // (upload_frame checks these too: here, before any device call)
+    if (rc || (rc = bind_device(h))) return rc;
     return upload_frame(h, slot, image, img_step, depth, depth_step, hipMemcpyHostToDevice, &u);
 }
 
@@ -2094,11 +2073,8 @@ int dsm_frame_upload_device_u16(dsm_handle *h, int slot, const void *image_dev, 
     if (!h) return DSM_E_INVALID;
     DEPTH_U16_CHECK(h, depth_scale, depth_op);
     const DepthU16 u = {depth_scale, depth_op};
-    if (!image_dev || !depth_dev) return fail(h, DSM_E_INVALID, "null image/depth");
-    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
-    if (img_step < (size_t)h->hc.w || depth_step < (size_t)h->hc.w * 2) return fail(h, DSM_E_INVALID, "row step smaller than a row");
-    int rc = bind_device(h);
-    if (rc) return rc;
+    int rc = check_frames(h, kOneSlot, slot, 1, {(const uint8_t *)image_dev, depth_dev, img_step, 0, depth_step, 0, &u});
+    if (rc || (rc = bind_device(h))) return rc;
     return upload_frame(h, slot, image_dev, img_step, depth_dev, depth_step, hipMemcpyDeviceToDevice, &u);
 }
 
@@ -2121,12 +2097,8 @@ static int frame_upload_fmt(dsm_handle *h, int slot, const void *image, size_t i
                             const dsm_frame_format *fmt, hipMemcpyKind kind) {
     if (!h) return DSM_E_INVALID;
     FRAME_FMT_PARSE(h, fmt, ff);
-    if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth"); // (upload_frame checks these too: here, before any device call)
-    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
-    if (img_step < (size_t)h->hc.w * (size_t)ff.p.gray.ch || depth_step < (size_t)h->hc.w * (size_t)ff.p.depth_elem)
-        return fail(h, DSM_E_INVALID, "row step smaller than a row");
-    int rc = bind_device(h);
-    if (rc) return rc;
+    int rc = check_frames(h, kOneSlot, slot, 1, {(const uint8_t *)image, depth, img_step, 0, depth_step, 0, ff.u16(), ff.gray()}); // (upload_frame checks these too: here, before any device call)
+    if (rc || (rc = bind_device(h))) return rc;
     return upload_frame(h, slot, image, img_step, depth, depth_step, kind, ff.u16(), ff.gray());
 }
 
@@ -2154,11 +2126,8 @@ int dsm_frame_upload_async(dsm_handle *h, int slot, const uint8_t *image, size_t
 static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
                                const void *depth, size_t depth_step, size_t depth_frame_step, const DepthU16 *u16, const ImageGray *gray = nullptr) {
     if (!h) return DSM_E_INVALID;
-    if (!image || !depth) return fail(h, DSM_E_INVALID, "null image/depth");
-    if (n < 1 || slot0 < 0 || slot0 + n > h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slots [%d,%d) out of range [0,%d)", slot0, slot0 + n, h->hc.n_slots);
-    const int w = h->hc.w, hh = h->hc.h, pitch = h->hc.pitch;
-    if (img_step < (size_t)w * (gray ? (size_t)gray->ch : 1) || depth_step < (size_t)w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
-    if (n > 1 && (img_frame_step < img_step * (size_t)hh || depth_frame_step < depth_step * (size_t)hh)) return fail(h, DSM_E_INVALID, "frame step smaller than a frame");
+    int rc = check_frames(h, kSlotRange, slot0, n, {image, depth, img_step, img_frame_step, depth_step, depth_frame_step, u16, gray});
+    if (rc) return rc;
     // A handle that advances with a batch and whose own stream has carried nothing since the batch last ordered itself
     // behind it (`touched` false: only batch calls since): whatever may still read these slots is covered by the batch's
     // latest marker -- the upload stream waits for THAT, directly.  The handle's own stream is not involved: no wait and no
@@ -2166,7 +2135,7 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
     // that other batches' graphs share: with 128 streamed subsequences, 256 of them per chunk).
     const bool via_batch = h->batch_order_ev != nullptr && !h->touched;
     if (via_batch) HIP_TRY(h, hipSetDevice(h->device));
-    else if (int rc = bind_device(h)) return rc;
+    else if ((rc = bind_device(h))) return rc;
     hipStream_t up = device_upload_stream(h->device, &h->up_which, h->batches_joined > 0); // (decided at the handle's first upload)
     if (!up) return fail(h, DSM_E_HIP, "no upload stream on device %d", h->device);
     // behind the frames that may still read these slots (dsm_handle::rd_ring): the newest dsm_replay_enqueue call that
@@ -2194,7 +2163,6 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
     }
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot0 * h->hc.slot_elems;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot0 * h->hc.slot_elems;
-    const size_t plane = (size_t)pitch * (size_t)hh; // elements of one slot
     // Rows laid out with the slot's own pitch go up as ONE transfer per plane -- and n frames laid out back to back like
     // the slots themselves as one transfer per plane for all of them (a transfer costs ~10 us before its first byte:
     // two per frame hold a 2.4 MB frame to a third of the link's rate).  Any other row step goes row by row (a 2-D copy
@@ -2205,10 +2173,10 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
     // rows at the slots' pitch: the kernel sits between two transfers of its stream, and 128 streamed subsequences reach 19.4-21.2 k
     // frames/s like this against 21.7 k with pitched rows, VERDICT r05's tight-row upload measured.  dsm_host_pack_frames lays
     // frames out at the pitch.)
-    const bool img_flat = img_step == (size_t)pitch, dep_flat = depth_step == (size_t)pitch * 4;
-    const size_t tight = (size_t)w * (size_t)hh;
-    const bool img_tight = !gray && !img_flat && img_step == (size_t)w && (n == 1 || img_frame_step == tight);
-    const bool dep_tight = !u16 && !dep_flat && depth_step == (size_t)w * 4 && (n == 1 || depth_frame_step == tight * 4);
+    const dsm_copy::Plan pi = gray ? dsm_copy::Plan{} : slot_plan(h, n, 1, img_step, img_frame_step, true); // (mono8 and float planes only:
+    const dsm_copy::Plan pd = u16 ? dsm_copy::Plan{} : slot_plan(h, n, 4, depth_step, depth_frame_step, true); // colour and u16 plan for themselves)
+    const bool img_tight = pi.packed, dep_tight = pd.packed;
+    const size_t tight = (size_t)h->hc.w * (size_t)h->hc.h;
     if ((img_tight || dep_tight) && n > h->stage_frames_cap) {
         HIP_TRY(h, hipStreamSynchronize(up)); // (an earlier call's repack may still read the old buffers)
         if (h->d_stage_frames_img) HIP_TRY(h, hipFree(h->d_stage_frames_img));
@@ -2218,37 +2186,19 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
         HIP_TRY(h, hipMalloc((void **)&h->d_stage_frames_depth, tight * (size_t)n * 4));
         h->stage_frames_cap = n;
     }
-    if (img_tight) HIP_TRY(h, hipMemcpyAsync(h->d_stage_frames_img, image, tight * (size_t)n, hipMemcpyHostToDevice, up));
-    if (dep_tight) HIP_TRY(h, hipMemcpyAsync(h->d_stage_frames_depth, depth, tight * (size_t)n * 4, hipMemcpyHostToDevice, up));
+    if (img_tight && (rc = copy_planes(h, h->d_stage_frames_img, image, pi, hipMemcpyHostToDevice, up))) return rc;
+    if (dep_tight && (rc = copy_planes(h, h->d_stage_frames_depth, depth, pd, hipMemcpyHostToDevice, up))) return rc;
     if (img_tight || dep_tight) {
-        const hipError_t e = launch_repack_frames(di, dd, pitch, (int64_t)plane, img_tight ? h->d_stage_frames_img : nullptr,
-                                                  dep_tight ? h->d_stage_frames_depth : nullptr, w, hh, n, up);
+        const hipError_t e = launch_repack_frames(di, dd, h->hc.pitch, h->hc.slot_elems, img_tight ? h->d_stage_frames_img : nullptr,
+                                                  dep_tight ? h->d_stage_frames_depth : nullptr, h->hc.w, h->hc.h, n, up);
         if (e != hipSuccess) return fail(h, DSM_E_HIP, "frame repack: %s", hipGetErrorString(e));
     }
-    if (gray) {
-        if (int rc = upload_image_gray(h, slot0, n, image, img_step, img_frame_step, hipMemcpyHostToDevice, *gray, up)) return rc;
-    } else if (img_tight) { // (already on its way)
-    } else if (img_flat && (n == 1 || img_frame_step == plane)) {
-        HIP_TRY(h, hipMemcpyAsync(di, image, plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w, hipMemcpyHostToDevice, up));
-    } else {
-        for (int i = 0; i < n; i++) {
-            const uint8_t *src = image + (size_t)i * img_frame_step;
-            if (img_flat) HIP_TRY(h, hipMemcpyAsync(di + (size_t)i * plane, src, (size_t)pitch * (size_t)(hh - 1) + (size_t)w, hipMemcpyHostToDevice, up));
-            else HIP_TRY(h, hipMemcpy2DAsync(di + (size_t)i * plane, (size_t)pitch, src, img_step, (size_t)w, (size_t)hh, hipMemcpyHostToDevice, up));
-        }
-    }
-    if (u16) {
-        if (int rc = upload_depth_u16(h, slot0, n, depth, depth_step, depth_frame_step, hipMemcpyHostToDevice, *u16, up)) return rc;
-    } else if (dep_tight) { // (already on its way)
-    } else if (dep_flat && (n == 1 || depth_frame_step == plane * 4)) {
-        HIP_TRY(h, hipMemcpyAsync(dd, depth, (plane * (size_t)(n - 1) + (size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 4, hipMemcpyHostToDevice, up));
-    } else {
-        for (int i = 0; i < n; i++) {
-            const float *src = (const float *)((const char *)depth + (size_t)i * depth_frame_step);
-            if (dep_flat) HIP_TRY(h, hipMemcpyAsync(dd + (size_t)i * plane, src, ((size_t)pitch * (size_t)(hh - 1) + (size_t)w) * 4, hipMemcpyHostToDevice, up));
-            else HIP_TRY(h, hipMemcpy2DAsync(dd + (size_t)i * plane, (size_t)pitch * 4, src, depth_step, (size_t)w * 4, (size_t)hh, hipMemcpyHostToDevice, up));
-        }
-    }
+    if (gray) rc = upload_image_gray(h, slot0, n, image, img_step, img_frame_step, hipMemcpyHostToDevice, *gray, up);
+    else if (!img_tight) rc = copy_planes(h, di, image, pi, hipMemcpyHostToDevice, up); // (else already on its way)
+    if (rc) return rc;
+    if (u16) rc = upload_depth_u16(h, slot0, n, depth, depth_step, depth_frame_step, hipMemcpyHostToDevice, *u16, up);
+    else if (!dep_tight) rc = copy_planes(h, dd, depth, pd, hipMemcpyHostToDevice, up);
+    if (rc) return rc;
     // a ring entry for this upload; when the ring is full the oldest entry is folded into the one after it (whose event
     // is later on the same stream: waiting for it instead is safe) and its event is reused
     hipEvent_t ev = nullptr;
@@ -2346,18 +2296,13 @@ static int replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, s
     if (n < 0 || (n > 0 && (!image || !depth || !ref_idx || !poses16))) return fail(h, DSM_E_INVALID, "null/negative argument");
     if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
     if (h->hc.n_slots < h->n_pipe) return fail(h, DSM_E_INVALID, "dsm_replay_enqueue_host keeps a frame in the slot of its pipeline: %d frame slots for pipeline_depth %d", h->hc.n_slots, h->n_pipe);
-    if (img_step < (size_t)h->hc.w * (gray ? (size_t)gray->ch : 1) || depth_step < (size_t)h->hc.w * (u16 ? 2 : 4)) return fail(h, DSM_E_INVALID, "row step smaller than a row");
-    if (n > 1 && (img_frame_step < img_step * (size_t)h->hc.h || depth_frame_step < depth_step * (size_t)h->hc.h)) return fail(h, DSM_E_INVALID, "frame step smaller than a frame");
-    int rc = bind_device(h);
-    if (rc) return rc;
+    HostFrames hf = {image, depth, img_step, img_frame_step, depth_step, depth_frame_step, u16, gray};
+    int rc = check_frames(h, kNoSlots, 0, n, hf);
+    if (rc || (rc = bind_device(h))) return rc;
     // the frames read -- and overwrite -- the slots of the pipelines they run on: uploads of the asynchronous kind that
     // follow wait for the whole stream
     std::vector<int32_t> slots((size_t)(n > 0 ? n : 0));
     for (int i = 0; i < n; i++) slots[(size_t)i] = (int32_t)((h->frames_submitted + i) % h->n_pipe);
-    HostFrames hf;
-    hf.img_step = img_step; hf.img_frame_step = img_frame_step; hf.depth_step = depth_step; hf.depth_frame_step = depth_frame_step;
-    hf.u16 = u16;
-    hf.gray = gray;
     for (int i = 0; i < n;) {
         int m = 0;
         if ((rc = stage_params_batch(h, n - i, slots.data() + i, ref_idx + i, poses16 + 16 * (size_t)i,
