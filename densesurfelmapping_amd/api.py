@@ -68,6 +68,8 @@ ABI_SYMBOLS = (
     "dsm_frames_upload_async_fmt", "dsm_replay_enqueue_host_fmt", "dsm_host_pack_frames_fmt", "dsm_debug_frame_planes",
     # the hexagon mesh as vertex and index buffers
     "dsm_mesh_compose", "dsm_mesh_indices",
+    # the map as depth / index / normal / intensity images from any pose
+    "dsm_render_compose",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -147,6 +149,10 @@ CLOUD_TILE = 1024  # records per workgroup of the map compaction (dsm_device.h k
 # dsm_mesh_compose's vertex layouts (include/dsm.h dsm_mesh_vertex_layout) and their bytes per surfel (six vertices)
 MESH_VERTEX_REF6, MESH_VERTEX_XYZ_RGBA8 = 0, 1
 MESH_SURFEL_BYTES = {MESH_VERTEX_REF6: 144, MESH_VERTEX_XYZ_RGBA8: 96}
+# dsm_render_compose (include/dsm.h): its flag, its planes in the order of dsm_render_planes, and their element types / trailing shape
+RENDER_CULL_BACKFACES = 1
+RENDER_PLANES = ("depth", "index", "normal", "intensity")
+RENDER_PLANE_TYPES = {"depth": (np.float32, ()), "index": (np.int32, ()), "normal": (np.float32, (3,)), "intensity": (np.uint8, ())}
 
 
 class DsmError(RuntimeError):
@@ -163,6 +169,49 @@ class _Config(C.Structure):
                 ("disparity_error", C.c_double), ("min_tolerate_diff", C.c_double),
                 ("device", C.c_int32), ("surfel_capacity", C.c_int32), ("frame_slots", C.c_int32),
                 ("flags", C.c_uint32), ("pipeline_depth", C.c_int32)]
+
+
+class _RenderCamera(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near_dist", C.c_float), ("far_dist", C.c_float)]
+
+
+class _RenderPlanes(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("index", C.c_void_p), ("normal", C.c_void_p), ("intensity", C.c_void_p)]
+
+
+def render_camera(cam) -> _RenderCamera:
+    """a dsm_render_camera from one (passed through), from (width, height, fx, fy, cx, cy, near_dist, far_dist), or from an object
+    with those attributes (near / far also do: synth's cameras)"""
+    if isinstance(cam, _RenderCamera):
+        return cam
+    if isinstance(cam, C.Structure):  # the same fields declared elsewhere
+        return _RenderCamera(*(getattr(cam, f[0]) for f in _RenderCamera._fields_))
+    if isinstance(cam, (tuple, list)):
+        return _RenderCamera(*cam)
+    near = cam.near_dist if hasattr(cam, "near_dist") else cam.near
+    far = cam.far_dist if hasattr(cam, "far_dist") else cam.far
+    return _RenderCamera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy, near, far)
+
+
+def render_outputs(cam, planes, dst_ptrs):
+    """(the dsm_render_planes struct, the numpy arrays behind it or None for device pointers)"""
+    unknown = set(planes) - set(RENDER_PLANES) if dst_ptrs is None else set(dst_ptrs) - set(RENDER_PLANES)
+    if unknown:
+        raise ValueError("no such render plane: %s" % sorted(unknown))
+    st = _RenderPlanes()
+    if dst_ptrs is not None:
+        for k, p in dst_ptrs.items():
+            setattr(st, k, p)
+        return st, None
+    out = {}
+    for k in RENDER_PLANES:
+        if k in planes:
+            dt, tail = RENDER_PLANE_TYPES[k]
+            # (a size the library will refuse still gets an array to point at: the refusal is the library's to make)
+            out[k] = np.zeros((min(max(cam.height, 0), 8192), min(max(cam.width, 0), 8192)) + tail, dt)
+            setattr(st, k, out[k].ctypes.data)
+    return st, out
 
 
 class _StageTimes(C.Structure):
@@ -225,6 +274,8 @@ def load_library():
     lib.dsm_frame_cloud.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int32, _vp]
     lib.dsm_mesh_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int32, _vp]
     lib.dsm_mesh_indices.argtypes = [_vp, C.c_int32, _vp, C.c_int]
+    lib.dsm_render_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_RenderCamera), _vp, _vp, C.c_uint32, C.POINTER(_RenderPlanes),
+                                       C.c_int, _vp]
     lib.dsm_frame_upload.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_upload_device.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_pitch.argtypes = [_vp, _vp]
@@ -529,6 +580,30 @@ class FusionFunctions:
         out = np.zeros((max(cap, 1), MESH_SURFEL_BYTES[layout] // 4), np.float32)
         self._check(self._lib.dsm_mesh_compose(self._h, select, len(seg), _ptr(b), _ptr(c), layout, _ptr(out), 0, cap, C.byref(n)))
         return out[: n.value].copy()
+
+    # ---- the map as an image ------------------------------------------------------------------------
+    def render(self, select, segs, camera, pose, pose_inv=None, flags=0, planes=RENDER_PLANES, dst_ptrs=None):
+        """dsm_render_compose: what `camera` (render_camera's forms) at `pose` (4x4 cam -> world, or 16 column-major floats) sees
+        of the surfel sequence of mesh_compose(select, segs): the nearest disc along every pixel's ray.  Returns a dict of
+        [height, width] numpy arrays for the `planes` asked for -- "depth" float32 (0 = nothing hit), "index" int32 (-1),
+        "normal" float32 [.., 3] (camera frame), "intensity" uint8 -- plus "n_surfels", the length of the sequence.  With
+        dst_ptrs = {plane: device pointer} (e.g. torch data_ptr()) the planes named there are written on the device and
+        n_surfels is returned.  pose_inv: the caller's own world -> cam matrix, as for the *_inv calls; flags: RENDER_CULL_BACKFACES."""
+        seg = np.ascontiguousarray(np.asarray(segs, np.int32).reshape(-1, 2))
+        b = np.ascontiguousarray(seg[:, 0]) if len(seg) else np.zeros(1, np.int32)
+        c = np.ascontiguousarray(seg[:, 1]) if len(seg) else np.zeros(1, np.int32)
+        cam = render_camera(camera)
+        p = np.asarray(pose, np.float32)
+        p = pose_to_colmajor(p) if p.shape == (4, 4) else np.ascontiguousarray(p.reshape(16))
+        _keep, inv_p = _inv_ptr(pose_inv)
+        st, out = render_outputs(cam, planes, dst_ptrs)
+        n = C.c_int32(0)
+        self._check(self._lib.dsm_render_compose(self._h, select, len(seg), _ptr(b), _ptr(c), C.byref(cam), _ptr(p), inv_p, flags, C.byref(st),
+                                                 0 if dst_ptrs is None else 1, C.byref(n)))
+        if dst_ptrs is not None:
+            return n.value
+        out["n_surfels"] = n.value
+        return out
 
     def mesh_indices(self, n_surfels, dst_ptr=None):
         """dsm_mesh_indices: the (n_surfels * 4, 3) uint32 triangles of n_surfels hexagons -- or, with dst_ptr, into device memory."""

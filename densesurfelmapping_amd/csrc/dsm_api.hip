@@ -262,6 +262,12 @@ struct dsm_handle {
     float4 *d_pub_out = nullptr;
     size_t pub_out_cap = 0;
     hipEvent_t ev_pub_dst = nullptr; // a device destination is written behind the null stream's work so far (as hipMemcpy would)
+    // dsm_render_compose: grow-only device scratch, none before the first render -- the key plane with the ray tables behind
+    // it (render_px pixels), the splat records and the number -> record table (render_seq surfels)
+    unsigned long long *d_render_keys = nullptr;
+    size_t render_px = 0;
+    void *d_render_splats = nullptr;
+    size_t render_seq = 0;
     // drop-in calls (dsm_fuse_map / dsm_fuse_initialize_map): page-locked staging owned by the handle
     uint8_t *pin_frame = nullptr; // one frame, image then depth, rows at the frame slots' pitch
     dsm_surfel *pin_map = nullptr; // shadow of the caller's array: what the last drop-in call returned == the device map
@@ -1385,6 +1391,8 @@ void dsm_destroy(dsm_handle *h) {
     if (h->d_pub) (void)hipFree(h->d_pub);
     if (h->d_pub_out) (void)hipFree(h->d_pub_out);
     if (h->ev_pub_dst) (void)hipEventDestroy(h->ev_pub_dst);
+    if (h->d_render_keys) (void)hipFree(h->d_render_keys);
+    if (h->d_render_splats) (void)hipFree(h->d_render_splats);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->h_scalars) (void)hipHostFree(h->h_scalars);
     if (h->pin_frame) (void)hipHostFree(h->pin_frame);
@@ -1984,6 +1992,126 @@ int dsm_mesh_indices(dsm_handle *h, int32_t n_surfels, void *dst, int dst_on_dev
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "mesh index launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (!dst_on_device) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)n_surfels * 48, hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ the map as an image (dsm_k_render.h)
+
+namespace {
+
+int render_reserve(dsm_handle *h, size_t px, size_t side_sum, size_t seq) {
+    const size_t want_px = px + (side_sum + 1) / 2 + 8; // the ray tables (floats) behind the keys, in units of a key
+    if (want_px > h->render_px) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_render_keys) (void)hipFree(h->d_render_keys);
+        h->d_render_keys = nullptr;
+        h->render_px = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->d_render_keys, want_px * sizeof(unsigned long long)));
+        h->render_px = want_px;
+    }
+    if (seq > h->render_seq) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_render_splats) (void)hipFree(h->d_render_splats);
+        h->d_render_splats = nullptr;
+        h->render_seq = 0;
+        const size_t want = seq + seq / 4 + 64;
+        HIP_TRY(h, hipMalloc(&h->d_render_splats, want * (sizeof(RenderSplat) + sizeof(int32_t))));
+        h->render_seq = want;
+    }
+    return DSM_OK;
+}
+
+} // namespace
+
+// the sequence is dsm_mesh_compose's: the store's record runs first, then the map part
+int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                       const dsm_render_camera *camera, const float *pose16, const float *pose_inv16, uint32_t flags, const dsm_render_planes *planes,
+                       int dst_on_device, int32_t *n_surfels) {
+    if (!h || !n_surfels) return DSM_E_INVALID;
+    if (!camera || !pose16 || !planes) return fail(h, DSM_E_INVALID, "null camera, pose or planes");
+    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
+    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
+    if (flags & ~(uint32_t)DSM_RENDER_CULL_BACKFACES) return fail(h, DSM_E_INVALID, "render flags 0x%x", flags);
+    const dsm_render_camera &c = *camera;
+    if (c.width < 1 || c.width > kRenderMaxSide || c.height < 1 || c.height > kRenderMaxSide)
+        return fail(h, DSM_E_INVALID, "render image %d x %d outside 1..%d", c.width, c.height, kRenderMaxSide);
+    if (!(c.fx > 0.0f && c.fy > 0.0f) || !std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy))
+        return fail(h, DSM_E_INVALID, "render camera fx %g fy %g cx %g cy %g", (double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy);
+    if (!(c.near_dist > 0.0f) || !(c.near_dist < c.far_dist) || !std::isfinite(c.far_dist))
+        return fail(h, DSM_E_INVALID, "render depth range (%g, %g)", (double)c.near_dist, (double)c.far_dist);
+    if (!planes->depth && !planes->index && !planes->normal && !planes->intensity) return fail(h, DSM_E_INVALID, "no output plane");
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(pose16[k]) || (pose_inv16 && !std::isfinite(pose_inv16[k]))) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
+    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
+    // the runs, checked before anything reaches the device; empty ones are dropped
+    std::vector<int32_t> seg;
+    int64_t runs_total = 0;
+    for (int32_t s = 0; s < n_segments; s++) {
+        const int32_t b = store_begin[s], cnt = store_count[s];
+        if (b < 0 || cnt < 0 || (int64_t)b + cnt > h->store_n)
+            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, cnt, h->store_n);
+        if (!cnt) continue;
+        seg.push_back(b);
+        seg.push_back(cnt);
+        seg.push_back((int32_t)runs_total);
+        runs_total += cnt;
+    }
+    const int n_upper = select == kCloudNone ? 0 : h->map_upper;
+    const int64_t bound = (int64_t)n_upper + runs_total;
+    if (bound > INT32_MAX - 4096) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)bound);
+    int rc = bind_device(h);
+    if (rc) return rc;
+    const int w = c.width, hh = c.height;
+    const size_t px = (size_t)w * hh, tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    // a host destination's planes are staged behind one another, each from a 16-byte boundary
+    const size_t q_depth = (px + 3) / 4, q_normal = (3 * px + 3) / 4, q_int = (px + 15) / 16;
+    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), dst_on_device ? 0 : 2 * q_depth + q_normal + q_int))) return rc;
+    if ((rc = render_reserve(h, px, (size_t)w + hh, (size_t)bound))) return rc;
+    if (dst_on_device && (rc = pub_order_dst(h))) return rc;
+    float pose_inv[16];
+    if (pose_inv16) memcpy(pose_inv, pose_inv16, sizeof pose_inv);
+    else inverse4<float>(pose16, pose_inv);
+    RenderCam cam;
+    cam.w = w; cam.h = hh;
+    cam.fx = c.fx; cam.fy = c.fy; cam.cx = c.cx; cam.cy = c.cy;
+    cam.near_d = c.near_dist; cam.far_d = c.far_dist;
+    std::vector<float> rays((size_t)w + hh);
+    for (int x = 0; x < w; x++) rays[(size_t)x] = ray_coeff(x, c.cx, c.fx);
+    for (int y = 0; y < hh; y++) rays[(size_t)w + y] = ray_coeff(y, c.cy, c.fy);
+    float *d_rays = (float *)(h->d_render_keys + px);
+    int32_t *d_total = h->d_pub, *d_counts = h->d_pub + 16, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
+    HIP_TRY(h, hipMemcpyAsync(d_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    RenderScratch sc;
+    sc.keys = h->d_render_keys;
+    sc.splats = (RenderSplat *)h->d_render_splats;
+    sc.slot_of = (int32_t *)((RenderSplat *)h->d_render_splats + h->render_seq);
+    sc.counts = d_counts;
+    sc.n_seq = (int32_t)bound;
+    float *o_depth = (float *)planes->depth;
+    int32_t *o_index = (int32_t *)planes->index;
+    float *o_normal = (float *)planes->normal;
+    uint8_t *o_int = (uint8_t *)planes->intensity;
+    if (!dst_on_device) {
+        float4 *st = h->d_pub_out;
+        if (o_depth) o_depth = (float *)st;
+        if (o_index) o_index = (int32_t *)(st + q_depth);
+        if (o_normal) o_normal = (float *)(st + 2 * q_depth);
+        if (o_int) o_int = (uint8_t *)(st + 2 * q_depth + q_normal);
+    }
+    const hipError_t e = launch_render(h->d_store, d_seg, (int)(seg.size() / 3), (int)runs_total, h->hc.local, h->hc.n_local, n_upper, select, d_tiles,
+                                       d_total, cam, pose_inv, flags, eigen33_products(h), sc, d_rays, d_rays + w, o_depth, o_index, o_normal, o_int,
+                                       h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "render launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + runs_total);
+    if (!dst_on_device) {
+        if (planes->depth) HIP_TRY(h, hipMemcpy(planes->depth, o_depth, px * sizeof(float), hipMemcpyDeviceToHost));
+        if (planes->index) HIP_TRY(h, hipMemcpy(planes->index, o_index, px * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (planes->normal) HIP_TRY(h, hipMemcpy(planes->normal, o_normal, 3 * px * sizeof(float), hipMemcpyDeviceToHost));
+        if (planes->intensity) HIP_TRY(h, hipMemcpy(planes->intensity, o_int, px, hipMemcpyDeviceToHost));
+    }
     return DSM_OK;
 }
 

@@ -219,4 +219,21 @@ hipError_t launch_mesh_gather(const dsm_surfel *src, const int32_t *seg, int n_s
 // 12 indices per surfel: 6 i + {0,1,2, 1,3,2, 2,3,4, 4,3,5}
 hipError_t launch_mesh_indices(uint32_t *out, int n, hipStream_t st);
 
+// ---- the map as an image (dsm_k_render.h; the definition is render_setup / render_hit / render_key of dsm_math.h)
+constexpr int kRenderSmallW = 16, kRenderSmallArea = 256; // boxes up to this wide AND this large: 16 lanes per splat; others: a workgroup
+struct RenderScratch {
+    unsigned long long *keys; // [h][w]
+    RenderSplat *splats;      // [n_seq]: small boxes from the front, large ones from the back
+    int32_t *slot_of;         // [n_seq]: surfel number -> its splat record
+    int32_t *counts;          // [2]: splats in the small list, in the large one
+    int32_t n_seq;            // an upper bound of the sequence's length (the runs + the map's running bound)
+};
+// The surfel sequence = the runs of `store` (seg: launch_cloud_gather's table, runs_total records), then the records [0,
+// min(*n_ptr, n_upper)) of `rec` that pass `select`; total[0] = how many of those passed.  inv16: world -> cam.  ray_x [w] /
+// ray_y [h]: ray_coeff of every column / row, in device memory.  Any plane may be null.  tile_cnt as for launch_cloud_map.
+hipError_t launch_render(const dsm_surfel *store, const int32_t *seg, int n_seg, int runs_total, const dsm_surfel *rec, const int32_t *n_ptr, int n_upper,
+                         int select, int32_t *tile_cnt, int32_t *total, const RenderCam &cam, const float *inv16, uint32_t flags, bool eigen33,
+                         const RenderScratch &sc, const float *ray_x, const float *ray_y, float *depth, int32_t *index, float *normal,
+                         uint8_t *intensity, hipStream_t st);
+
 } // namespace dsm

@@ -813,6 +813,90 @@ template <typename S> DSM_HD void surfel_hexagon(const S &s, float pt[6][3], int
     }
 }
 
+// ---------------------------------------------------------------- the map as an image (dsm_k_render.h, tests/render_host.cpp)
+// A surfel is a disc of radius `size` about its position in the plane of its normal; the ray of pixel (u, v) is
+// (ray_coeff(u, cx, fx), ray_coeff(v, cy, fy), 1).  render_setup is the per-surfel part (camera-frame centre and normal, the
+// early rejects, the pixel box), render_hit the per-pixel test, render_key the total order the nearest hit is the minimum of.
+// The kernels and the host checker call these three and nothing else; every parenthesis is part of the definition.
+struct RenderCam {
+    int w, h;
+    float fx, fy, cx, cy, near_d, far_d;
+};
+struct RenderSplat {       // 48 bytes
+    float pc[3], nc[3];    // centre and normal in the camera frame
+    float r2, d;           // size * size; nc . pc
+    uint16_t x0, y0, x1, y1; // the pixel box [x0, x1) x [y0, y1), clipped to the image (<= 8192 per side)
+    int32_t number;        // position in the render's surfel sequence
+    uint32_t intensity;    // surfel_color_byte(surfel_color_int(color))
+};
+constexpr int kRenderMaxSide = 8192;
+constexpr uint32_t kRenderCullBackfaces = 1u; // DSM_RENDER_CULL_BACKFACES
+
+// floor(v) clamped to [0, n] for a box side; NaN -> nan_value.  No value outside [0, n] reaches the cast (n <= 8192).
+DSM_HD int render_clamp_px(float v, int n, int nan_value) {
+    if (v != v) return nan_value;
+    if (v <= 0.0f) return 0;
+    if (v >= (float)n) return n;
+    return (int)v;
+}
+
+// One axis of the box: the pixels whose ray coefficient can lie in [lo / z, hi / z] for some z in [zlo, zhi] (0 < zlo <= zhi),
+// as [b0, b1) clipped to [0, n).  Outward by one pixel plus 1e-5 of the magnitudes involved: far more than the roundings of
+// ray_coeff and of the products below; a side that is not a number opens to the image's.
+DSM_HD void render_box_axis(float lo, float hi, float zlo, float zhi, float f, float c, int n, int &b0, int &b1) {
+    const float rlo = lo >= 0.0f ? lo / zhi : lo / zlo;
+    const float rhi = hi >= 0.0f ? hi / zlo : hi / zhi;
+    const float ulo = rlo * f + c, uhi = rhi * f + c;
+    const float mlo = 1.0f + 1e-5f * (fabsf(c) + fabsf(ulo)), mhi = 1.0f + 1e-5f * (fabsf(c) + fabsf(uhi));
+    b0 = render_clamp_px(ulo - mlo, n, 0);
+    b1 = render_clamp_px((uhi + mhi) + 1.0f, n, n);
+}
+
+// S = dsm_surfel (or Surfel).  inv = world -> cam, column-major.  False: the surfel hits no pixel of this camera.
+// The rejects, each implied by render_hit: r2 a NaN (no distance is <= it); d = nc . pc not finite (z = d / den is then never
+// finite; any NaN or infinity in pc or nc makes d one, so below pc and nc are finite) or zero (z is 0 or a NaN, and near_d > 0);
+// with kRenderCullBackfaces d >= 0; a depth range or a box that is empty.  The box: a hit point (z rx, z ry, z) lies within
+// sqrt(r2) of pc in every coordinate -- up to the roundings of the test, which rp and the 4e-7 |pc| terms exceed (1e-18: squares
+// that underflow) -- so z is in [zlo, zhi] and the ray coefficients in the intervals render_box_axis inverts.
+template <bool E33, typename S> DSM_HD bool render_setup(const RenderCam &cam, const float *inv, uint32_t flags, const S &s, int number, RenderSplat &o) {
+    const float pw[3] = {s.px, s.py, s.pz}, nw[3] = {s.nx, s.ny, s.nz};
+    xform_point(inv, pw, o.pc);
+    xform_dir_as<E33>(inv, nw, o.nc);
+    o.r2 = s.size * s.size;
+    o.d = (o.nc[0] * o.pc[0] + o.nc[1] * o.pc[1]) + o.nc[2] * o.pc[2];
+    o.number = number;
+    o.intensity = surfel_color_byte(surfel_color_int(s.color));
+    o.x0 = o.y0 = o.x1 = o.y1 = 0;
+    if (!(o.r2 >= 0.0f)) return false;
+    if (!(fabsf(o.d) < __builtin_inff()) || o.d == 0.0f) return false;
+    if ((flags & kRenderCullBackfaces) && o.d >= 0.0f) return false;
+    const float rp = sqrtf(o.r2) * 1.00001f + 1e-18f;
+    const float sx = rp + 4e-7f * fabsf(o.pc[0]), sy = rp + 4e-7f * fabsf(o.pc[1]), sz = rp + 4e-7f * fabsf(o.pc[2]);
+    const float zlo = fmaxf(o.pc[2] - sz, cam.near_d), zhi = fminf(o.pc[2] + sz, cam.far_d);
+    if (!(zlo <= zhi)) return false;
+    int x0, x1, y0, y1;
+    render_box_axis(o.pc[0] - sx, o.pc[0] + sx, zlo, zhi, cam.fx, cam.cx, cam.w, x0, x1);
+    render_box_axis(o.pc[1] - sy, o.pc[1] + sy, zlo, zhi, cam.fy, cam.cy, cam.h, y0, y1);
+    if (x0 >= x1 || y0 >= y1) return false;
+    o.x0 = (uint16_t)x0; o.x1 = (uint16_t)x1; o.y0 = (uint16_t)y0; o.y1 = (uint16_t)y1;
+    return true;
+}
+
+// the test of one pixel, (rx, ry) its ray coefficients: z = (nc . pc) / (nc . ray); a hit iff near_d < z < far_d (a NaN or an
+// infinite z fails both) and the hit point z * ray is within the disc
+DSM_HD bool render_hit(const RenderSplat &s, float rx, float ry, float near_d, float far_d, float &z) {
+    const float den = (s.nc[0] * rx + s.nc[1] * ry) + s.nc[2];
+    z = s.d / den;
+    if (!(z > near_d && z < far_d)) return false;
+    const float hx = z * rx - s.pc[0], hy = z * ry - s.pc[1], hz = z - s.pc[2];
+    const float dist2 = (hx * hx + hy * hy) + hz * hz;
+    return dist2 <= s.r2;
+}
+
+// z > 0, so its bits order as unsigned integers: the minimum key is the nearest hit, the lower number on a tie
+constexpr uint64_t kRenderEmpty = ~0ull;
+DSM_HD uint64_t render_key(float z, int number) { return ((uint64_t)__builtin_bit_cast(uint32_t, z) << 32) | (uint32_t)number; }
+
 // worker k's [begin,end) over n items, FF.cpp:198-202 / 392-396 / 471-475
 DSM_HD int chunk_of(int n, int i) {
     int step = n / kWorkers;

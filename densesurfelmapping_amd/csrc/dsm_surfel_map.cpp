@@ -355,6 +355,7 @@ int synchronize_msgs(dsm_surfel_map *m) {
     m->last.relative_index = relative_index;
     m->last.fuse_pose = matrix_to_pose(fuse_pose); // fuse_pose_ros (:151-152)
     m->last.slot = slot;
+    for (int k = 0; k < 16; k++) m->last.pose16[k] = pose16[k];
     m->pose_reference_buffer.pop_front(); // :163
     m->frames_fused++;
     // :189-197 publish results (dsm_surfel_map_set_publish; nothing to do unless it installed a publisher)

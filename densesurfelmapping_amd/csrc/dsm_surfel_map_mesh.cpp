@@ -24,17 +24,6 @@ int mesh_fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
 
 int mesh_engine_fail(dsm_surfel_map *m, int rc, const char *what) { return mesh_fail(m, rc, "%s: %s", what, dsm_last_error(m->engine)); }
 
-// :1226-1238: the attached surfels keyframe by keyframe, in poses_database order (not store order)
-void attached_runs(const dsm_surfel_map *m, std::vector<int32_t> &begin, std::vector<int32_t> &count) {
-    for (const dsm_surfel_map::PoseElement &pe : m->poses_database) {
-        if (pe.segment < 0) continue;
-        const dsm_surfel_map::Segment &sg = m->segments[(size_t)pe.segment];
-        if (sg.count <= 0) continue;
-        begin.push_back(sg.begin);
-        count.push_back(sg.count);
-    }
-}
-
 // the attached surfels, then the active ones with update_times >= 5 (:1240-1248)
 int build_mesh(dsm_surfel_map *m, int layout, void *dst, int on_device, int32_t cap, int32_t *n) {
     if (!m->last.valid) return mesh_fail(m, DSM_E_STATE, "no frame fused yet");

@@ -1,5 +1,6 @@
 // dsm_surfel_map_node.h -- the state of the node (include/dsm_surfel_map.h), shared by its two translation units:
-// dsm_surfel_map.cpp (the host logic of class SurfelMap) and dsm_surfel_map_clouds.cpp (the point-cloud publications).
+// dsm_surfel_map.cpp (the host logic of class SurfelMap), dsm_surfel_map_clouds.cpp (the point-cloud publications),
+// dsm_surfel_map_mesh.cpp and dsm_surfel_map_render.cpp (the mesh and the rendered images).
 // dsm_surfel_map.cpp calls only the engine entry points it always called; the publications reach it through the function
 // pointers of struct dsm_surfel_map.  Internal: not installed, not part of the C ABI.
 #pragma once
@@ -110,6 +111,7 @@ struct FuseInfo {
     int relative_index = -1;
     dsm_pose_msg fuse_pose = {}; // fuse_pose_ros = pose_eigen2ros(reference_pose * relative_pose)
     int slot = 0;               // the engine frame slot that holds the fused frame
+    float pose16[16] = {};      // the cam -> world matrix the engine fused it with (dsm_surfel_map_render's default pose)
 };
 
 } // namespace dsm_node
@@ -162,6 +164,18 @@ inline void get_driftfree_poses(const dsm_surfel_map *m, int root_index, std::ve
                 }
         this_level.swap(next_level);
         next_level.clear();
+    }
+}
+
+// save_mesh's order of the attached surfels (surfel_map.cpp:1226-1238): keyframe by keyframe, in poses_database order (not
+// store order), as runs of the store
+inline void attached_runs(const dsm_surfel_map *m, std::vector<int32_t> &begin, std::vector<int32_t> &count) {
+    for (const dsm_surfel_map::PoseElement &pe : m->poses_database) {
+        if (pe.segment < 0) continue;
+        const dsm_surfel_map::Segment &sg = m->segments[(size_t)pe.segment];
+        if (sg.count <= 0) continue;
+        begin.push_back(sg.begin);
+        count.push_back(sg.count);
     }
 }
 

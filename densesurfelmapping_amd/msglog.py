@@ -87,7 +87,7 @@ def read_log(path):
 EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-products -> SurfelMap(engine_flags=...)
 
 
-def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None):
+def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None):
     """Feed a log to a SurfelMap on the GPU; returns a summary dict."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
@@ -105,6 +105,9 @@ def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, e
         node.save_mesh(save_mesh)
     if save_mesh_binary:
         node.save_mesh_binary(save_mesh_binary)
+    if render:  # the whole map as the node's camera sees it from the final fuse pose
+        planes = node.render("all")
+        np.savez(render, **{k: planes[k] for k in api.RENDER_PLANES})
     node.close()
     return out
 
@@ -115,6 +118,7 @@ def main():
     ap.add_argument("--save-cloud", help="ASCII PCD (SurfelMap::save_cloud)")
     ap.add_argument("--save-mesh", help="ASCII PLY hexagon mesh (SurfelMap::save_mesh)")
     ap.add_argument("--save-mesh-binary", help="the same mesh as a binary little-endian PLY, vertices built on the GPU")
+    ap.add_argument("--render", metavar="PATH.npz", help="depth, index, normal and intensity images of the whole map at the final fuse pose")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
                     help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
@@ -124,7 +128,7 @@ def main():
         cam = synth.KITTI_1226
         write_log(args.log, cam, 10, synth.node_messages(cam, synth.Scene(), args.synth, lap=120))
     print(json.dumps(replay(args.log, args.save_cloud, args.save_mesh, device=args.device, eigen_products=args.eigen_products,
-                            save_mesh_binary=args.save_mesh_binary)))
+                            save_mesh_binary=args.save_mesh_binary, render=args.render)))
 
 
 if __name__ == "__main__":

@@ -23,6 +23,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_get_inactive_cloud", "dsm_surfel_map_get_cloud", "dsm_surfel_map_get_cloud_device", "dsm_surfel_map_set_publish",
     "dsm_surfel_map_depth_input_u16", "dsm_surfel_map_image_input_color",
     "dsm_surfel_map_get_mesh", "dsm_surfel_map_get_mesh_device", "dsm_surfel_map_save_mesh_binary",
+    "dsm_surfel_map_render", "dsm_surfel_map_render_device",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -93,6 +94,9 @@ def _bind(lib):
             lib.dsm_surfel_map_get_mesh.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
             lib.dsm_surfel_map_get_mesh_device.argtypes = [_vp, C.c_int, _vp, C.c_int32, _vp]
             lib.dsm_surfel_map_save_mesh_binary.argtypes = [_vp, C.c_char_p]
+        if hasattr(lib, "dsm_surfel_map_render"):  # (nor the renderer)
+            for name in ("dsm_surfel_map_render", "dsm_surfel_map_render_device"):
+                getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._RenderCamera), _vp, C.c_uint32, C.POINTER(api._RenderPlanes), _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -209,6 +213,28 @@ class SurfelMap:
     def save_mesh_binary(self, path: str):
         """save_mesh's mesh as a binary little-endian PLY (15-byte vertices, 13-byte faces), streamed from the GPU in chunks"""
         self._check(self._lib.dsm_surfel_map_save_mesh_binary(self._h, path.encode()))
+
+    # ---- the map as images (dsm_render_compose)
+    def render(self, kind="all", camera=None, pose=None, flags=0, planes=api.RENDER_PLANES, dst_ptrs=None):
+        """What `camera` (None: the node's; api.render_camera's forms) at `pose` (4x4 cam -> world or 16 column-major floats; None:
+        the pose of the latest fuse) sees of the surfels of cloud `kind` ("active" / "inactive" / "all" / "neighbor" or CLOUD_*):
+        a dict of [height, width] arrays "depth" float32, "index" int32 (for "all": the surfel's number in get_mesh), "normal"
+        float32 [.., 3], "intensity" uint8, plus "n_surfels" -- or, with dst_ptrs = {plane: device pointer}, n_surfels."""
+        k = self._kind(kind)
+        cam = None if camera is None else api.render_camera(camera)
+        shape_cam = cam if cam is not None else api.render_camera(self.cam)
+        p = None
+        if pose is not None:
+            p = np.asarray(pose, np.float32)
+            p = api.pose_to_colmajor(p) if p.shape == (4, 4) else np.ascontiguousarray(p.reshape(16))
+        st, out = api.render_outputs(shape_cam, planes, dst_ptrs)
+        n = C.c_int32()
+        fn = self._lib.dsm_surfel_map_render if dst_ptrs is None else self._lib.dsm_surfel_map_render_device
+        self._check(fn(self._h, k, None if cam is None else C.byref(cam), None if p is None else _ptr(p), flags, C.byref(st), C.byref(n)))
+        if dst_ptrs is not None:
+            return n.value
+        out["n_surfels"] = n.value
+        return out
 
     # ---- taps
     @property

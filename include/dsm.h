@@ -273,6 +273,39 @@ int dsm_mesh_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
  * host or device memory (n_surfels * 48 bytes; at most 715827882 surfels: the vertex index is 32 bits).  Synchronises. */
 int dsm_mesh_indices(dsm_handle *h, int32_t n_surfels, void *dst, int dst_on_device);
 
+/* ---- the map as an image: what a pinhole camera at any pose sees of the surfels (no counterpart in the reference) ----
+ * The surfel sequence is dsm_mesh_compose's: the store's RECORD runs in list order, then the map part chosen by `select`;
+ * surfel number i of a render is surfel i of the mesh.  A surfel is a disc of radius `size` about its position in the plane
+ * of its normal.  The ray of pixel (u, v) is ((u - cx) / fx, (v - cy) / fy, 1): it passes through the integer pixel
+ * coordinate, as the fuse kernel's projection assumes.  With p_c, n_c the surfel's centre and normal in the camera frame,
+ * z = (n_c . p_c) / (n_c . ray); the pixel is hit iff near_dist < z < far_dist (z finite) and |z ray - p_c|^2 <= size * size.
+ * So a zero normal, an edge-on disc and a record with a NaN or an infinity never hit.  The pixel shows the hit with the
+ * smallest 64-bit key (bits of z) << 32 | surfel number: the nearest, the lower number on an exact tie -- a minimum over a
+ * total order, so the image does not depend on the order the GPU finds the hits in and is reproducible bit for bit. */
+typedef struct dsm_render_camera {
+    int32_t width, height;     /* 1 .. 8192 each; independent of the handle's frame size */
+    float fx, fy, cx, cy;      /* fx, fy > 0 */
+    float near_dist, far_dist; /* 0 < near_dist < far_dist */
+} dsm_render_camera;
+/* tight row-major planes, host or device memory; any may be NULL (not written), not all */
+typedef struct dsm_render_planes {
+    float *depth;       /* [height][width]     camera-frame z of the nearest hit; 0.0f where nothing is hit */
+    int32_t *index;     /* [height][width]     its surfel number in the sequence; -1 */
+    float *normal;      /* [height][width][3]  its normal rotated into the camera frame (in DSM_FLAG_EIGEN33_PRODUCTS' order on a
+                                               handle created with that flag); 0 0 0 */
+    uint8_t *intensity; /* [height][width]     (int)color clamped to 0..255, the byte of DSM_MESH_VERTEX_XYZ_RGBA8; 0 */
+} dsm_render_planes;
+#define DSM_RENDER_CULL_BACKFACES 1u /* also drop surfels with n_c . p_c >= 0 (the default is two-sided) */
+/* pose16: cam -> world, 16 column-major floats as for dsm_fuse_map; pose_inv16: the caller's own world -> cam matrix (the
+ * rule of the *_inv entry points) or NULL = the closed-form inverse.  *n_surfels = the length of the sequence: index values
+ * are below it.  Checked before any device work (DSM_E_INVALID, nothing written): a run outside the store, width / height
+ * outside 1..8192, fx / fy not positive, near_dist <= 0 or near_dist >= far_dist, a non-finite camera or pose entry, all four
+ * planes NULL, unknown flags.  Launched eagerly on the handle's stream behind the frames enqueued so far; a device
+ * destination is ordered like dsm_cloud_compose's.  Synchronises. */
+int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                       const dsm_render_camera *camera, const float *pose16, const float *pose_inv16, uint32_t flags,
+                       const dsm_render_planes *planes, int dst_on_device, int32_t *n_surfels);
+
 /* Copy a frame into frame slot `slot` (0 .. frame_slots-1 of the config) and return when it is there (the host
  * buffers may be reused).  By default the copy is ordered behind everything enqueued so far.  With
  * DSM_FLAG_UPLOAD_STREAM it runs on the handle's upload stream instead: it waits only for the enqueued frames that

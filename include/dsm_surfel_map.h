@@ -158,6 +158,19 @@ int dsm_surfel_map_get_mesh_device(dsm_surfel_map *m, int vertex_layout, void *d
  * path is DSM_E_INVALID; the file is opened after the last call that can fail without it, and removed if a later one fails. */
 int dsm_surfel_map_save_mesh_binary(dsm_surfel_map *m, const char *path);
 
+/* ---- the map as images: what a camera sees of it (dsm_render_compose of dsm.h, where a render is defined) ----
+ * kind = DSM_CLOUD_ACTIVE / INACTIVE / ALL / NEIGHBOR: the surfel set of that cloud, as RECORD runs in the mesh's order -- the
+ * attached surfels keyframe by keyframe first (ALL, INACTIVE: in poses_database order, so that for ALL surfel number i is
+ * surfel i of dsm_surfel_map_get_mesh; NEIGHBOR: the non-local drift-free neighbours in their breadth-first order), then the
+ * active surfels (ACTIVE, ALL: update_times >= 5; NEIGHBOR: update_times != 0).  DSM_CLOUD_RAW: DSM_E_INVALID.  camera NULL:
+ * the node's own camera and fuse distances.  pose16 (cam -> world, 16 column-major floats) NULL: the pose of the latest fuse --
+ * the map's prediction of the frame just fused.  flags: DSM_RENDER_*.  DSM_E_STATE before the first fuse.  Synchronises. */
+int dsm_surfel_map_render(dsm_surfel_map *m, int kind, const dsm_render_camera *camera, const float *pose16, uint32_t flags,
+                          const dsm_render_planes *planes, int32_t *n_surfels);
+/* the same with the planes in device memory of the node's GPU */
+int dsm_surfel_map_render_device(dsm_surfel_map *m, int kind, const dsm_render_camera *camera, const float *pose16, uint32_t flags,
+                                 const dsm_render_planes *planes_device, int32_t *n_surfels);
+
 /* ---- taps (what the publish_* methods read) ---- */
 dsm_handle *dsm_surfel_map_engine(dsm_surfel_map *m); /* active map: dsm_map_size / dsm_map_download */
 int64_t dsm_surfel_map_frames_fused(const dsm_surfel_map *m);

@@ -124,6 +124,7 @@ class SurfelMap {
         c.surfel_capacity = p.surfel_capacity;
         c.max_buffered_frames = p.max_buffered_frames;
         c.engine_flags = p.engine_flags;
+        own_pixels_ = (size_t)(p.cam_width > 0 ? p.cam_width : 0) * (size_t)(p.cam_height > 0 ? p.cam_height : 0);
         const int rc = dsm_surfel_map_create(&c, &m_);
         if (rc != DSM_OK) {
             m_ = nullptr;
@@ -202,6 +203,31 @@ class SurfelMap {
     }
     int save_mesh_binary(const std::string &save_path_name) { return check(dsm_surfel_map_save_mesh_binary(m_, save_path_name.c_str())); }
 
+    // the map as images (dsm_render_compose of dsm.h): what `camera` (nullptr: the node's) at `pose16` (cam -> world, column-major;
+    // nullptr: the latest fuse's) sees of the surfels of cloud `kind`.  The planes that are not nullptr are resized to width * height
+    // (normal: * 3) and filled: depth 0 / index -1 / normal 0 0 0 / intensity 0 where nothing is hit.
+    int render(dsm_cloud_kind kind, const dsm_render_camera *camera, const float *pose16, uint32_t flags, std::vector<float> *depth,
+               std::vector<int32_t> *index, std::vector<float> *normal, std::vector<uint8_t> *intensity, int32_t *n_surfels = nullptr) {
+        const size_t px = camera ? (size_t)(camera->width > 0 ? camera->width : 0) * (size_t)(camera->height > 0 ? camera->height : 0) : own_pixels_;
+        dsm_render_planes planes = {nullptr, nullptr, nullptr, nullptr};
+        if (depth) { depth->resize(px); planes.depth = depth->data(); }
+        if (index) { index->resize(px); planes.index = index->data(); }
+        if (normal) { normal->resize(px * 3); planes.normal = normal->data(); }
+        if (intensity) { intensity->resize(px); planes.intensity = intensity->data(); }
+        int32_t n = 0;
+        const int rc = check(dsm_surfel_map_render(m_, kind, camera, pose16, flags, &planes, &n));
+        if (n_surfels) *n_surfels = n;
+        return rc;
+    }
+    // the same into device memory of the node's GPU
+    int render_device(dsm_cloud_kind kind, const dsm_render_camera *camera, const float *pose16, uint32_t flags, const dsm_render_planes &planes_device,
+                      int32_t *n_surfels = nullptr) {
+        int32_t n = 0;
+        const int rc = check(dsm_surfel_map_render_device(m_, kind, camera, pose16, flags, &planes_device, &n));
+        if (n_surfels) *n_surfels = n;
+        return rc;
+    }
+
     // the point-cloud topics (publish_*_pointcloud, surfel_map.cpp:1115-1151, 1283-1454): xyzi = 4 floats per point
     int get_cloud(dsm_cloud_kind kind, std::vector<float> &xyzi) {
         int32_t n = 0;
@@ -252,6 +278,7 @@ class SurfelMap {
         return rc; // (with DSM_WITH_ROS the callbacks report and carry on, as the reference's void callbacks do)
     }
     dsm_surfel_map *m_ = nullptr;
+    size_t own_pixels_ = 0; // cam_width * cam_height: the size of render()'s planes for the node's own camera
     int32_t gray_weights_[4] = DSM_GRAY_OPENCV_14BIT;
     std::unique_ptr<PublishFn> publish_; // the callback: outlives the map (the destructor body destroys the map first)
 };
