@@ -70,6 +70,8 @@ ABI_SYMBOLS = (
     "dsm_mesh_compose", "dsm_mesh_indices",
     # the map as depth / index / normal / intensity images from any pose
     "dsm_render_compose",
+    # a depth frame against the rendered map: one evaluation of the normal equations, and the point-to-plane loop
+    "dsm_align_params_init", "dsm_align_equations", "dsm_align_frame",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -155,6 +157,12 @@ RENDER_PLANES = ("depth", "index", "normal", "intensity")
 RENDER_PLANE_TYPES = {"depth": (np.float32, ()), "index": (np.int32, ()), "normal": (np.float32, (3,)), "intensity": (np.uint8, ())}
 
 
+# dsm_align_status, and the layout of the 29 sums (include/dsm.h)
+ALIGN_CONVERGED, ALIGN_MAX_ITERATIONS, ALIGN_TOO_FEW, ALIGN_SINGULAR = range(4)
+ALIGN_STATUS = ("converged", "max_iterations", "too_few", "singular")
+ALIGN_SUMS = 29
+
+
 class DsmError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"dsm error {code}: {msg}")
@@ -178,6 +186,39 @@ class _RenderCamera(C.Structure):
 
 class _RenderPlanes(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("index", C.c_void_p), ("normal", C.c_void_p), ("intensity", C.c_void_p)]
+
+
+class _AlignParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_iterations", C.c_int32), ("stride", C.c_int32), ("dist_max", C.c_float),
+                ("min_view_cos", C.c_float), ("huber", C.c_float), ("min_pixels", C.c_int32), ("stop_translation", C.c_float),
+                ("stop_rotation", C.c_float)]
+
+
+class _AlignResult(C.Structure):
+    _fields_ = [("pose16", C.c_float * 16), ("T16", C.c_float * 16), ("status", C.c_int32), ("iterations", C.c_int32), ("n_pixels", C.c_int32),
+                ("scale_log2", C.c_int32), ("rms", C.c_double), ("sums", C.c_int64 * ALIGN_SUMS)]
+
+
+def align_params(params=None, **kw) -> _AlignParams:
+    """a dsm_align_params: one passed through, or the library's defaults (dsm_align_params_init: 10 iterations, stride 2, dist_max
+    0.25 m, min_view_cos 0.2, huber 0.05 m, min_pixels 200, stop at 1e-4 m and 1e-4 rad) with the fields named in kw replaced"""
+    if isinstance(params, _AlignParams):
+        return params
+    p = _AlignParams()
+    load_library().dsm_align_params_init(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if k not in dict(_AlignParams._fields_):
+            raise ValueError("no such align parameter: %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def align_result(r: _AlignResult) -> dict:
+    """a dsm_align_result as a dict: "pose" and "T" 4x4 float32 (row-major numpy), "status" (ALIGN_*), "iterations", "n_pixels",
+    "rms", "scale_log2", "sums" int64 [29]"""
+    return {"pose": np.array(r.pose16, np.float32).reshape(4, 4).T.copy(), "T": np.array(r.T16, np.float32).reshape(4, 4).T.copy(),
+            "status": r.status, "iterations": r.iterations, "n_pixels": r.n_pixels, "rms": r.rms, "scale_log2": r.scale_log2,
+            "sums": np.array(r.sums, np.int64)}
 
 
 def render_camera(cam) -> _RenderCamera:
@@ -276,6 +317,11 @@ def load_library():
     lib.dsm_mesh_indices.argtypes = [_vp, C.c_int32, _vp, C.c_int]
     lib.dsm_render_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_RenderCamera), _vp, _vp, C.c_uint32, C.POINTER(_RenderPlanes),
                                        C.c_int, _vp]
+    lib.dsm_align_params_init.argtypes = [C.POINTER(_AlignParams)]
+    lib.dsm_align_params_init.restype = None
+    lib.dsm_align_equations.argtypes = [_vp, C.c_int, C.POINTER(_RenderCamera), _vp, _vp, _vp, C.POINTER(_AlignParams), _vp, _vp]
+    lib.dsm_align_frame.argtypes = [_vp, C.c_int, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_RenderCamera), _vp, C.POINTER(_AlignParams),
+                                    C.POINTER(_AlignResult)]
     lib.dsm_frame_upload.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_upload_device.argtypes = [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]
     lib.dsm_frame_pitch.argtypes = [_vp, _vp]
@@ -604,6 +650,36 @@ class FusionFunctions:
             return n.value
         out["n_surfels"] = n.value
         return out
+
+    # ---- a depth frame against the rendered map -----------------------------------------------------
+    def align_equations(self, slot, model_cam, model_depth_ptr, model_normal_ptr, T, params=None):
+        """dsm_align_equations: one evaluation of the frame in `slot` against the model planes in DEVICE memory (pointers, e.g.
+        torch data_ptr(): depth [h, w] float32, normal [h, w, 3] float32 as render() writes them for `model_cam`), T the 4x4
+        frame camera -> model camera transform (or 16 column-major floats).  Returns (sums int64 [29], scale_log2)."""
+        cam = render_camera(model_cam)
+        t = np.asarray(T, np.float32)
+        t = pose_to_colmajor(t) if t.shape == (4, 4) else np.ascontiguousarray(t.reshape(16))
+        p = align_params(params)
+        sums = np.zeros(ALIGN_SUMS, np.int64)
+        k = C.c_int32(0)
+        self._check(self._lib.dsm_align_equations(self._h, slot, C.byref(cam), _vp(model_depth_ptr), _vp(model_normal_ptr), _ptr(t), C.byref(p),
+                                                  _ptr(sums), C.byref(k)))
+        return sums, k.value
+
+    def align_frame(self, slot, select, segs, pose_guess, model_cam=None, params=None):
+        """dsm_align_frame: the frame in `slot` aligned, point to plane, against the surfel sequence of render(select, segs) seen by
+        `model_cam` (None: the handle's camera and fuse distances) at `pose_guess`.  Returns align_result's dict."""
+        seg = np.ascontiguousarray(np.asarray(segs, np.int32).reshape(-1, 2))
+        b = np.ascontiguousarray(seg[:, 0]) if len(seg) else np.zeros(1, np.int32)
+        c = np.ascontiguousarray(seg[:, 1]) if len(seg) else np.zeros(1, np.int32)
+        cam = None if model_cam is None else render_camera(model_cam)
+        g = np.asarray(pose_guess, np.float32)
+        g = pose_to_colmajor(g) if g.shape == (4, 4) else np.ascontiguousarray(g.reshape(16))
+        p = align_params(params)
+        r = _AlignResult()
+        self._check(self._lib.dsm_align_frame(self._h, slot, select, len(seg), _ptr(b), _ptr(c), None if cam is None else C.byref(cam), _ptr(g),
+                                              C.byref(p), C.byref(r)))
+        return align_result(r)
 
     def mesh_indices(self, n_surfels, dst_ptr=None):
         """dsm_mesh_indices: the (n_surfels * 4, 3) uint32 triangles of n_surfels hexagons -- or, with dst_ptr, into device memory."""

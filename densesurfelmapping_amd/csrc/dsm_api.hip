@@ -268,6 +268,12 @@ struct dsm_handle {
     size_t render_px = 0;
     void *d_render_splats = nullptr;
     size_t render_seq = 0;
+    // dsm_align_equations / dsm_align_frame: none before the first call -- the 29 sums on the device and their page-locked landing
+    // place, and (dsm_align_frame, grow-only) the rendered model planes: align_px depths, then 3 * align_px normal components
+    unsigned long long *d_align_sums = nullptr;
+    int64_t *h_align_sums = nullptr;
+    float *d_align_planes = nullptr;
+    size_t align_px = 0;
     // drop-in calls (dsm_fuse_map / dsm_fuse_initialize_map): page-locked staging owned by the handle
     uint8_t *pin_frame = nullptr; // one frame, image then depth, rows at the frame slots' pitch
     dsm_surfel *pin_map = nullptr; // shadow of the caller's array: what the last drop-in call returned == the device map
@@ -1393,6 +1399,9 @@ void dsm_destroy(dsm_handle *h) {
     if (h->ev_pub_dst) (void)hipEventDestroy(h->ev_pub_dst);
     if (h->d_render_keys) (void)hipFree(h->d_render_keys);
     if (h->d_render_splats) (void)hipFree(h->d_render_splats);
+    if (h->d_align_sums) (void)hipFree(h->d_align_sums);
+    if (h->d_align_planes) (void)hipFree(h->d_align_planes);
+    if (h->h_align_sums) (void)hipHostFree(h->h_align_sums);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->h_scalars) (void)hipHostFree(h->h_scalars);
     if (h->pin_frame) (void)hipHostFree(h->pin_frame);
@@ -2024,13 +2033,47 @@ int render_reserve(dsm_handle *h, size_t px, size_t side_sum, size_t seq) {
 } // namespace
 
 // the sequence is dsm_mesh_compose's: the store's record runs first, then the map part
+namespace {
+
+// What dsm_render_compose is asked to show, checked before anything reaches the device (dsm_align_frame makes the same checks in
+// front of its own device work): the select, the run list, the poses, the resident map, every run against the store, and the
+// length of the sequence.  seg: (begin, count, offset in the sequence) of the runs that are not empty.
+struct RenderSequence {
+    std::vector<int32_t> seg;
+    int64_t runs_total = 0, bound = 0;
+    int n_upper = 0;
+};
+
+int render_check_sequence(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, const float *pose16,
+                          const float *pose_inv16, RenderSequence &sq) {
+    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
+    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(pose16[k]) || (pose_inv16 && !std::isfinite(pose_inv16[k]))) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
+    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
+    for (int32_t s = 0; s < n_segments; s++) {
+        const int32_t b = store_begin[s], cnt = store_count[s];
+        if (b < 0 || cnt < 0 || (int64_t)b + cnt > h->store_n)
+            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, cnt, h->store_n);
+        if (!cnt) continue; // empty runs are dropped
+        sq.seg.push_back(b);
+        sq.seg.push_back(cnt);
+        sq.seg.push_back((int32_t)sq.runs_total);
+        sq.runs_total += cnt;
+    }
+    sq.n_upper = select == kCloudNone ? 0 : h->map_upper;
+    sq.bound = (int64_t)sq.n_upper + sq.runs_total;
+    if (sq.bound > INT32_MAX - 4096) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)sq.bound);
+    return DSM_OK;
+}
+
+} // namespace
+
 int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
                        const dsm_render_camera *camera, const float *pose16, const float *pose_inv16, uint32_t flags, const dsm_render_planes *planes,
                        int dst_on_device, int32_t *n_surfels) {
     if (!h || !n_surfels) return DSM_E_INVALID;
     if (!camera || !pose16 || !planes) return fail(h, DSM_E_INVALID, "null camera, pose or planes");
-    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
-    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
     if (flags & ~(uint32_t)DSM_RENDER_CULL_BACKFACES) return fail(h, DSM_E_INVALID, "render flags 0x%x", flags);
     const dsm_render_camera &c = *camera;
     if (c.width < 1 || c.width > kRenderMaxSide || c.height < 1 || c.height > kRenderMaxSide)
@@ -2040,27 +2083,13 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
     if (!(c.near_dist > 0.0f) || !(c.near_dist < c.far_dist) || !std::isfinite(c.far_dist))
         return fail(h, DSM_E_INVALID, "render depth range (%g, %g)", (double)c.near_dist, (double)c.far_dist);
     if (!planes->depth && !planes->index && !planes->normal && !planes->intensity) return fail(h, DSM_E_INVALID, "no output plane");
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(pose16[k]) || (pose_inv16 && !std::isfinite(pose_inv16[k]))) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
-    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
-    // the runs, checked before anything reaches the device; empty ones are dropped
-    std::vector<int32_t> seg;
-    int64_t runs_total = 0;
-    for (int32_t s = 0; s < n_segments; s++) {
-        const int32_t b = store_begin[s], cnt = store_count[s];
-        if (b < 0 || cnt < 0 || (int64_t)b + cnt > h->store_n)
-            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, cnt, h->store_n);
-        if (!cnt) continue;
-        seg.push_back(b);
-        seg.push_back(cnt);
-        seg.push_back((int32_t)runs_total);
-        runs_total += cnt;
-    }
-    const int n_upper = select == kCloudNone ? 0 : h->map_upper;
-    const int64_t bound = (int64_t)n_upper + runs_total;
-    if (bound > INT32_MAX - 4096) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)bound);
-    int rc = bind_device(h);
+    RenderSequence sq;
+    int rc = render_check_sequence(h, select, n_segments, store_begin, store_count, pose16, pose_inv16, sq);
     if (rc) return rc;
+    const std::vector<int32_t> &seg = sq.seg;
+    const int64_t runs_total = sq.runs_total, bound = sq.bound;
+    const int n_upper = sq.n_upper;
+    if ((rc = bind_device(h))) return rc;
     const int w = c.width, hh = c.height;
     const size_t px = (size_t)w * hh, tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
     // a host destination's planes are staged behind one another, each from a 16-byte boundary
@@ -2112,6 +2141,151 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
         if (planes->normal) HIP_TRY(h, hipMemcpy(planes->normal, o_normal, 3 * px * sizeof(float), hipMemcpyDeviceToHost));
         if (planes->intensity) HIP_TRY(h, hipMemcpy(planes->intensity, o_int, px, hipMemcpyDeviceToHost));
     }
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ a depth frame against the rendered map (dsm_k_align.h)
+
+namespace {
+
+const char *align_params_error(const dsm_align_params *p) {
+    if (p->struct_size != sizeof(dsm_align_params)) return "struct_size is not sizeof(dsm_align_params)";
+    if (p->max_iterations < 1) return "max_iterations < 1";
+    return nullptr;
+}
+
+// the handle's frame side and the checks that need no device: c is ready but for T
+int align_setup(dsm_handle *h, int slot, const dsm_render_camera *model_cam, const dsm_align_params *params, AlignConst &c) {
+    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
+    if (const char *why = align_params_error(params)) return fail(h, DSM_E_INVALID, "align: %s", why);
+    AlignFrame f;
+    f.w = h->hc.w; f.h = h->hc.h; f.pitch = h->hc.pitch;
+    f.fx = h->cfg.fx; f.fy = h->cfg.fy; f.cx = h->cfg.cx; f.cy = h->cfg.cy;
+    f.near_d = h->cfg.near_dist; f.far_d = h->cfg.far_dist;
+    RenderCam m;
+    m.w = model_cam->width; m.h = model_cam->height;
+    m.fx = model_cam->fx; m.fy = model_cam->fy; m.cx = model_cam->cx; m.cy = model_cam->cy;
+    m.near_d = model_cam->near_dist; m.far_d = model_cam->far_dist;
+    if (const char *why = align_prepare(f, m, params->stride, params->dist_max, params->min_view_cos, params->huber, c))
+        return fail(h, DSM_E_INVALID, "align: %s", why);
+    return DSM_OK;
+}
+
+int align_reserve(dsm_handle *h, size_t px) {
+    if (!h->d_align_sums) HIP_TRY(h, hipMalloc((void **)&h->d_align_sums, 256));
+    if (!h->h_align_sums) HIP_TRY(h, hipHostMalloc((void **)&h->h_align_sums, 256, hipHostMallocDefault));
+    if (px > h->align_px) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_align_planes) (void)hipFree(h->d_align_planes);
+        h->d_align_planes = nullptr;
+        h->align_px = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->d_align_planes, (px * 4 + 64) * sizeof(float)));
+        h->align_px = px;
+    }
+    return DSM_OK;
+}
+
+// the stream behind the uploads that wrote the slot
+int align_order_slot(dsm_handle *h, int slot) {
+    const ReadSlots reads(h, slot, slot + 1);
+    return wait_uploads(h, h->stream, kSerialBit);
+}
+
+// one evaluation: clear, launch, bring the 29 words back through page-locked memory, wait
+int align_evaluate(dsm_handle *h, const AlignConst &c, int slot, const float *zm, const float *nm, int64_t *sums) {
+    const float *depth = (const float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
+    const hipError_t e = launch_align(c, depth, zm, nm, h->d_align_sums, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "align launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(h->h_align_sums, h->d_align_sums, kAlignSums * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    memcpy(sums, h->h_align_sums, kAlignSums * sizeof(int64_t));
+    return DSM_OK;
+}
+
+} // namespace
+
+void dsm_align_params_init(dsm_align_params *p) {
+    if (!p) return;
+    p->struct_size = (uint32_t)sizeof(dsm_align_params);
+    p->max_iterations = 10;
+    p->stride = 2;
+    p->dist_max = 0.25f;
+    p->min_view_cos = 0.2f;
+    p->huber = 0.05f;
+    p->min_pixels = 200;
+    p->stop_translation = 1e-4f;
+    p->stop_rotation = 1e-4f;
+}
+
+int dsm_align_equations(dsm_handle *h, int slot, const dsm_render_camera *model_cam, const void *model_depth_dev, const void *model_normal_dev,
+                        const float *T16, const dsm_align_params *params, int64_t *sums, int32_t *scale_log2) {
+    if (!h) return DSM_E_INVALID;
+    if (!model_cam || !model_depth_dev || !model_normal_dev || !T16 || !params || !sums || !scale_log2)
+        return fail(h, DSM_E_INVALID, "align: null argument");
+    AlignConst c;
+    int rc = align_setup(h, slot, model_cam, params, c);
+    if (rc) return rc;
+    for (int k = 0; k < 16; k++) {
+        if (!std::isfinite(T16[k])) return fail(h, DSM_E_INVALID, "align: T entry %d is not finite", k);
+        c.T[k] = T16[k];
+    }
+    if ((rc = bind_device(h))) return rc;
+    if ((rc = align_reserve(h, 0))) return rc;
+    if ((rc = pub_order_dst(h))) return rc;
+    if ((rc = align_order_slot(h, slot))) return rc;
+    int64_t got[kAlignSums];
+    if ((rc = align_evaluate(h, c, slot, (const float *)model_depth_dev, (const float *)model_normal_dev, got))) return rc;
+    memcpy(sums, got, sizeof got);
+    *scale_log2 = c.scale_log2;
+    return DSM_OK;
+}
+
+int dsm_align_frame(dsm_handle *h, int slot, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                    const dsm_render_camera *model_cam, const float *pose16_guess, const dsm_align_params *params, dsm_align_result *result) {
+    if (!h) return DSM_E_INVALID;
+    if (!pose16_guess || !params || !result) return fail(h, DSM_E_INVALID, "align: null argument");
+    dsm_render_camera own;
+    if (!model_cam) { // the handle's camera and fuse distances
+        own.width = h->hc.w; own.height = h->hc.h;
+        own.fx = h->cfg.fx; own.fy = h->cfg.fy; own.cx = h->cfg.cx; own.cy = h->cfg.cy;
+        own.near_dist = h->cfg.near_dist; own.far_dist = h->cfg.far_dist;
+        model_cam = &own;
+    }
+    AlignConst c;
+    int rc = align_setup(h, slot, model_cam, params, c);
+    if (rc) return rc;
+    // dsm_render_compose's own checks of what it is handed below, made here so that they too come before any device work
+    RenderSequence sq;
+    if ((rc = render_check_sequence(h, select, n_segments, store_begin, store_count, pose16_guess, nullptr, sq))) return rc;
+    if ((rc = bind_device(h))) return rc;
+    const size_t px = (size_t)model_cam->width * model_cam->height;
+    if ((rc = align_reserve(h, px))) return rc;
+    // the model, once: two-sided, the closed-form inverse, into the handle's scratch (the call synchronises)
+    float *zm = h->d_align_planes, *nm = h->d_align_planes + px;
+    dsm_render_planes planes = {zm, nullptr, nm, nullptr};
+    int32_t n_surfels = 0;
+    if ((rc = dsm_render_compose(h, select, n_segments, store_begin, store_count, model_cam, pose16_guess, nullptr, 0, &planes, 1, &n_surfels))) return rc;
+    if ((rc = align_order_slot(h, slot))) return rc;
+    AlignLoop lp;
+    lp.max_iterations = params->max_iterations;
+    lp.min_pixels = params->min_pixels;
+    lp.stop_translation = (double)params->stop_translation;
+    lp.stop_rotation = (double)params->stop_rotation;
+    lp.scale_log2 = c.scale_log2;
+    AlignOutcome o;
+    rc = align_loop(lp, [&](const float *T16, int64_t *sums) {
+        for (int k = 0; k < 16; k++) c.T[k] = T16[k];
+        return align_evaluate(h, c, slot, zm, nm, sums);
+    }, o);
+    if (rc) return rc;
+    align_refined_pose(pose16_guess, o.T, result->pose16);
+    for (int k = 0; k < 16; k++) result->T16[k] = (float)o.T[k];
+    result->status = o.status;
+    result->iterations = o.iterations;
+    result->n_pixels = (int32_t)o.n_pixels;
+    result->scale_log2 = c.scale_log2;
+    result->rms = o.rms;
+    for (int k = 0; k < kAlignSums; k++) result->sums[k] = o.sums[k];
     return DSM_OK;
 }
 

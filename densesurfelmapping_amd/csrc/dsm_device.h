@@ -236,4 +236,9 @@ hipError_t launch_render(const dsm_surfel *store, const int32_t *seg, int n_seg,
                          const RenderScratch &sc, const float *ray_x, const float *ray_y, float *depth, int32_t *index, float *normal,
                          uint8_t *intensity, hipStream_t st);
 
+// ---- a depth frame against the rendered map (dsm_k_align.h; the definition is align_pixel of dsm_align.h)
+// One evaluation: clears sums[29] on `st`, then adds the fixed-point terms of every sampled pixel of the frame plane `depth`
+// ([h][pitch]) that passes align_pixel against the model planes zm [mh][mw] and nm [mh][mw][3].  c from align_prepare, with T set.
+hipError_t launch_align(const AlignConst &c, const float *depth, const float *zm, const float *nm, unsigned long long *sums, hipStream_t st);
+
 } // namespace dsm

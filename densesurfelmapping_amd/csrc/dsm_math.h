@@ -906,3 +906,6 @@ DSM_HD int chunk_of(int n, int i) {
 }
 
 } // namespace dsm
+
+// a depth frame against the rendered map: align_pixel and the 29 fixed-point sums, the 6x6 step and the loop
+#include "dsm_align.h"

@@ -1,6 +1,6 @@
 // dsm_surfel_map_node.h -- the state of the node (include/dsm_surfel_map.h), shared by its two translation units:
 // dsm_surfel_map.cpp (the host logic of class SurfelMap), dsm_surfel_map_clouds.cpp (the point-cloud publications),
-// dsm_surfel_map_mesh.cpp and dsm_surfel_map_render.cpp (the mesh and the rendered images).
+// dsm_surfel_map_mesh.cpp, dsm_surfel_map_render.cpp and dsm_surfel_map_align.cpp (the mesh, the rendered images, the alignment).
 // dsm_surfel_map.cpp calls only the engine entry points it always called; the publications reach it through the function
 // pointers of struct dsm_surfel_map.  Internal: not installed, not part of the C ABI.
 #pragma once
@@ -177,6 +177,29 @@ inline void attached_runs(const dsm_surfel_map *m, std::vector<int32_t> &begin, 
         begin.push_back(sg.begin);
         count.push_back(sg.count);
     }
+}
+
+// The surfel set of a cloud kind as dsm_render_compose takes it: the map part's `select` and the store's record runs in the mesh's
+// order (dsm_surfel_map_render's rules; NEIGHBOR: surfel_map.cpp:1292-1319).  False: the kind has no such set (RAW, unknown).
+inline bool render_runs(const dsm_surfel_map *m, int kind, int &select, std::vector<int32_t> &begin, std::vector<int32_t> &count) {
+    select = DSM_CLOUD_SELECT_NONE;
+    if (kind == DSM_CLOUD_ACTIVE || kind == DSM_CLOUD_INACTIVE || kind == DSM_CLOUD_ALL) {
+        if (kind != DSM_CLOUD_INACTIVE) select = DSM_CLOUD_SELECT_MATURE;
+        if (kind != DSM_CLOUD_ACTIVE) attached_runs(m, begin, count);
+        return true;
+    }
+    if (kind != DSM_CLOUD_NEIGHBOR) return false;
+    select = DSM_CLOUD_SELECT_NONZERO;
+    std::vector<int> neighbor_indexs;
+    get_driftfree_poses(m, m->last.relative_index, neighbor_indexs, 2 * m->cfg.drift_free_poses);
+    for (int this_pose : neighbor_indexs) {
+        if (m->local_surfels_indexs.count(this_pose)) continue;
+        const int sg = m->poses_database[(size_t)this_pose].segment;
+        if (sg < 0 || m->segments[(size_t)sg].count <= 0) continue;
+        begin.push_back(m->segments[(size_t)sg].begin);
+        count.push_back(m->segments[(size_t)sg].count);
+    }
+    return true;
 }
 
 } // namespace dsm_node

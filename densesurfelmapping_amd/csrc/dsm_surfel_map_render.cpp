@@ -27,23 +27,7 @@ int render(dsm_surfel_map *m, int kind, const dsm_render_camera *camera, const f
     if (!m->last.valid) return render_fail(m, DSM_E_STATE, "no frame fused yet");
     int select = DSM_CLOUD_SELECT_NONE;
     std::vector<int32_t> begin, count;
-    if (kind == DSM_CLOUD_ACTIVE || kind == DSM_CLOUD_INACTIVE || kind == DSM_CLOUD_ALL) {
-        if (kind != DSM_CLOUD_INACTIVE) select = DSM_CLOUD_SELECT_MATURE;
-        if (kind != DSM_CLOUD_ACTIVE) attached_runs(m, begin, count);
-    } else if (kind == DSM_CLOUD_NEIGHBOR) { // surfel_map.cpp:1292-1319
-        select = DSM_CLOUD_SELECT_NONZERO;
-        std::vector<int> neighbor_indexs;
-        get_driftfree_poses(m, m->last.relative_index, neighbor_indexs, 2 * m->cfg.drift_free_poses);
-        for (int this_pose : neighbor_indexs) {
-            if (m->local_surfels_indexs.count(this_pose)) continue;
-            const int sg = m->poses_database[(size_t)this_pose].segment;
-            if (sg < 0 || m->segments[(size_t)sg].count <= 0) continue;
-            begin.push_back(m->segments[(size_t)sg].begin);
-            count.push_back(m->segments[(size_t)sg].count);
-        }
-    } else {
-        return render_fail(m, DSM_E_INVALID, "render kind %d", kind);
-    }
+    if (!render_runs(m, kind, select, begin, count)) return render_fail(m, DSM_E_INVALID, "render kind %d", kind);
     dsm_render_camera own;
     if (!camera) { // the node's camera
         own.width = m->cfg.cam_width;

@@ -87,16 +87,26 @@ def read_log(path):
 EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-products -> SurfelMap(engine_flags=...)
 
 
-def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None):
-    """Feed a log to a SurfelMap on the GPU; returns a summary dict."""
+def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None, align=None):
+    """Feed a log to a SurfelMap on the GPU; returns a summary dict.  align = a cloud kind: after every fused frame that frame is
+    aligned against the surfels of that kind at the pose it was fused with (SurfelMap.align_last, the library's defaults) and a
+    JSON line says how it went; the poses fed to the map are not changed."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
     node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity,
                                 engine_flags=EIGEN_PRODUCTS[eigen_products])
     n = 0
     for ev in events:
+        fused = node.frames_fused
         node.feed(ev)
         n += 1
+        if align and node.frames_fused > fused:
+            a = node.align_last(align)
+            T = a["T"].astype(np.float64)
+            turn = 2.0 * np.arcsin(min(np.linalg.norm(T[:3, :3] - np.eye(3)) / np.sqrt(8.0), 1.0))
+            print(json.dumps({"frame": node.frames_fused, "align": align, "status": api.ALIGN_STATUS[a["status"]], "iterations": a["iterations"],
+                              "n_pixels": a["n_pixels"], "rms_m": a["rms"], "correction_m": float(np.linalg.norm(T[:3, 3])),
+                              "correction_deg": float(np.degrees(turn))}))
     out = {"messages": n, "frames_fused": node.frames_fused, "keyframes": node.pose_count,
            "active_surfels": int(len(node.local_surfels())), "inactive_surfels": int(len(node.inactive_cloud()))}
     if save_cloud:
@@ -119,6 +129,8 @@ def main():
     ap.add_argument("--save-mesh", help="ASCII PLY hexagon mesh (SurfelMap::save_mesh)")
     ap.add_argument("--save-mesh-binary", help="the same mesh as a binary little-endian PLY, vertices built on the GPU")
     ap.add_argument("--render", metavar="PATH.npz", help="depth, index, normal and intensity images of the whole map at the final fuse pose")
+    ap.add_argument("--align", metavar="KIND", choices=("active", "inactive", "all", "neighbor"),
+                    help="after every fused frame, align it against the surfels of this cloud kind and print status, iterations, pixels, rms and the size of the correction")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
                     help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
@@ -128,7 +140,7 @@ def main():
         cam = synth.KITTI_1226
         write_log(args.log, cam, 10, synth.node_messages(cam, synth.Scene(), args.synth, lap=120))
     print(json.dumps(replay(args.log, args.save_cloud, args.save_mesh, device=args.device, eigen_products=args.eigen_products,
-                            save_mesh_binary=args.save_mesh_binary, render=args.render)))
+                            save_mesh_binary=args.save_mesh_binary, render=args.render, align=args.align)))
 
 
 if __name__ == "__main__":

@@ -24,6 +24,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_depth_input_u16", "dsm_surfel_map_image_input_color",
     "dsm_surfel_map_get_mesh", "dsm_surfel_map_get_mesh_device", "dsm_surfel_map_save_mesh_binary",
     "dsm_surfel_map_render", "dsm_surfel_map_render_device",
+    "dsm_surfel_map_align_last", "dsm_surfel_map_last_pose16",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -97,6 +98,10 @@ def _bind(lib):
         if hasattr(lib, "dsm_surfel_map_render"):  # (nor the renderer)
             for name in ("dsm_surfel_map_render", "dsm_surfel_map_render_device"):
                 getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._RenderCamera), _vp, C.c_uint32, C.POINTER(api._RenderPlanes), _vp]
+        if hasattr(lib, "dsm_surfel_map_align_last"):  # (nor the alignment)
+            lib.dsm_surfel_map_align_last.argtypes = [_vp, C.c_int, _vp, C.POINTER(api._AlignParams), C.POINTER(api._AlignResult)]
+        if hasattr(lib, "dsm_surfel_map_last_pose16"):
+            lib.dsm_surfel_map_last_pose16.argtypes = [_vp, _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -235,6 +240,26 @@ class SurfelMap:
             return n.value
         out["n_surfels"] = n.value
         return out
+
+    # ---- the latest frame against the map (dsm_align_frame)
+    def align_last(self, kind="active", pose_guess=None, params=None):
+        """The depth frame of the latest fuse aligned, point to plane, against the surfels of cloud `kind` ("active" / "inactive" /
+        "all" / "neighbor" or CLOUD_*) seen by the node's camera at `pose_guess` (4x4 cam -> world or 16 column-major floats; None:
+        the pose of the latest fuse).  params: api.align_params' forms.  Returns api.align_result's dict; nothing is changed."""
+        g = None
+        if pose_guess is not None:
+            g = np.asarray(pose_guess, np.float32)
+            g = api.pose_to_colmajor(g) if g.shape == (4, 4) else np.ascontiguousarray(g.reshape(16))
+        p = api.align_params(params)
+        r = api._AlignResult()
+        self._check(self._lib.dsm_surfel_map_align_last(self._h, self._kind(kind), None if g is None else _ptr(g), C.byref(p), C.byref(r)))
+        return api.align_result(r)
+
+    def last_pose(self) -> np.ndarray:
+        """the pose of the latest fuse as the engine was given it: 4x4 float32, cam -> world (align_last's and render's default)"""
+        p = np.zeros(16, np.float32)
+        self._check(self._lib.dsm_surfel_map_last_pose16(self._h, _ptr(p)))
+        return p.reshape(4, 4).T.copy()
 
     # ---- taps
     @property

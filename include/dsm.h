@@ -306,6 +306,75 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
                        const dsm_render_camera *camera, const float *pose16, const float *pose_inv16, uint32_t flags,
                        const dsm_render_planes *planes, int dst_on_device, int32_t *n_surfels);
 
+/* ---- a depth frame against the map: projective association and point-to-plane alignment (no counterpart in the reference) ----
+ * What dsm_render_compose predicts for a camera (the MODEL camera: depth plane Zm, camera-frame normal plane Nm) is compared with
+ * the depth plane of a frame slot, whichever upload wrote it.  T is a rigid transform from the frame camera to the model camera,
+ * 16 column-major floats.  One EVALUATION visits the frame pixels (u, v) with u % stride == 0 and v % stride == 0 (never a pad
+ * column); fp32, non-fused, in the order written:
+ *   1. d = depth[v][u]; skip unless near_dist < d < far_dist (the handle's; d finite)
+ *   2. p = (((u - cx) / fx) d, ((v - cy) / fy) d, d)              3. q = R p + t as ((a0 x + a1 y) + a2 z) + a3
+ *   4. skip unless near_m < q.z < far_m and |q|^2 <= qmax^2, qmax = far_m times the length of the most oblique ray one pixel
+ *      outside the model image
+ *   5. um = int((q.x fx_m) / q.z + cx_m + 0.5), vm likewise (the + 0.5 in double, truncating: the fuse kernel's rounding); skip
+ *      unless inside the model image          6. zm = Zm[vm][um]; skip unless zm > 0
+ *   7. n = Nm[vm][um]; skip unless 0.5 <= |n|^2 <= 2
+ *   8. pm = (((um - cx_m) / fx_m) zm, ((vm - cy_m) / fy_m) zm, zm), e = q - pm; skip unless |e|^2 <= dist_max^2
+ *   9. skip unless (n . q)^2 >= min_view_cos^2 |q|^2
+ *  10. in double, from those floats: r = n . e, J = (n, q x n), w = 1 or, with huber > 0, w = |r| <= huber ? 1 : huber / |r|
+ * and adds to 29 sums: the 21 upper-triangle entries of w J J^T row by row, the 6 of w J r, w r^2, and the count.  Every term
+ * but the count enters as llrint(term * 2^scale_log2) (round to nearest even) into an int64: integer addition is associative, so
+ * the sums are the same bits whatever the launch geometry and the order of the atomics.  scale_log2 is the largest value <= 40
+ * for which no sum can leave int64 for this model camera and this many sampled pixels (csrc/dsm_align.h derives the bound); a
+ * camera that leaves less than 10 is refused.
+ * The LOOP (dsm_align_frame) renders the map at pose16_guess once, starts from T = I and repeats: evaluate; fewer than min_pixels
+ * pixels: TOO_FEW; solve A xi = -b (double, LDL^T in a fixed order; a pivot not > 1e-9 trace(A): SINGULAR), xi = (v, omega);
+ * T <- [Rodrigues(omega) R, Rodrigues(omega) t + v] (kept in double, cast to float for each evaluation); |v| < stop_translation and
+ * |omega| < stop_rotation: CONVERGED; max_iterations steps taken: MAX_ITERATIONS.  One last evaluation at the final estimate gives
+ * n_pixels, rms = sqrt(sum w r^2 / count) and the sums reported.  pose16 = pose16_guess . T, a double product cast to float. */
+typedef enum {
+    DSM_ALIGN_CONVERGED = 0,
+    DSM_ALIGN_MAX_ITERATIONS = 1,
+    DSM_ALIGN_TOO_FEW = 2,
+    DSM_ALIGN_SINGULAR = 3
+} dsm_align_status;
+typedef struct dsm_align_params {
+    uint32_t struct_size;   /* sizeof(dsm_align_params) */
+    int32_t max_iterations; /* >= 1; default 10 */
+    int32_t stride;         /* >= 1; default 2: a quarter of the pixels */
+    float dist_max;         /* metres, in (0, qmax]; default 0.25 */
+    float min_view_cos;     /* in [0, 1]; default 0.2 */
+    float huber;            /* metres, >= 0, 0 = every weight 1; default 0.05 */
+    int32_t min_pixels;     /* default 200 */
+    float stop_translation; /* metres; default 1e-4 */
+    float stop_rotation;    /* radians; default 1e-4 */
+} dsm_align_params;
+#define DSM_ALIGN_SUMS 29
+typedef struct dsm_align_result {
+    float pose16[16];  /* the refined cam -> world pose */
+    float T16[16];     /* the correction: frame camera -> the camera at pose16_guess */
+    int32_t status;    /* dsm_align_status */
+    int32_t iterations; /* steps taken */
+    int32_t n_pixels;  /* pixels that passed in the last evaluation */
+    int32_t scale_log2;
+    double rms;        /* of the last evaluation; 0 when n_pixels is 0 */
+    int64_t sums[DSM_ALIGN_SUMS]; /* of the last evaluation */
+} dsm_align_result;
+void dsm_align_params_init(dsm_align_params *p);
+/* One evaluation against the caller's DEVICE planes (model_depth_dev [height][width] floats, model_normal_dev [height][width][3],
+ * tight, as dsm_render_compose writes them for model_cam), read behind the work enqueued on the null stream so far.  The 29
+ * device words are cleared on the handle's stream before every evaluation and come back through page-locked memory.
+ * Checked before any device work (DSM_E_INVALID, outputs untouched): slot out of range, a camera dsm_render_compose would refuse
+ * or one that leaves scale_log2 < 10, a non-finite T16 entry, struct_size, stride < 1, dist_max not in (0, qmax], min_view_cos
+ * outside [0, 1], huber negative or not finite, max_iterations < 1.  Synchronises. */
+int dsm_align_equations(dsm_handle *h, int slot, const dsm_render_camera *model_cam, const void *model_depth_dev, const void *model_normal_dev,
+                        const float *T16, const dsm_align_params *params, int64_t *sums /* 29 */, int32_t *scale_log2);
+/* The loop, against the surfel sequence of dsm_render_compose(select, runs) rendered at pose16_guess (two-sided, the closed-form
+ * inverse) into scratch of the handle (allocated at the first call).  model_cam NULL = the handle's camera and fuse distances.
+ * The checks of dsm_align_equations and of dsm_render_compose (run bounds, non-finite pose) come before any device work; *result
+ * is written only on DSM_OK.  The map, the store and the frame are not changed.  Synchronises. */
+int dsm_align_frame(dsm_handle *h, int slot, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                    const dsm_render_camera *model_cam, const float *pose16_guess, const dsm_align_params *params, dsm_align_result *result);
+
 /* Copy a frame into frame slot `slot` (0 .. frame_slots-1 of the config) and return when it is there (the host
  * buffers may be reused).  By default the copy is ordered behind everything enqueued so far.  With
  * DSM_FLAG_UPLOAD_STREAM it runs on the handle's upload stream instead: it waits only for the enqueued frames that

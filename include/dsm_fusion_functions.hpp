@@ -124,6 +124,26 @@ class FusionFunctions {
         return check(rc, h_);
     }
 
+    // A depth frame against the map (dsm_align_* of dsm.h, where the alignment is defined).  The frame is the one in frame slot
+    // `slot` of the resident path (dsm_frame_upload & co. on handle()); pose_guess is the cam -> world matrix the map is rendered at.
+    static dsm_align_params align_params() {
+        dsm_align_params p;
+        dsm_align_params_init(&p);
+        return p;
+    }
+    // one evaluation against the caller's device planes: the 29 sums and their scale
+    int align_equations(int slot, const dsm_render_camera &model_cam, const void *model_depth_dev, const void *model_normal_dev, const float *T16,
+                        const dsm_align_params &params, int64_t *sums, int32_t *scale_log2) {
+        return check(dsm_align_equations(h_, slot, &model_cam, model_depth_dev, model_normal_dev, T16, &params, sums, scale_log2), h_);
+    }
+    // the loop, against the surfels of dsm_render_compose(select, runs); model_cam nullptr: the handle's camera
+    template <typename Pose>
+    int align_frame(int slot, int select, const std::vector<int32_t> &store_begin, const std::vector<int32_t> &store_count,
+                    const dsm_render_camera *model_cam, const Pose &pose_guess, const dsm_align_params &params, dsm_align_result &result) {
+        const size_t n = store_begin.size() < store_count.size() ? store_begin.size() : store_count.size();
+        return check(dsm_align_frame(h_, slot, select, (int32_t)n, store_begin.data(), store_count.data(), model_cam, pose_guess.data(), &params, &result), h_);
+    }
+
     dsm_handle *handle() const { return h_; }
 
   private:

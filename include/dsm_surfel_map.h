@@ -171,6 +171,17 @@ int dsm_surfel_map_render(dsm_surfel_map *m, int kind, const dsm_render_camera *
 int dsm_surfel_map_render_device(dsm_surfel_map *m, int kind, const dsm_render_camera *camera, const float *pose16, uint32_t flags,
                                  const dsm_render_planes *planes_device, int32_t *n_surfels);
 
+/* ---- the latest frame against the map (dsm_align_frame of dsm.h, where the alignment is defined) ----
+ * Aligns the depth frame of the latest fuse, still in its engine slot, against the surfel set of `kind` with the rules and runs of
+ * dsm_surfel_map_render (ACTIVE: refine or judge a pose; INACTIVE: verify a loop closure against the inactive map), seen by the
+ * node's own camera at pose16_guess (cam -> world, 16 column-major floats; NULL: the pose of the latest fuse).  DSM_CLOUD_RAW and
+ * unknown kinds: DSM_E_INVALID.  DSM_E_STATE before the first fuse.  The map, the store and the frame are not changed: what to do
+ * with the refined pose is the caller's decision.  Synchronises. */
+int dsm_surfel_map_align_last(dsm_surfel_map *m, int kind, const float *pose16_guess, const dsm_align_params *params, dsm_align_result *result);
+/* The pose of the latest fuse as the engine was given it (cam -> world, 16 column-major floats): the guess and the render pose
+ * that NULL stands for above.  fuse_pose of a publication is the same pose as a quaternion.  DSM_E_STATE before the first fuse. */
+int dsm_surfel_map_last_pose16(const dsm_surfel_map *m, float *pose16);
+
 /* ---- taps (what the publish_* methods read) ---- */
 dsm_handle *dsm_surfel_map_engine(dsm_surfel_map *m); /* active map: dsm_map_size / dsm_map_download */
 int64_t dsm_surfel_map_frames_fused(const dsm_surfel_map *m);

@@ -228,6 +228,20 @@ class SurfelMap {
         return rc;
     }
 
+    // the frame of the latest fuse aligned, point to plane, against the surfels of cloud `kind` seen from pose16_guess (cam -> world,
+    // column-major; nullptr: the latest fuse's pose): dsm_align_frame of dsm.h.  params nullptr: dsm_align_params_init's defaults.
+    // Nothing is changed: what to do with result.pose16 is the caller's decision.
+    int align_last(dsm_cloud_kind kind, const float *pose16_guess, const dsm_align_params *params, dsm_align_result &result) {
+        dsm_align_params own;
+        if (!params) {
+            dsm_align_params_init(&own);
+            params = &own;
+        }
+        return check(dsm_surfel_map_align_last(m_, kind, pose16_guess, params, &result));
+    }
+    // the pose of the latest fuse, cam -> world, 16 column-major floats: align_last's default guess
+    int last_pose16(float *pose16) { return check(dsm_surfel_map_last_pose16(m_, pose16)); }
+
     // the point-cloud topics (publish_*_pointcloud, surfel_map.cpp:1115-1151, 1283-1454): xyzi = 4 floats per point
     int get_cloud(dsm_cloud_kind kind, std::vector<float> &xyzi) {
         int32_t n = 0;
