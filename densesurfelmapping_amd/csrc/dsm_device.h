@@ -71,8 +71,8 @@ struct DeviceCtx {
     // 16 bits per pixel (label_t: a frame has at most kMaxSeeds = 65 535 superpixels, kNoLabel = the reference's -1): the label
     // image is read by every stage of a frame, by the window walks several times over -- a third of a frame's memory-side
     // traffic when it was 4 bytes per pixel
-    label_t *label; // [h][pitch] superpixel index of every pixel: every sweep's image in turn (k_apply_labels works in place), then the final one
-    label_t *cand;  // [h][pitch] seed picked by this sweep before the stable-skip rule is applied
+    label_t *label; // [h][pitch] superpixel index of every pixel: every sweep's image in turn (k_assign and k_resolve work in place), then the final one
+    label_t *cand;  // [h][pitch] seed picked by this sweep, at the pixels on `worklist` only (whose old seed was stable at sweep start)
     float4 *core;   // [S] x, y, mean_intensity, mean_depth  (live seed state during the sweeps)
     double *inv_depth; // [S] 1.0 / mean_depth, FF.cpp:380
     float4 *core_stage; // [S] update_seeds output before the chunk-commit rule
@@ -81,7 +81,7 @@ struct DeviceCtx {
     // otherwise the first pixel key (row-major) at which an evaluated pixel picked the seed.
     int32_t *tmin;
     int32_t *first_empty; // [kSweeps][kWorkers] first unstable seed without pixels, per worker chunk
-    int32_t *worklist;    // pixel keys whose old and new seeds were both stable at sweep start
+    int32_t *worklist;    // pixel keys whose old seed was stable at sweep start and which picked another one
     int32_t *work_count;
     int32_t fit_small_cap;  // kFitSmallCap, or less (dsm_debug_set_fit_small_cap: lets a test push ordinary groups through the other tier)
     int32_t *fit_big_count; // groups of seeds queued in `worklist` for the full-length tier of k_seed_fit (batched launches)

@@ -1,4 +1,4 @@
-// dsm_k_superpixel.h -- the superpixel sweeps: k_init_seeds, k_assign, k_resolve, k_apply_labels, k_update_seeds (lane and
+// dsm_k_superpixel.h -- the superpixel sweeps: k_init_seeds, k_assign, k_resolve, k_update_seeds (lane and
 // wave forms, k_update_seeds_rest), k_commit_seeds.  FF.cpp:364-629.  Included by dsm_kernels.hip.
 #pragma once
 #include "dsm_k_common.h"
@@ -167,8 +167,9 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_init_seeds_lanes(
 // ------------------------------------------------------------------------------ assign
 // One thread per column of FOUR pixels (a 4 x 4 quadrant of a cell shares its <= 2 x 2 candidate seeds: they are fetched
 // once per thread), a 64x16-pixel tile per block; the <=10x4 seeds a tile can pick from are staged in LDS.  FIRST sweep:
-// every pixel is evaluated (all labels 0, seed 0 unstable) so the pick is the label.  Later sweeps: the pick goes to
-// `cand`, and the sequential skip rule is resolved through tmin (see k_resolve).
+// every pixel is evaluated (all labels 0, seed 0 unstable) so the pick is the label.  Later sweeps: the pick is the label
+// at once where the pixel's old seed was unstable at sweep start (nearly everywhere); the few other picks go to `cand` and
+// onto a list, and the sequential skip rule is resolved through tmin (see k_resolve).
 constexpr int kTileW = 64, kTileCellsX = kTileW / kCell + 2;
 template <int COLS> struct AssignTile { // COLS pixels per thread: 4 in launches batched over many handles, 1 where latency counts
     static constexpr int kH = 4 * COLS, kCellsY = (kH + kCell - 1) / kCell + 2;
@@ -179,23 +180,68 @@ template <int COLS> struct AssignTile { // COLS pixels per thread: 4 in launches
 // picks.  With T[s] = first pixel key at which s is cleared this reads
 //     evaluated(p)  <=>  T[label(p)] < p ,      T[s] = min { p : evaluated(p), pick(p) = s } ,
 // whose least fixed point from above (T = -1 for unstable seeds, +inf for stable ones) is reached
-// by repeated atomicMin.  Every pixel whose seed was unstable applies its own atomicMin directly;
-// only pixels whose old and new seeds were both stable (a short list: borders between two seeds
-// that stopped moving) can still change the picture; k_resolve iterates that list to the fixed point.
-__device__ void resolve_worklist(const DeviceCtx *c, const label_t *label_in) {
+// by repeated atomicMin, and the sweep's label image is  new(p) = T[old(p)] < p ? pick(p) : old(p).
+// A pixel whose old seed was unstable at sweep start (T = -1, for the whole sweep) is evaluated whatever
+// happens elsewhere: k_assign applies its atomicMin and stores its pick as its label on the spot.  A pixel
+// whose old seed was stable keeps its label unless it picks another seed AND its old seed is cleared
+// before the scan reaches it: k_assign leaves its label alone, puts the pick into `cand` and the pixel
+// onto the list (a short one: with image noise a handful of seeds are stable; in a quiet scene the borders
+// between seeds that stopped moving).  Here ONE workgroup iterates that list to the fixed point -- only an
+// entry whose picked seed was stable too can still lower a T, the others cost a test per pass -- and then walks
+// it once more to store the picks that count.  A listed pixel's label is touched by nothing before that walk, and
+// there only by its own entry.
+// A thread holds its first kResolveHeld entries (pixel, old label, pick) in registers: a list of up to 2 048 pixels is
+// read once, a pass over it is ONE round trip to tmin for all of a thread's entries together, and the walk needs none:
+// the pass that ended the loop changed nothing, so what it read of tmin is final.  Longer lists: the rest entry by entry.
+constexpr int kResolveHeld = 8;
+__device__ void resolve_worklist(const DeviceCtx *c, label_t *label) {
     const int n = c->work_count[0];
     if (n == 0) return;
+    const int tid = threadIdx.x;
+    int p[kResolveHeld], l[kResolveHeld], pk[kResolveHeld]; // (p = -1: no entry; its seeds 0 are read and never used)
+    bool ev[kResolveHeld];
+#pragma unroll
+    for (int k = 0; k < kResolveHeld; k++) p[k] = tid + k * 256 < n ? c->worklist[tid + k * 256] : -1;
+#pragma unroll
+    for (int k = 0; k < kResolveHeld; k++) {
+        l[k] = p[k] >= 0 ? (int)label[p[k]] : 0; // (both seeds of a listed pixel exist)
+        pk[k] = p[k] >= 0 ? (int)c->cand[p[k]] : 0;
+    }
     for (;;) {
         int changed = 0;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const int p = c->worklist[i];
-            const int l = label_in[p], pk = c->cand[p]; // (both seeds of a listed pixel exist)
-            if (load_coherent(&c->tmin[l]) < p && load_coherent(&c->tmin[pk]) > p) {
-                atomicMin(&c->tmin[pk], p);
+        int tl[kResolveHeld], tp[kResolveHeld];
+#pragma unroll
+        for (int k = 0; k < kResolveHeld; k++) {
+            if (k * 256 >= n) break; // (the same for the whole workgroup)
+            tl[k] = load_coherent(&c->tmin[l[k]]);
+            tp[k] = load_coherent(&c->tmin[pk[k]]);
+        }
+#pragma unroll
+        for (int k = 0; k < kResolveHeld; k++) {
+            ev[k] = k * 256 < n && p[k] >= 0 && tl[k] < p[k];
+            if (ev[k] && tp[k] > p[k]) {
+                atomicMin(&c->tmin[pk[k]], p[k]);
+                changed = 1;
+            }
+        }
+        for (int i = tid + kResolveHeld * 256; i < n; i += 256) {
+            const int q = c->worklist[i];
+            const int lq = label[q], pq = c->cand[q];
+            if (load_coherent(&c->tmin[lq]) < q && load_coherent(&c->tmin[pq]) > q) {
+                atomicMin(&c->tmin[pq], q);
                 changed = 1;
             }
         }
         if (!__syncthreads_or(changed)) break;
+    }
+    // (the barrier above: every atomicMin of this workgroup, the only one at work on tmin by now, was issued before the last pass)
+#pragma unroll
+    for (int k = 0; k < kResolveHeld; k++)
+        if (ev[k]) label[p[k]] = (label_t)pk[k];
+    for (int i = tid + kResolveHeld * 256; i < n; i += 256) {
+        const int q = c->worklist[i];
+        const int lq = label[q];
+        if (load_coherent(&c->tmin[lq]) < q) label[q] = c->cand[q];
     }
 }
 
@@ -243,25 +289,30 @@ template <bool FIRST, bool BATCH, int COLS> __global__ __launch_bounds__(256) vo
     __syncthreads();
     // what becomes of a pixel once its pick is known (FF.cpp:442-451 and the stable-skip bookkeeping, see resolve_worklist).
     // tl = tmin of the pixel's old seed (-1 never changes; >= 0 only moves among values >= 0: it may be read at any time),
-    // tp = tmin of the picked seed, read coherently after the pick was known.
+    // tp = tmin of the picked seed, read coherently after the pick was known.  The label plane is updated IN PLACE: a
+    // thread reads it at the pixels it settles and nowhere else, and every pixel is settled once.
     auto settle = [&](int p, int l, int pick, int tl, int tp) {
         if (pick < 0) { // every candidate cost >= the reference's 1e6 sentinel: it would index seeds[-1]
             atomicOr(c->status, kStatusBadPick);
-            if (FIRST) label_put(c->label, (unsigned)p, 0); else label_put(c->cand, (unsigned)p, l);
+            if (FIRST) label_put(c->label, (unsigned)p, 0); // (a later sweep: the pixel keeps its label)
         } else if (FIRST) {
             label_put(c->label, (unsigned)p, pick);
-        } else {
+        } else if (tl == -1) {
+            // the old seed was unstable at sweep start: this pixel is evaluated whatever happens
+            // elsewhere, so its pick is its label and loses `stable` no later than at p
+            if (pick != l) label_put(c->label, (unsigned)p, pick);
+            if (tp > p) atomicMin(&c->tmin[pick], p);
+        } else if (pick != l) {
+            // the old seed was stable at sweep start: whether this pixel is evaluated depends on the
+            // scan order -- k_resolve decides (slot_elems entries: room for every pixel)
+            // (one atomic per wave for the lanes that are here together: in a quiet scene they are many)
             label_put(c->cand, (unsigned)p, pick);
-            if (tl == -1) {
-                // the old seed was unstable at sweep start: this pixel is evaluated whatever happens
-                // elsewhere, so its pick loses `stable` no later than at p
-                if (tp > p) atomicMin(&c->tmin[pick], p);
-            } else if (pick != l && tp != -1) {
-                // old and new seed both stable at sweep start: whether this pixel is evaluated depends
-                // on the scan order -- resolved below
-                const int slot = atomicAdd(c->work_count, 1);
-                c->worklist[slot] = p;
-            }
+            const unsigned long long m = __ballot(true);
+            const int rk = rank_below(m);
+            int base = 0;
+            if (rk == 0) base = atomicAdd(c->work_count, __popcll(m));
+            base = __builtin_amdgcn_readlane(base, __ffsll((long long)m) - 1);
+            c->worklist[base + rk] = p;
         }
     };
     auto tmin_of = [&](int s) { // tmin[s] by a 32-bit offset from the uniform base, coherently (other workgroups lower it)
@@ -303,7 +354,7 @@ template <bool FIRST, bool BATCH, int COLS> __global__ __launch_bounds__(256) vo
             pick[r] = fpk.seed;
             sure[r] = fpk.sure;
             // ragged border beyond every cell's reach: label -1, once per frame (no later stage changes these pixels:
-            // every seed window ends before them, and k_apply_labels keeps a -1)
+            // every seed window ends before them, and such a pixel is never settled)
             if (FIRST && y < h && !live[r]) label_put(c->label, p0 + (unsigned)(r * pitch), -1);
         }
         // ---- a pixel the filter leaves open goes onto the tile's list: the reference's typed arithmetic is several hundred
@@ -354,7 +405,7 @@ template <bool FIRST, bool BATCH, int COLS> __global__ __launch_bounds__(256) vo
     }
 }
 
-// One workgroup iterates the worklist to the fixed point.  (Folding this into k_assign behind a
+// One workgroup iterates the worklist to the fixed point and stores the listed pixels' labels.  (Folding this into k_assign behind a
 // "last block done" ticket costs a device-scope release per workgroup -- an L2 write-back on this
 // multi-XCD part -- and was 10x slower than the extra launch.)
 template <bool BATCH> __global__ __launch_bounds__(256) void k_resolve(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch, int sweep) {
@@ -436,8 +487,8 @@ __device__ __forceinline__ float huber_passes_wave(const float *dl, float *lt, i
 // so member depths are compacted in order into LDS and summed sequentially.
 constexpr int kWin = 2 * kCell; // 16
 
-// The label image of a sweep >= 1 is  new(p) = T[old(p)] < p ? pick(p) : old(p)  (see k_assign): k_apply_labels forms it,
-// once per pixel and in place, before the seeds are updated.
+// The label image of a sweep >= 1 is  new(p) = T[old(p)] < p ? pick(p) : old(p)  (see resolve_worklist): k_assign and
+// k_resolve have formed it, in place, before the seeds are updated.
 // Second half of update_seeds for one seed (one wave): the sums of its members are in the lanes' registers, the
 // member depths > 0.1 in window row-major order in dl[0..nd).
 __device__ __forceinline__ void update_seed_finish(const DeviceCtx *__restrict__ c, int sweep, int s, int lane, int wx0, int wy0,
@@ -536,57 +587,6 @@ __device__ __forceinline__ void update_seed_wave(const DeviceCtx *__restrict__ c
     update_seed_finish(c, sweep, s, lane, wx0, wy0, old, dl, lt, cnt, sdx, sdy, si, nd);
 }
 
-// ---- the label image of a sweep >= 1, one thread per eight pixels of a row (16 bytes of each plane):  new(p) = T[old(p)] < p ? pick(p) : old(p)
-// with T = tmin after k_resolve (see k_assign), IN PLACE: a pixel's new label needs nothing but its own old one, and most
-// pixels keep theirs -- only quads in which a label changes are stored.  Until round 4 every seed's window walk formed
-// the new labels on the fly for the 256 pixels of its window -- every pixel four times over, each time behind a gather of
-// tmin[old label] by 64 lanes that hold 64 different seeds -- and the registers of that (two more row planes, the
-// gathered tmin) held the lane-per-seed kernel to one wave per SIMD.  Here a pixel is resolved once, and neighbouring
-// pixels mostly share their old label: a wave's gather touches a handful of lines.  Pixels beyond every cell's reach keep
-// their -1 (no seed, no tmin).
-// A thread takes the eight pixels of kApplyRows consecutive rows; tmin is fetched only for a pixel whose pick differs from its
-// label (the others keep theirs whatever tmin says: from the second sweep on that is nearly all of them).
-constexpr int kApplyRows = 2;
-template <bool BATCH> __global__ __launch_bounds__(256) void k_apply_labels(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch, int sweep) {
-    const BlockOf blk = block_of<BATCH>();
-    DeviceCtx batch_ctx;
-    if (BATCH) batch_ctx = load_ctx(batch + blk.z);
-    const DeviceCtx *__restrict__ c = BATCH ? &batch_ctx : &ctx;
-    const int pitch = c->pitch;
-    const int xq = blk.x * 64 + (threadIdx.x & 63), y0 = (blk.y * 4 + (threadIdx.x >> 6)) * kApplyRows;
-    if (8 * xq >= pitch || y0 >= c->h) return;
-    uint4 lab[kApplyRows], cd[kApplyRows];
-#pragma unroll
-    for (int r = 0; r < kApplyRows; r++) {
-        const int key0 = __mul24(min(y0 + r, c->h - 1), pitch) + 8 * xq; // (a row past the image: the last row again, not stored)
-        lab[r] = ld_vec<uint4>(c->label, (unsigned)key0 << 1);
-        cd[r] = ld_vec<uint4>(c->cand, (unsigned)key0 << 1);
-    }
-#pragma unroll
-    for (int r = 0; r < kApplyRows; r++) {
-        if (y0 + r >= c->h) break;
-        const int key0 = __mul24(y0 + r, pitch) + 8 * xq;
-        const unsigned lw[4] = {lab[r].x, lab[r].y, lab[r].z, lab[r].w}, cw[4] = {cd[r].x, cd[r].y, cd[r].z, cd[r].w};
-        unsigned l[8], pk[8], o[8];
-        int t[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            l[j] = (j & 1) ? lw[j >> 1] >> 16 : lw[j >> 1] & 0xffffu;
-            pk[j] = (j & 1) ? cw[j >> 1] >> 16 : cw[j >> 1] & 0xffffu;
-            t[j] = (l[j] != (unsigned)kNoLabel && pk[j] != l[j]) ? ld_off(c->tmin, l[j] << 2) : kIntMax;
-        }
-        bool changed = false;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            o[j] = t[j] < key0 + j ? pk[j] : l[j];
-            changed = changed || o[j] != l[j];
-        }
-        if (changed)
-            *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(c->label) + ((unsigned)key0 << 1)) =
-                make_uint4(o[0] | o[1] << 16, o[2] | o[3] << 16, o[4] | o[5] << 16, o[6] | o[7] << 16);
-    }
-}
-
 // One Huber-Newton pass (FF.cpp:536-553) of up to 64 seeds at once, one chain per lane: a = ordered sum of 2*r over the
 // Huber core, +-hr (added in double) per tail element; returns the Newton step -a / (b + 10), b = 2 * (core elements).
 // fetch(i) = element i of this lane's list (i is wave-uniform; any value beyond the list's end); lim = the list's
@@ -659,8 +659,9 @@ __device__ __forceinline__ float huber_pass_regs(const float (&v)[kRestRegs], in
 // ordered depth sum in registers, compacts its member depths in order into its own LDS row ([element][lane]:
 // conflict-free whatever the lanes' list lengths), and runs the first Huber-Newton pass as 64 independent chains: one
 // v_add serves 64 seeds.  Same operations on the same operands in the same order as the reference, seed by seed.  The
-// label image it reads is the sweep's own (k_apply_labels): 170 registers, two waves per SIMD where the form that
-// applied the labels inside the walk (round 3: two more row planes, a gathered tmin per pixel) held one.
+// label image it reads is the sweep's own (k_assign stores it in place, k_resolve the few pixels that wait for the fixed
+// point): 170 registers, two waves per SIMD where the form that applied the labels inside the walk (round 3: two more
+// row planes, a gathered tmin per pixel) held one.
 // What the first Huber pass does not finish goes to k_update_seeds_rest through two queues: the 13 % of the seeds that
 // need more passes, packed 64 to a wave again, and the seeds whose list does not fit the 123 depths a lane keeps in LDS (a
 // superpixel averages 53, the longest of 64 neighbours ~95; 0.05 % of all seeds have more), which get a wave

@@ -4,8 +4,8 @@
 // surfel_fusion/src/surfel_map.cpp of the reference):
 //   k_init_seeds    initialize_seeds_kernel          FF.cpp:577-629
 //   k_assign        update_pixels_kernel             FF.cpp:389-453 (+ calculate_cost 364-387)
-//   k_resolve       the sequential `stable` skip rule of FF.cpp:400,445,450 as a fixed point
-//   k_update_seeds  update_seeds_kernel              FF.cpp:468-562 (+ the new label image of the sweep)
+//   k_resolve       the sequential `stable` skip rule of FF.cpp:400,445,450 as a fixed point (+ the labels that depend on it)
+//   k_update_seeds  update_seeds_kernel              FF.cpp:468-562
 //   k_commit_seeds  the early `return` of FF.cpp:516-517 (per worker chunk)
 //   k_pixel_normals calculate_pixels_norms_kernel (the normals that are read)   FF.cpp:664-712
 //   k_seed_stats    calculate_spaces / calculate_sp_depth_norms up to the fit's starting point
@@ -89,7 +89,6 @@ static hipError_t launch_frame_as(const DeviceCtx &hc, int map_upper_bound, int 
     const bool lanes = batched && n_batch >= (lanes_from > 0 ? lanes_from : kLaneBatch);
     const dim3 g_tile1((hc.w + kTileW - 1) / kTileW, (hc.h + AssignTile<1>::kH - 1) / AssignTile<1>::kH);
     const dim3 g_tile4((hc.w + kTileW - 1) / kTileW, (hc.h + AssignTile<4>::kH - 1) / AssignTile<4>::kH);
-    const dim3 g_row8((hc.pitch / 8 + 63) / 64, (hc.h + 3) / 4); // thread per eight pixels of a row, 512 x 4 per block
     if (ev) hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, st, 40000LL); // 400 us
     DSM_MARK();
     if (lanes) hipLaunchStage(k_init_seeds_lanes<true>, k_init_seeds_lanes<true>, g_seed_thr, dim3(256));
@@ -104,8 +103,7 @@ static hipError_t launch_frame_as(const DeviceCtx &hc, int map_upper_bound, int 
             if (lanes) hipLaunchStage((k_assign<false, true, 4>), (k_assign<false, true, 4>), g_tile4, dim3(256), sweep);
             else hipLaunchStage((k_assign<false, false, 1>), (k_assign<false, true, 1>), g_tile1, dim3(256), sweep);
             DSM_MARK();
-            hipLaunchStage(k_resolve<false>, k_resolve<true>, dim3(1), dim3(256), sweep);
-            hipLaunchStage(k_apply_labels<false>, k_apply_labels<true>, dim3(g_row8.x, (hc.h + 4 * kApplyRows - 1) / (4 * kApplyRows)), dim3(256), sweep); // (part of the resolve stage: the sweep's label image)
+            hipLaunchStage(k_resolve<false>, k_resolve<true>, dim3(1), dim3(256), sweep); // (the fixed point, then the labels that waited for it)
             DSM_MARK();
         }
         if (lanes) {

@@ -579,9 +579,10 @@ int dsm_seed_count(const dsm_handle *h);
  * ABI 3 notes for users of these taps:
  *  - there is ONE label image, updated in place from sweep to sweep; `which` = 0 and 1 both name it (the sweeps used to take
  *    turns between two buffers, and old callers pass `sweep & 1`);
- *  - a sweep >= 1 is the PAIR assign_k + resolve_k (stages 4-5 and 8-9): assign leaves its picks in a side plane and
- *    resolve rewrites the label image from them.  Re-running assign_k alone after its resolve_k reads the already updated
- *    image and does not reproduce the sweep: inject the pre-sweep image (dsm_debug_set_label_buffer) and run the pair;
+ *  - a sweep >= 1 is the PAIR assign_k + resolve_k (stages 4-5 and 8-9): assign rewrites the label image where a pixel's
+ *    old superpixel was not stable and leaves the other picks in a side plane; resolve stores those of them that count.
+ *    Re-running assign_k alone reads the already updated image and does not reproduce the sweep: inject the pre-sweep
+ *    image (dsm_debug_set_label_buffer) and run the pair;
  *  - dsm_debug_set_label_buffer checks the image: every entry a superpixel index of this grid, and -1 exactly at the pixels
  *    beyond every cell's reach (image sizes with (size mod 8) > 4), where the assignment stage itself writes -1 --
  *    DSM_E_INVALID otherwise (the kernels index per-seed arrays with the labels they read). */
