@@ -1315,6 +1315,7 @@ int dsm_create(const dsm_config *cfg, dsm_handle **out) {
         q.fit_small_cap = kFitSmallCap;
         CREATE_TRY(dev_alloc(h, &q.cur, 1));
         CREATE_TRY(dev_alloc(h, &q.rest_list, (size_t)((c.n_seed + 63) / 64) * kRestListCap * 64));
+        CREATE_TRY(dev_alloc(h, &q.inl_mask, (size_t)((c.n_seed + 63) / 64) * (2 * kCell) * 64)); // whole groups of 64: the lanes past the last seed own a slot
         if ((cfg->flags & DSM_FLAG_WAVE_STAMPS) && kWaveStamps) CREATE_TRY(dev_alloc(h, &q.stamps, (size_t)5 * c.n_seed * 8));
         q.params = h->d_params;
         if (np > 1) CREATE_TRY(hipEventRecord(pp.ev_map, h->stream)); // "buffers free"

@@ -89,6 +89,12 @@ struct DeviceCtx {
                             // seeds that need more Huber passes | seeds whose depth list outgrew its LDS row
     float *rest_list;       // [ceil(S / 64)][kRestListCap][64] depth lists of the queued seeds, entry-major within a group of 64
     GnHeader *gn_hdr; // [S]
+    // [ceil(S / 64)][16][64] which pixels of window row r are depth inliers of seed 64 g + l (bit j = window column j, window_pixel
+    // of dsm_math.h): inl_mask[g][r][l], group-major so that a wave of k_seed_stats stores 128 contiguous bytes per row.  Written by
+    // k_seed_stats for every seed of the frame, read by the k_seed_fit that follows it (sixteen lanes per seed, one row each) instead
+    // of the labels.  Rows of seed s are valid iff gn_hdr[s].m_in > 0: a seed without a plane keeps whatever an earlier frame or its
+    // own rejected walk left.  k_seed_points does not write it; the fit behind it derives its inliers itself.
+    uint16_t *inl_mask;
     float4 *plane;    // [S] the plane k_seed_fit fitted (normal, offset: before plane_finish), for k_seed_finish
     float *normals;   // [h][pitch][3] forward-difference normal of every depth inlier of its own superpixel (k_pixel_normals); other entries stale, never read
     dsm_seed *seeds; // [S] final seed table, reference layout

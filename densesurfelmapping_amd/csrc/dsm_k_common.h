@@ -140,6 +140,7 @@ __device__ __forceinline__ DeviceCtx load_ctx(const DeviceCtx *src) {
     DSM_G(rest_count);
     DSM_G(rest_list);
     DSM_G(gn_hdr);
+    DSM_G(inl_mask);
     DSM_G(normals);
     DSM_G(plane);
     DSM_G(seeds);

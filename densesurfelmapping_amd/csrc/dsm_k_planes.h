@@ -65,6 +65,7 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_seed_points(const
     // ---- members with depth > 0.05, and the superpixel radius (FF.cpp:813-838)
     int n = 0;
     float far2 = 0.0f;
+    const float md = core.w;
     int lab[4];
     float pd[4];
     const int x0 = wx0 + (lane & (kWin - 1)), y0 = wy0 + (lane >> 4);
@@ -82,7 +83,8 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_seed_points(const
     for (int k = 0; k < 4; k++) {
         const int idx = k * 64 + lane;
         const int x = wx0 + (idx & (kWin - 1)), y = wy0 + (idx >> 4);
-        const bool mem = lab[k] == s;
+        const WindowPixel px = window_pixel(true, true, lab[k] == s, pd[k], md, hr_above); // (lab: -1 outside the image)
+        const bool mem = px.member;
         float d = 0.0f;
         if (mem) {
             d = pd[k];
@@ -90,7 +92,7 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_seed_points(const
             const float d2 = ex * ex + ey * ey;
             if (d2 > far2) far2 = d2;
         }
-        const bool ok = mem && d > flt_below(0.05); // (double)d > 0.05
+        const bool ok = px.has_depth;
         const unsigned long long m = __ballot(ok);
         if (ok) {
             const int pos = n + rank_below(m);
@@ -107,7 +109,6 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_seed_points(const
     wave_priority(n); // long lists first: they are the kernel's critical path
     if (n >= 16) { // FF.cpp:841
         // ---- depth inliers: their pixel normals and back-projected points, in order (FF.cpp:846-861)
-        const float md = core.w;
         int m_in = 0;
         for (int base = 0; base < n; base += 64) {
             const int i = base + lane;
@@ -126,8 +127,7 @@ template <bool BATCH> __global__ __launch_bounds__(256) void k_seed_points(const
                 }
                 rx0 = ld_off(c->ray_x, (unsigned)x << 2); rx1 = ld_off(c->ray_x, ((unsigned)x << 2) + 4u);
                 ry0 = ld_off(c->ray_y, (unsigned)y << 2); ry1 = ld_off(c->ray_y, ((unsigned)y << 2) + 4u);
-                const float r = md - d;
-                ok = fabsf(r) < hr_above; // (double)r < hr && (double)r > -hr
+                ok = window_pixel(true, true, true, d, md, hr_above).inlier; // (a list entry is a member with depth)
             }
             const unsigned long long m = __ballot(ok);
             if (ok) {
@@ -253,7 +253,7 @@ template <bool BATCH> __global__ __launch_bounds__(64) void k_seed_stats(const D
     const DeviceCtx *__restrict__ c = BATCH ? &batch_ctx : &ctx;
     // which pixels of every window row are depth inliers of the lane's seed (bit j = window column j): found by the first
     // walk, and all the second walk needs to know -- it fetches normals only for the quads that hold one and no labels at all
-    __shared__ unsigned short s_inl[kWin + 2][64];
+    __shared__ __attribute__((aligned(16))) unsigned short s_inl[kWin + 2][64];
     const int lane = lane_id();
     const int S = c->n_seed;
     const int s = (((S + 63) >> 6) - 1 - blk.x) * 64 + lane; // bottom rows first, see seed_of_block
@@ -316,13 +316,12 @@ template <bool BATCH> __global__ __launch_bounds__(64) void k_seed_stats(const D
         unsigned bits = 0u;
 #pragma unroll
         for (int j = 0; j < kWin; j++) {
-            const bool mem = comp(A.lab[j >> 2], j & 3) == s_row && col_in[j];
-            const float d2 = exx[j] + eyy;
-            far2 = fmaxf(far2, mem ? d2 : 0.0f);               // FF.cpp:820-824, over all members
             const float d = comp(A.dp[j >> 2], j & 3);
-            const bool ok = mem && d > flt_below(0.05);        // (double)d > 0.05
-            n += ok ? 1 : 0;
-            const bool inl = ok && fabsf(md - d) < hr_above;    // (double)r < hr && (double)r > -hr
+            const WindowPixel px = window_pixel(true, col_in[j], comp(A.lab[j >> 2], j & 3) == s_row, d, md, hr_above); // (s_row: no seed in a row outside the image)
+            const float d2 = exx[j] + eyy;
+            far2 = fmaxf(far2, px.member ? d2 : 0.0f);         // FF.cpp:820-824, over all members
+            n += px.has_depth ? 1 : 0;
+            const bool inl = px.inlier;
             m_in += inl ? 1 : 0;
             bits |= inl ? 1u << j : 0u;
             sx += inl ? rx[j] * d : 0.0f;                       // back_project (FF.cpp:91-97), summed in window order (FF.cpp:111-116)
@@ -361,6 +360,15 @@ template <bool BATCH> __global__ __launch_bounds__(64) void k_seed_stats(const D
     }
     float nx = 0.0f, ny = 0.0f, nz = 0.0f;
     wave_lds_sync();
+    // ---- the masks are also what k_seed_fit gathers its points by: the window's sixteen rows of s_inl are the wave's 2 KB of
+    // c->inl_mask as they stand ([group][row][lane]), copied out in two 16-byte stores per lane.  The plane holds whole groups of
+    // 64, so the slots of lanes past the last seed are the wave's own; which rows mean anything is in the header (m_in > 0).
+    {
+        uint4 *const dst = reinterpret_cast<uint4 *>(c->inl_mask + (size_t)((((S + 63) >> 6) - 1 - blk.x) * kWin) * 64);
+        const uint4 *src = reinterpret_cast<const uint4 *>(&s_inl[0][0]);
+#pragma unroll
+        for (int t = 0; t < kWin * 64 * 2 / (64 * 16); t++) st_off(dst, (unsigned)(t * 64 + lane) << 4, src[t * 64 + lane]);
+    }
     if (__ballot(fit) != 0) {
         // ---- second walk: the normals of the depth inliers, in window order (k_pixel_normals left zero where an inlier
         // has no normal).  A lane fetches the twelve floats of a quad only if the quad holds one of its inliers: on
@@ -541,7 +549,9 @@ template <int TIER> struct FitShape {
 };
 
 // the group of seeds s0 .. s0+3 on one wave
-template <int TIER> __device__ __forceinline__ void fit_group(const DeviceCtx *__restrict__ c, int s0,
+// masks: the stage before was k_seed_stats, which left every seed's inlier row masks in c->inl_mask (launch_frame knows);
+// otherwise (k_seed_points) the lanes derive their rows' inliers from labels and depths themselves.  Wave-uniform.
+template <int TIER> __device__ __forceinline__ void fit_group(const DeviceCtx *__restrict__ c, int s0, bool masks,
                                                              float (*s_col)[kFitCols][FitShape<TIER>::kStride], float *s_ones,
                                                              double (*s_solver)[52], float4 *s_plane) {
     constexpr int kChunks = FitShape<TIER>::kChunks;
@@ -558,10 +568,11 @@ template <int TIER> __device__ __forceinline__ void fit_group(const DeviceCtx *_
     hd.m_in = 0;
     float4 core = make_float4(0, 0, 0, 0);
     // Everything a lane will want from memory is asked for at once, before anything is waited for: the seed's header, and
-    // this lane's window row (labels, depths, the rays of the sixteen columns) for the gather below -- whether the seed has
+    // this lane's window row (its inlier mask or its labels, depths, the rays of the sixteen columns) for the gather below -- whether the seed has
     // a list at all is in the header, but a wave of this kernel lives as long as its round trips take (a third of a
     // wave's life was waiting: for the header, then for the rows, then for one ray per inlier column, each in turn).
-    LabelQuad row_lab[4];
+    LabelQuad row_lab[4] = {};
+    unsigned row_mask = 0u, row_o4[4];
     float4 row_dp[4];
     float row_rx[kWin], row_ry = 0.0f;
     int wx0 = 0;
@@ -576,7 +587,7 @@ template <int TIER> __device__ __forceinline__ void fit_group(const DeviceCtx *_
     const int xcol = kFitX[gl], ycol = kFitY[gl], h_row = kFitRow[gl], h_col = kFitColI[gl];
     if (live) {
         hd = c->gn_hdr[s];
-        core = c->core[s];
+        if (masks) row_mask = ld_off(c->inl_mask, ((((unsigned)s >> 6) * kWin + (unsigned)gl) << 7) + (((unsigned)s & 63u) << 1));
         const float *dep = frame_depth(c, fp);
         const int w = c->w, h = c->h, pitch = c->pitch;
         int gx, gy;
@@ -590,8 +601,13 @@ template <int TIER> __device__ __forceinline__ void fit_group(const DeviceCtx *_
         for (int q = 0; q < 4; q++) { // window quads redirected into the row where they leave it (masked below)
             const int xq = wx0 + 4 * q;
             const unsigned o4 = (row + (unsigned)(xq < 0 ? 0 : (xq > pitch - 4 ? pitch - 4 : xq))) << 2;
-            row_lab[q] = label_quad(c->label, o4 >> 2);
             row_dp[q] = ld_vec<float4>(dep, o4);
+            row_o4[q] = o4;
+        }
+        if (!masks) { // no masks from the stage before: the row's labels and the seed's mean depth, for window_pixel below
+            core = c->core[s];
+#pragma unroll
+            for (int q = 0; q < 4; q++) row_lab[q] = label_quad(c->label, row_o4[q] >> 2);
         }
 #pragma unroll
         for (int j = 0; j < kWin; j++) {
@@ -629,15 +645,16 @@ template <int TIER> __device__ __forceinline__ void fit_group(const DeviceCtx *_
         }
         wave_lds_sync();
         if (m > 0) {
-            const int w = c->w;
-            const float md = core.w;
-            unsigned inl = 0; // this row's inliers, bit j = window column j
+            unsigned inl = row_mask; // this row's inliers, bit j = window column j: as k_seed_stats found them (valid, since m > 0)
+            if (!masks) {             // ... or worked out here, behind k_seed_points
+                const int w = c->w;
+                const float md = core.w;
 #pragma unroll
-            for (int j = 0; j < kWin; j++) {
-                const float d = comp(row_dp[j >> 2], j & 3);
-                const bool ok = row_in && (unsigned)(wx0 + j) < (unsigned)w && comp(row_lab[j >> 2], j & 3) == (unsigned)s && d > flt_below(0.05) &&
-                                fabsf(md - d) < hr_above;
-                inl |= ok ? 1u << j : 0u;
+                for (int j = 0; j < kWin; j++) {
+                    const float d = comp(row_dp[j >> 2], j & 3);
+                    const bool ok = window_pixel(row_in, (unsigned)(wx0 + j) < (unsigned)w, comp(row_lab[j >> 2], j & 3) == (unsigned)s, d, md, hr_above).inlier;
+                    inl |= ok ? 1u << j : 0u;
+                }
             }
             // where this row's points start in the seed's list: exclusive prefix of the row counts over the group's 16 lanes
             const int cnt = __popc(inl);
@@ -875,7 +892,7 @@ template <bool BATCH, bool E33 = false> __global__ __launch_bounds__(256) void k
     c->seed_weight[s] = depth_weight(out.mean_depth); // FF.cpp:274: what a surfel fusing into this seed weighs it with
 }
 
-template <bool BATCH, int TIER> __global__ __launch_bounds__(64) void k_seed_fit(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch) {
+template <bool BATCH, int TIER> __global__ __launch_bounds__(64) void k_seed_fit(const DeviceCtx ctx, const DeviceCtx *__restrict__ batch, int from_stats) {
     const BlockOf blk = block_of<BATCH>();
     DeviceCtx batch_ctx;
     if (BATCH) batch_ctx = load_ctx(batch + blk.z);
@@ -884,15 +901,16 @@ template <bool BATCH, int TIER> __global__ __launch_bounds__(64) void k_seed_fit
     __shared__ __attribute__((aligned(16))) float s_ones[8];
     __shared__ double s_solver[kFitSeeds][52]; // per seed: [16] damped H | [12] 2x2 dets | [16] inverse | [4] J | [4] update
     __shared__ float4 s_plane[kFitSeeds];      // per seed: the plane of the step being taken
+    const bool masks = BATCH && TIER != kFitAll && from_stats != 0; // (one handle: always behind k_seed_points)
     if (TIER == kFitLarge) {
         const int n_big = c->fit_big_count[0];
         for (int e = blk.x; e < n_big; e += kFitLargeBlocks) {
-            fit_group<TIER>(c, c->worklist[e] * kFitSeeds, s_col, s_ones, s_solver, s_plane);
+            fit_group<TIER>(c, c->worklist[e] * kFitSeeds, masks, s_col, s_ones, s_solver, s_plane);
             wave_lds_sync();
         }
     } else {
         const int n_groups = (c->n_seed + kFitSeeds - 1) / kFitSeeds;
-        fit_group<TIER>(c, (n_groups - 1 - blk.x) * kFitSeeds, s_col, s_ones, s_solver, s_plane); // bottom rows (long lists) first, see seed_of_block
+        fit_group<TIER>(c, (n_groups - 1 - blk.x) * kFitSeeds, masks, s_col, s_ones, s_solver, s_plane); // bottom rows (long lists) first, see seed_of_block
     }
 }
 

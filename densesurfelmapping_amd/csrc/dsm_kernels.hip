@@ -123,8 +123,12 @@ static hipError_t launch_frame_as(const DeviceCtx &hc, int map_upper_bound, int 
         hipLaunchStage(k_seed_points<false>, k_seed_points<true>, g_seed_wave, dim3(256));
     }
     DSM_MARK();
-    hipLaunchStage((k_seed_fit<false, kFitAll>), (k_seed_fit<true, kFitSmall>), dim3((S + kFitSeeds - 1) / kFitSeeds), dim3(64));
-    if (batched) hipLaunchStage((k_seed_fit<false, kFitAll>), (k_seed_fit<true, kFitLarge>), dim3(kFitLargeBlocks), dim3(64));
+    // the fit takes its inliers from the row masks k_seed_stats left (c->inl_mask) exactly where that kernel ran just before it: the
+    // lane forms.  Behind k_seed_points -- one handle (k_seed_fit<false, kFitAll>), or a batched launch below the lane threshold
+    // (the same two tier kernels) -- it derives them itself.  Both tiers of a launch read the same way.
+    const int fit_masks = lanes ? 1 : 0;
+    hipLaunchStage((k_seed_fit<false, kFitAll>), (k_seed_fit<true, kFitSmall>), dim3((S + kFitSeeds - 1) / kFitSeeds), dim3(64), fit_masks);
+    if (batched) hipLaunchStage((k_seed_fit<false, kFitAll>), (k_seed_fit<true, kFitLarge>), dim3(kFitLargeBlocks), dim3(64), fit_masks);
     hipLaunchStage((k_seed_finish<false, E33>), (k_seed_finish<true, E33>), g_seed_thr, dim3(256));
     DSM_MARK();
     // grid-stride over the map with no more workgroups than the device holds at once (the ones that start late would run

@@ -378,6 +378,23 @@ DSM_HD float huber_mean_depth(const float *list, int n, float sum, double huber)
     return md;
 }
 
+// ------------------------------------------- a window pixel against its seed, FF.cpp:811-850
+// What calculate_sp_depth_norms asks of one pixel of a seed's 16 x 16 window, in the order it asks: is it a member of the
+// superpixel (in the image, and labelled with the seed: FF.cpp:816-818, counts for the radius), has it a depth (FF.cpp:827, the
+// count the 16-member rule uses), is that depth an inlier of the seed's mean depth (FF.cpp:849-850: the points and normals of
+// the plane fit).  hr_above = flt_above(HUBER_RANGE); a NaN depth or mean depth is no inlier.  The one statement of the
+// predicate: k_seed_stats publishes it as row masks, k_seed_points and the fit that follows it evaluate it themselves.
+struct WindowPixel {
+    bool member, has_depth, inlier;
+};
+DSM_HD WindowPixel window_pixel(bool row_in, bool col_in, bool label_is_seed, float d, float mean_depth, float hr_above) {
+    WindowPixel p;
+    p.member = row_in && col_in && label_is_seed;
+    p.has_depth = p.member && d > flt_below(0.05);                      // (double)d > 0.05
+    p.inlier = p.has_depth && fabsf(mean_depth - d) < hr_above;         // (double)r < hr && (double)r > -hr
+    return p;
+}
+
 // ------------------------------------------------------------- back-projection, FF.cpp:91-97
 DSM_HD void back_project(const Intrinsics &k, float u, float v, float d, float &x, float &y, float &z) {
     x = (u - k.cx) / k.fx * d;
