@@ -48,6 +48,9 @@ struct Emu {
     // cached inverse is reused), [1] of them with all four Jacobian sums provably exact in any order, [2] of those, sums that
     // differ from the ordered sums all the same (must be 0)
     long long cert_stats[3] = {0, 0, 0};
+    // k_seed_fit's other two branches: [0] steps 2..5 whose class mask is non-empty and unchanged (the mask comparison lets the
+    // cached inverse stand), [1] steps 2..5 that qualify for the free-order sums, fail the exactness test and take the ordered sums
+    long long branch_stats[2] = {0, 0};
     long long exact_operand_pass = 0; // steps 2..5 that pass the cheaper OPERAND-level test: range(r) + range(p_a) + 1 <= 21 for every a
     long long fast_total = 0, fast_unsure = 0, fast_mismatches = 0, fast_checked = 0, fast_bound_violations = 0; // pick_seed_fast
     long long unsure_by_sweep[kSweeps] = {0, 0, 0};
@@ -298,6 +301,7 @@ void seed_planes(Emu &e) {
                     bool all_core = true;
                     for (int i = 0; i < m; i++) all_core = all_core && cls[i] == 0;
                     if (all_core) e.exact_stats[4]++;
+                    if (it > 0 && !all_core && same) e.branch_stats[0]++;
                     bool sums_ok = all_core; // every sum of this step spans <= 21 binades
                     for (int lane = 0; lane < 20; lane++) {
                         const bool is_j = lane >= 16;
@@ -367,6 +371,8 @@ void seed_planes(Emu &e) {
                         if (exact) {
                             e.cert_stats[1]++;
                             if (memcmp(Jt, acc + 16, sizeof Jt) != 0) e.cert_stats[2]++;
+                        } else {
+                            e.branch_stats[1]++;
                         }
                     }
                     gn_step(acc, acc + 16, nx, ny, nz, nb);
@@ -484,6 +490,14 @@ int emu_tolerance_is_fp32(void *p) {
 }
 void emu_set_order_salt(void *p, int salt) { ((Emu *)p)->order_salt = salt; }
 void emu_cert_stats(void *p, long long *out) { for (int i = 0; i < 3; i++) out[i] = ((Emu *)p)->cert_stats[i]; }
+// the Huber classes of the fit so far: out[0] seeds with a residual outside the core at step 1, [1] fitted seeds, [2] seeds whose
+// classes change after step 1, [3] steps 2..5 with a change, [4] steps 2..5 with a non-empty mask unchanged (the cached inverse is
+// reused after the mask comparison), [5] steps 2..5 where the exactness test fails and the ordered sums run
+void emu_fit_class_stats(void *p, long long *out) {
+    Emu &e = *(Emu *)p;
+    out[0] = e.gn_first_noncore; out[1] = e.gn_seeds; out[2] = e.gn_seeds_mask_changed; out[3] = e.gn_steps_mask_changed;
+    out[4] = e.branch_stats[0]; out[5] = e.branch_stats[1];
+}
 void emu_exact_sum_stats(void *p, long long *out) { for (int i = 0; i < 5; i++) out[i] = ((Emu *)p)->exact_stats[i]; out[5] = ((Emu *)p)->exact_operand_pass; }
 // pick_seed_fast over every pixel assigned so far: out[24] (12..14: undecided picks by sweep; 7: seeds with a non-core residual at step 1; 8..11: fitted seeds, seeds with a class change after step 1, steps 2..5, steps with a change);
 // out[0..7] = [pixels, unsure, answered differently from pick_seed, costs checked,

@@ -33,8 +33,9 @@ def _same_frame(tag, api, ff, want):
     assert not bad, f"{tag}: surfels differ {bad}"
 
 
-def _handle(api, cam, fr, depth=1, flags=0, fit_small_cap=None):
-    ff = api.FusionFunctions.from_camera(cam, frame_slots=len(fr), surfel_capacity=1 << 16, pipeline_depth=depth, flags=flags)
+def _handle(api, cam, fr, depth=1, flags=0, fit_small_cap=None, constants=None):
+    ff = api.FusionFunctions.from_camera(cam, frame_slots=len(fr), surfel_capacity=1 << 16, pipeline_depth=depth, flags=flags,
+                                         constants=constants)
     if fit_small_cap is not None:
         ff.debug_set_fit_small_cap(fit_small_cap)
     for t, (img, dep, _, _) in enumerate(fr):
@@ -47,12 +48,12 @@ def _plan(api, fr):
     return api.FusionFunctions.pack_replay(list(range(len(fr))), [f[3] for f in fr], np.stack([f[2] for f in fr]))
 
 
-def _lockstep(api, cam, runs, want, tag, flags=0, fit_small_cap=None):
+def _lockstep(api, cam, runs, want, tag, flags=0, fit_small_cap=None, constants=None):
     """the handles of `runs` as ONE batch, a frame at a time, every handle against its oracle after every frame; -> tier counts"""
     n = len(runs[0])
     handles, batch = [], None
     try:
-        handles = [_handle(api, cam, fr, flags=flags, fit_small_cap=fit_small_cap) for fr in runs]
+        handles = [_handle(api, cam, fr, flags=flags, fit_small_cap=fit_small_cap, constants=constants) for fr in runs]
         plans = [_plan(api, fr) for fr in runs]
         batch = api.Batch(handles)
         tiers = []
