@@ -72,6 +72,8 @@ ABI_SYMBOLS = (
     "dsm_render_compose",
     # a depth frame against the rendered map: one evaluation of the normal equations, and the point-to-plane loop
     "dsm_align_params_init", "dsm_align_equations", "dsm_align_frame",
+    # the map as an occupancy voxel grid with inflation and a cell list
+    "dsm_grid_spec_init", "dsm_grid_spec_around", "dsm_grid_compose", "dsm_grid_inflate",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -155,6 +157,11 @@ MESH_SURFEL_BYTES = {MESH_VERTEX_REF6: 144, MESH_VERTEX_XYZ_RGBA8: 96}
 RENDER_CULL_BACKFACES = 1
 RENDER_PLANES = ("depth", "index", "normal", "intensity")
 RENDER_PLANE_TYPES = {"depth": (np.float32, ()), "index": (np.int32, ()), "normal": (np.float32, (3,)), "intensity": (np.uint8, ())}
+# dsm_grid_compose (include/dsm.h): its flag, its planes in the order of dsm_grid_planes, the largest grid and inflation radius
+GRID_CELLS_OF_INFLATED = 1
+GRID_PLANES = ("occupied", "inflated", "index", "cells")
+GRID_MAX_VOXELS = 1 << 28
+GRID_MAX_INFLATE = 16
 
 
 # dsm_align_status, and the layout of the 29 sums (include/dsm.h)
@@ -188,6 +195,15 @@ class _RenderPlanes(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("index", C.c_void_p), ("normal", C.c_void_p), ("intensity", C.c_void_p)]
 
 
+class _GridSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("origin", C.c_float * 3), ("voxel", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("inflate", C.c_int32)]
+
+
+class _GridPlanes(C.Structure):
+    _fields_ = [("occupied", C.c_void_p), ("inflated", C.c_void_p), ("index", C.c_void_p), ("cells", C.c_void_p), ("cells_cap", C.c_int32)]
+
+
 class _AlignParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_iterations", C.c_int32), ("stride", C.c_int32), ("dist_max", C.c_float),
                 ("min_view_cos", C.c_float), ("huber", C.c_float), ("min_pixels", C.c_int32), ("stop_translation", C.c_float),
@@ -219,6 +235,75 @@ def align_result(r: _AlignResult) -> dict:
     return {"pose": np.array(r.pose16, np.float32).reshape(4, 4).T.copy(), "T": np.array(r.T16, np.float32).reshape(4, 4).T.copy(),
             "status": r.status, "iterations": r.iterations, "n_pixels": r.n_pixels, "rms": r.rms, "scale_log2": r.scale_log2,
             "sums": np.array(r.sums, np.int64)}
+
+
+def grid_spec(origin=(0.0, 0.0, 0.0), voxel=0.1, dims=(1, 1, 1), inflate=0) -> _GridSpec:
+    """a dsm_grid_spec: the low corner of voxel (0, 0, 0), the edge in metres, (nx, ny, nz), the inflation radius in voxels.
+    Nothing is checked here: the library does."""
+    g = _GridSpec()
+    load_library().dsm_grid_spec_init(C.byref(g))
+    g.origin[:] = [float(v) for v in origin]
+    g.voxel = float(voxel)
+    g.nx, g.ny, g.nz = (int(v) for v in dims)
+    g.inflate = int(inflate)
+    return g
+
+
+def grid_spec_around(centre, voxel=0.1, dims=(64, 64, 32), inflate=0) -> _GridSpec:
+    """dsm_grid_spec_around: a grid of `dims` voxels around `centre` on the lattice of multiples of `voxel`, so that grids taken
+    around successive poses share one lattice"""
+    g = grid_spec(voxel=voxel, dims=dims, inflate=inflate)
+    c = (C.c_float * 3)(*(float(v) for v in centre))
+    load_library().dsm_grid_spec_around(C.byref(g), c, float(voxel), *(int(v) for v in dims))
+    return g
+
+
+def grid_shapes(spec):
+    """(words per row, the shape of a bit set, the shape of the index plane) of a dsm_grid_spec"""
+    wx = (spec.nx + 31) // 32
+    return wx, (spec.nz, spec.ny, wx), (spec.nz, spec.ny, spec.nx)
+
+
+def grid_unpack(bits, nx) -> np.ndarray:
+    """a bit set [nz, ny, wx] uint32 as a bool array [nz, ny, nx]"""
+    b = np.ascontiguousarray(bits, np.uint32)
+    x = np.arange(nx)
+    return ((b[..., x >> 5] >> (x & 31).astype(np.uint32)) & 1).astype(bool)
+
+
+def grid_cell_centres(spec, cells) -> np.ndarray:
+    """the voxel centres (n, 3) float32 of the linear indices `cells`: the voxel-down-sampled cloud, with the definition's arithmetic"""
+    c = np.asarray(cells, np.int64)
+    ijk = np.stack([c % spec.nx, c // spec.nx % spec.ny, c // (spec.nx * spec.ny)], 1)
+    o, v = np.array(spec.origin[:], np.float32), np.float32(spec.voxel)
+    return (o[None, :] + (ijk.astype(np.float32) + np.float32(0.5)) * v).astype(np.float32)
+
+
+def grid_outputs(spec, planes, dst_ptrs, cells_cap):
+    """(the dsm_grid_planes struct, the numpy arrays behind it or None for device pointers)"""
+    unknown = set(planes) - set(GRID_PLANES) if dst_ptrs is None else set(dst_ptrs) - set(GRID_PLANES)
+    if unknown:
+        raise ValueError("no such grid plane: %s" % sorted(unknown))
+    st = _GridPlanes()
+    st.cells_cap = 0 if cells_cap is None else int(cells_cap)
+    if dst_ptrs is not None:
+        for k, p in dst_ptrs.items():
+            setattr(st, k, p)
+        return st, None
+    # (a size the library will refuse still gets arrays to point at: the refusal is the library's to make)
+    nx, ny, nz = (min(max(int(v), 1), 1 << 10) for v in (spec.nx, spec.ny, spec.nz))
+    ok = 1 <= spec.nx and 1 <= spec.ny and 1 <= spec.nz and spec.nx * spec.ny * spec.nz <= GRID_MAX_VOXELS
+    if ok:
+        nx, ny, nz = spec.nx, spec.ny, spec.nz
+    out = {}
+    for k in GRID_PLANES:
+        if k in planes:
+            if k == "cells":
+                out[k] = np.zeros(max(st.cells_cap, 1), np.int32)
+            else:
+                out[k] = np.zeros((nz, ny, nx) if k == "index" else (nz, ny, (nx + 31) // 32), np.int32 if k == "index" else np.uint32)
+            setattr(st, k, out[k].ctypes.data)
+    return st, out
 
 
 def render_camera(cam) -> _RenderCamera:
@@ -317,6 +402,12 @@ def load_library():
     lib.dsm_mesh_indices.argtypes = [_vp, C.c_int32, _vp, C.c_int]
     lib.dsm_render_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_RenderCamera), _vp, _vp, C.c_uint32, C.POINTER(_RenderPlanes),
                                        C.c_int, _vp]
+    lib.dsm_grid_spec_init.argtypes = [C.POINTER(_GridSpec)]
+    lib.dsm_grid_spec_init.restype = None
+    lib.dsm_grid_spec_around.argtypes = [C.POINTER(_GridSpec), _vp, C.c_float, C.c_int32, C.c_int32, C.c_int32]
+    lib.dsm_grid_spec_around.restype = None
+    lib.dsm_grid_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_GridSpec), C.c_uint32, C.POINTER(_GridPlanes), C.c_int, _vp, _vp]
+    lib.dsm_grid_inflate.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
     lib.dsm_align_params_init.argtypes = [C.POINTER(_AlignParams)]
     lib.dsm_align_params_init.restype = None
     lib.dsm_align_equations.argtypes = [_vp, C.c_int, C.POINTER(_RenderCamera), _vp, _vp, _vp, C.POINTER(_AlignParams), _vp, _vp]
@@ -650,6 +741,44 @@ class FusionFunctions:
             return n.value
         out["n_surfels"] = n.value
         return out
+
+    # ---- the map as a voxel grid -------------------------------------------------------------------
+    def grid(self, select, segs, spec, flags=0, planes=("occupied", "inflated", "cells"), dst_ptrs=None, cells_cap=None):
+        """dsm_grid_compose: the surfel sequence of render(select, segs) as an occupancy grid `spec` (grid_spec / grid_spec_around).
+        Returns a dict of the `planes` asked for -- "occupied" and "inflated" uint32 [nz, ny, wx] bit sets (bit x & 31 of word
+        x >> 5; grid_unpack gives bools), "index" int32 [nz, ny, nx] (the lowest surfel number covering the voxel, -1), "cells"
+        int32 [n_cells] (the linear indices of the set voxels, of `inflated` with GRID_CELLS_OF_INFLATED; grid_cell_centres gives
+        points) -- plus "n_surfels" and "n_cells".  cells_cap None: the list is sized by a second call when the first reports
+        more cells than fit.  With dst_ptrs = {plane: device pointer} the planes named there are written on the device (cells
+        needs cells_cap) and (n_surfels, n_cells) is returned.  More cells than cells_cap: DsmError with code DSM_E_CAPACITY and
+        .n_cells = the count needed."""
+        seg = np.ascontiguousarray(np.asarray(segs, np.int32).reshape(-1, 2))
+        b = np.ascontiguousarray(seg[:, 0]) if len(seg) else np.zeros(1, np.int32)
+        c = np.ascontiguousarray(seg[:, 1]) if len(seg) else np.zeros(1, np.int32)
+        n, nc = C.c_int32(0), C.c_int32(0)
+        auto = dst_ptrs is None and cells_cap is None and "cells" in planes
+        st, out = grid_outputs(spec, planes, dst_ptrs, 4096 if auto else cells_cap)
+        rc = self._lib.dsm_grid_compose(self._h, select, len(seg), _ptr(b), _ptr(c), C.byref(spec), flags, C.byref(st), 0 if dst_ptrs is None else 1,
+                                        C.byref(n), C.byref(nc))
+        if rc == DSM_E_CAPACITY and auto:
+            st, out = grid_outputs(spec, planes, None, nc.value)
+            rc = self._lib.dsm_grid_compose(self._h, select, len(seg), _ptr(b), _ptr(c), C.byref(spec), flags, C.byref(st), 0, C.byref(n), C.byref(nc))
+        if rc == DSM_E_CAPACITY:
+            e = DsmError(rc, self._lib.dsm_last_error(self._h).decode())
+            e.n_cells, e.n_surfels, e.planes = nc.value, n.value, out
+            raise e
+        self._check(rc)
+        if dst_ptrs is not None:
+            return n.value, nc.value
+        if "cells" in out:
+            out["cells"] = out["cells"][: nc.value]
+        out["n_surfels"], out["n_cells"] = n.value, nc.value
+        return out
+
+    def grid_inflate(self, dims, radius, src_ptr, dst_ptr):
+        """dsm_grid_inflate: the inflation alone on a bit set [nz, ny, wx] in device memory (pointers, e.g. torch data_ptr()):
+        dst = src dilated by the voxels within `radius`; dims = (nx, ny, nz)"""
+        self._check(self._lib.dsm_grid_inflate(self._h, int(dims[0]), int(dims[1]), int(dims[2]), int(radius), _vp(src_ptr), _vp(dst_ptr)))
 
     # ---- a depth frame against the rendered map -----------------------------------------------------
     def align_equations(self, slot, model_cam, model_depth_ptr, model_normal_ptr, T, params=None):

@@ -168,7 +168,7 @@ struct dsm_handle {
     std::vector<void *> allocs; // every hipMalloc of this handle
     std::vector<hipGraphExec_t> retired; // graphs replaced while possibly in flight (map_grows): destroyed at the next synchronisation point
     FrameParams *h_params = nullptr; // pinned staging ring
-    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size; [64..127] the device's scalar block as it came
+    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size, [6] grid cells; [64..127] the device's scalar block as it came
     int32_t *d_scalars = nullptr;    // the device's scalar block (64 ints: n_local @8, n_local_next @16, n_new @24, n_holes @32, status @48, delta count @56)
     FrameParams *d_params = nullptr;
     uint8_t *d_stage_img = nullptr; // one tightly packed frame on its way into a pitched slot
@@ -268,6 +268,12 @@ struct dsm_handle {
     size_t render_px = 0;
     void *d_render_splats = nullptr;
     size_t render_seq = 0;
+    // dsm_grid_compose: grow-only device scratch, none before the first grid -- the surfel records (grid_seq surfels), and the
+    // planes the caller did not pass or passed as host memory with the cell list's scan counts behind them (grid_bytes bytes)
+    void *d_grid_splats = nullptr;
+    size_t grid_seq = 0;
+    void *d_grid_planes = nullptr;
+    size_t grid_bytes = 0;
     // dsm_align_equations / dsm_align_frame: none before the first call -- the 29 sums on the device and their page-locked landing
     // place, and (dsm_align_frame, grow-only) the rendered model planes: align_px depths, then 3 * align_px normal components
     unsigned long long *d_align_sums = nullptr;
@@ -1400,6 +1406,8 @@ void dsm_destroy(dsm_handle *h) {
     if (h->ev_pub_dst) (void)hipEventDestroy(h->ev_pub_dst);
     if (h->d_render_keys) (void)hipFree(h->d_render_keys);
     if (h->d_render_splats) (void)hipFree(h->d_render_splats);
+    if (h->d_grid_splats) (void)hipFree(h->d_grid_splats);
+    if (h->d_grid_planes) (void)hipFree(h->d_grid_planes);
     if (h->d_align_sums) (void)hipFree(h->d_align_sums);
     if (h->d_align_planes) (void)hipFree(h->d_align_planes);
     if (h->h_align_sums) (void)hipHostFree(h->h_align_sums);
@@ -2142,6 +2150,167 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
         if (planes->normal) HIP_TRY(h, hipMemcpy(planes->normal, o_normal, 3 * px * sizeof(float), hipMemcpyDeviceToHost));
         if (planes->intensity) HIP_TRY(h, hipMemcpy(planes->intensity, o_int, px, hipMemcpyDeviceToHost));
     }
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ the map as a voxel grid (dsm_k_grid.h)
+
+namespace {
+
+int grid_reserve(dsm_handle *h, size_t seq, size_t bytes) {
+    if (seq > h->grid_seq) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_grid_splats) (void)hipFree(h->d_grid_splats);
+        h->d_grid_splats = nullptr;
+        h->grid_seq = 0;
+        const size_t want = seq + seq / 4 + 64;
+        HIP_TRY(h, hipMalloc(&h->d_grid_splats, want * sizeof(GridSplat)));
+        h->grid_seq = want;
+    }
+    if (bytes > h->grid_bytes) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_grid_planes) (void)hipFree(h->d_grid_planes);
+        h->d_grid_planes = nullptr;
+        h->grid_bytes = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        HIP_TRY(h, hipMalloc(&h->d_grid_planes, want));
+        h->grid_bytes = want;
+    }
+    return DSM_OK;
+}
+
+// a dimension < 1 or more than kGridMaxVoxels voxels: false
+bool grid_dims_ok(int32_t nx, int32_t ny, int32_t nz) {
+    if (nx < 1 || ny < 1 || nz < 1) return false;
+    const int64_t xy = (int64_t)nx * ny; // < 2^62
+    return xy <= kGridMaxVoxels && xy * nz <= kGridMaxVoxels;
+}
+
+} // namespace
+
+void dsm_grid_spec_init(dsm_grid_spec *spec) {
+    if (!spec) return;
+    memset(spec, 0, sizeof *spec);
+    spec->struct_size = (uint32_t)sizeof(dsm_grid_spec);
+    spec->voxel = 0.1f;
+    spec->nx = spec->ny = spec->nz = 1;
+}
+
+void dsm_grid_spec_around(dsm_grid_spec *spec, const float *centre, float voxel, int32_t nx, int32_t ny, int32_t nz) {
+    if (!spec || !centre) return;
+    const int32_t n[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; a++) spec->origin[a] = (float)(std::floor((double)centre[a] / (double)voxel - (double)n[a] / 2.0) * (double)voxel);
+    spec->voxel = voxel;
+    spec->nx = nx;
+    spec->ny = ny;
+    spec->nz = nz;
+}
+
+int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, const dsm_grid_spec *spec,
+                     uint32_t flags, const dsm_grid_planes *planes, int dst_on_device, int32_t *n_surfels, int32_t *n_cells) {
+    if (!h || !n_surfels || !n_cells) return DSM_E_INVALID;
+    if (!spec || !planes) return fail(h, DSM_E_INVALID, "null grid spec or planes");
+    if (spec->struct_size != sizeof(dsm_grid_spec)) return fail(h, DSM_E_INVALID, "dsm_grid_spec struct_size %u, not %zu", spec->struct_size, sizeof(dsm_grid_spec));
+    if (flags & ~(uint32_t)DSM_GRID_CELLS_OF_INFLATED) return fail(h, DSM_E_INVALID, "grid flags 0x%x", flags);
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(spec->origin[a])) return fail(h, DSM_E_INVALID, "grid origin %d is not finite", a);
+    if (!std::isfinite(spec->voxel) || !(spec->voxel > 0.0f)) return fail(h, DSM_E_INVALID, "grid voxel %g", (double)spec->voxel);
+    if (!grid_dims_ok(spec->nx, spec->ny, spec->nz))
+        return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", spec->nx, spec->ny, spec->nz);
+    if (spec->inflate < 0 || spec->inflate > kGridMaxInflate) return fail(h, DSM_E_INVALID, "grid inflate %d outside 0..%d", spec->inflate, kGridMaxInflate);
+    if (!planes->occupied && !planes->inflated && !planes->index && !planes->cells) return fail(h, DSM_E_INVALID, "no output plane");
+    if (planes->cells && planes->cells_cap < 0) return fail(h, DSM_E_INVALID, "cells_cap %d", planes->cells_cap);
+    if (dst_on_device && ((((uintptr_t)planes->occupied | (uintptr_t)planes->inflated | (uintptr_t)planes->index | (uintptr_t)planes->cells) & 3)))
+        return fail(h, DSM_E_INVALID, "device output not 4-byte aligned");
+    {
+        const void *p[4] = {planes->occupied, planes->inflated, planes->index, planes->cells};
+        for (int a = 0; a < 4; a++)
+            for (int b = a + 1; b < 4; b++)
+                if (p[a] && p[a] == p[b]) return fail(h, DSM_E_INVALID, "two output planes are the same memory");
+    }
+    const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; // (no pose is involved)
+    RenderSequence sq;
+    int rc = render_check_sequence(h, select, n_segments, store_begin, store_count, identity, nullptr, sq);
+    if (rc) return rc;
+    const std::vector<int32_t> &seg = sq.seg;
+    const int64_t runs_total = sq.runs_total, bound = sq.bound;
+    const int n_upper = sq.n_upper;
+    if ((rc = bind_device(h))) return rc;
+    const int nx = spec->nx, ny = spec->ny, nz = spec->nz, wx = (nx + 31) / 32;
+    const size_t rows = (size_t)ny * nz, n_vox = rows * nx, n_words = rows * wx, tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    const bool cells_of_inflated = (flags & DSM_GRID_CELLS_OF_INFLATED) != 0;
+    const bool want_inflated = planes->inflated || (planes->cells && cells_of_inflated);
+    const size_t cells_cap = planes->cells ? ((size_t)planes->cells_cap < n_vox ? (size_t)planes->cells_cap : n_vox) : 0; // (no more cells than voxels)
+    // what is not the caller's device memory lies in the handle's scratch, each part from a 16-byte boundary
+    const auto pad4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+    size_t words = 0;
+    const auto take = [&](bool here, size_t n) { const size_t at = words; if (here) words += pad4(n); return at; };
+    const size_t at_occ = take(!(dst_on_device && planes->occupied), n_words);
+    const size_t at_infl = take(want_inflated && !(dst_on_device && planes->inflated), n_words);
+    const size_t at_index = take(planes->index && !dst_on_device, n_vox);
+    const size_t at_cells = take(planes->cells && !dst_on_device, cells_cap);
+    const size_t at_tiles = take(planes->cells != nullptr, (n_words + 255) / 256);
+    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), 0))) return rc;
+    if ((rc = grid_reserve(h, (size_t)bound, words * sizeof(uint32_t)))) return rc;
+    if (dst_on_device && (rc = pub_order_dst(h))) return rc;
+    int32_t *d_total = h->d_pub, *d_counts = h->d_pub + 16, *d_cells_total = h->d_pub + 32, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
+    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    uint32_t *scratch = (uint32_t *)h->d_grid_planes;
+    GridSpec g;
+    for (int a = 0; a < 3; a++) g.origin[a] = spec->origin[a];
+    g.voxel = spec->voxel;
+    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
+    GridScratch sc;
+    sc.splats = (GridSplat *)h->d_grid_splats;
+    sc.counts = d_counts;
+    sc.n_seq = (int32_t)bound;
+    sc.cell_tiles = (int32_t *)(scratch + at_tiles);
+    GridOut out;
+    out.occupied = dst_on_device && planes->occupied ? planes->occupied : scratch + at_occ;
+    out.inflated = !want_inflated ? nullptr : dst_on_device && planes->inflated ? planes->inflated : scratch + at_infl;
+    out.index = !planes->index ? nullptr : dst_on_device ? planes->index : (int32_t *)(scratch + at_index);
+    out.cells = !planes->cells ? nullptr : dst_on_device ? planes->cells : (int32_t *)(scratch + at_cells);
+    out.cells_cap = (int32_t)cells_cap;
+    out.cells_total = planes->cells ? d_cells_total : nullptr;
+    out.cells_of_inflated = cells_of_inflated;
+    const hipError_t e = launch_grid(h->d_store, d_seg, (int)(seg.size() / 3), (int)runs_total, h->hc.local, h->hc.n_local, n_upper, select, d_tiles, d_total,
+                                     g, spec->inflate, sc, out, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "grid launch: %s", hipGetErrorString(e));
+    h->h_scalars[6] = 0;
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (planes->cells) HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[6], d_cells_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + runs_total);
+    const int32_t cells = h->h_scalars[6];
+    *n_cells = cells;
+    if (!dst_on_device) {
+        if (planes->occupied) HIP_TRY(h, hipMemcpy(planes->occupied, out.occupied, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (planes->inflated) HIP_TRY(h, hipMemcpy(planes->inflated, out.inflated, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (planes->index) HIP_TRY(h, hipMemcpy(planes->index, out.index, n_vox * sizeof(int32_t), hipMemcpyDeviceToHost));
+        const size_t n_out = (size_t)cells < cells_cap ? (size_t)cells : cells_cap;
+        if (planes->cells && n_out) HIP_TRY(h, hipMemcpy(planes->cells, out.cells, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (planes->cells && cells > planes->cells_cap) return fail(h, DSM_E_CAPACITY, "%d cells, room for %d", cells, planes->cells_cap);
+    return DSM_OK;
+}
+
+int dsm_grid_inflate(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t radius, const void *src_device, void *dst_device) {
+    if (!h) return DSM_E_INVALID;
+    if (!src_device || !dst_device || src_device == dst_device) return fail(h, DSM_E_INVALID, "grid inflate: null source or destination, or the same");
+    if ((((uintptr_t)src_device | (uintptr_t)dst_device) & 3)) return fail(h, DSM_E_INVALID, "grid inflate: a bit set not 4-byte aligned");
+    if (!grid_dims_ok(nx, ny, nz)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", nx, ny, nz);
+    {
+        const uintptr_t a = (uintptr_t)src_device, b = (uintptr_t)dst_device;
+        const uintptr_t bytes = (uintptr_t)((nx + 31) / 32) * (uintptr_t)ny * (uintptr_t)nz * sizeof(uint32_t); // <= 2^30
+        if ((a < b ? b - a : a - b) < bytes) return fail(h, DSM_E_INVALID, "grid inflate: source and destination overlap");
+    }
+    if (radius < 0 || radius > kGridMaxInflate) return fail(h, DSM_E_INVALID, "grid inflate %d outside 0..%d", radius, kGridMaxInflate);
+    int rc = bind_device(h);
+    if (rc) return rc;
+    if ((rc = pub_order_dst(h))) return rc;
+    const hipError_t e = launch_grid_inflate((const uint32_t *)src_device, (uint32_t *)dst_device, nx, ny, nz, radius, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "grid inflate launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return DSM_OK;
 }
 

@@ -242,6 +242,30 @@ hipError_t launch_render(const dsm_surfel *store, const int32_t *seg, int n_seg,
                          const RenderScratch &sc, const float *ray_x, const float *ray_y, float *depth, int32_t *index, float *normal,
                          uint8_t *intensity, hipStream_t st);
 
+// ---- the map as a voxel grid (dsm_k_grid.h; the definition is grid_setup / grid_covers / grid_centre of dsm_math.h)
+constexpr int kGridSmallW = 16, kGridSmallRows = 256; // boxes up to this wide along x AND of this many (y, z) rows: 16 lanes per surfel; others: a workgroup
+struct GridScratch {
+    GridSplat *splats;   // [n_seq]: small boxes from the front, large ones from the back
+    int32_t *counts;     // [2]: surfels in the small list, in the large one
+    int32_t n_seq;       // an upper bound of the sequence's length (the runs + the map's running bound)
+    int32_t *cell_tiles; // [ceil(words / 256)]: scratch of the cell list's scan
+};
+struct GridOut {          // device memory; row-major [nz][ny][..]
+    uint32_t *occupied;   // [nz][ny][wx], never null (the work plane of the others)
+    uint32_t *inflated;   // [nz][ny][wx] or null
+    int32_t *index;       // [nz][ny][nx] or null: then the bit set is splatted directly
+    int32_t *cells;       // [cells_cap] or null
+    int32_t cells_cap;
+    int32_t *cells_total; // the number of set cells, or null: no cell list
+    bool cells_of_inflated;
+};
+// The surfel sequence as for launch_render.  inflate: the radius in voxels, 0 .. kGridMaxInflate.  tile_cnt as for launch_cloud_map.
+hipError_t launch_grid(const dsm_surfel *store, const int32_t *seg, int n_seg, int runs_total, const dsm_surfel *rec, const int32_t *n_ptr, int n_upper,
+                       int select, int32_t *tile_cnt, int32_t *total, const GridSpec &g, int inflate, const GridScratch &sc, const GridOut &out,
+                       hipStream_t st);
+// dst = src dilated by the voxels within radius r; pad bits of src ignored, of dst 0.  src != dst.
+hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int ny, int nz, int r, hipStream_t st);
+
 // ---- a depth frame against the rendered map (dsm_k_align.h; the definition is align_pixel of dsm_align.h)
 // One evaluation: clears sums[29] on `st`, then adds the fixed-point terms of every sampled pixel of the frame plane `depth`
 // ([h][pitch]) that passes align_pixel against the model planes zm [mh][mw] and nm [mh][mw][3].  c from align_prepare, with T set.

@@ -1,0 +1,399 @@
+// dsm_k_grid.h -- the surfel map as a world-aligned occupancy voxel grid (dsm_grid_compose, dsm_grid_inflate): the lowest surfel
+// number covering every voxel, the occupied bit set, its inflation by a sphere of voxels, and the list of set cells.  The
+// definition (grid_setup / grid_covers / grid_centre) is in dsm_math.h and shared with the host checker tests/grid_host.cpp; this
+// file is how it is evaluated:
+//   k_grid_clear       the index plane to -1 or the bit set to 0 (whichever is splatted into), and the two list counts
+//   k_grid_setup_map   as k_render_setup_map / _run: the map records that pass `select` and the runs of the store's records,
+//   k_grid_setup_run   a lane per surfel does grid_setup; survivors are appended as GridSplat records to ONE array, small boxes
+//                      from the front, large ones from the back, by a wave ballot and one atomic add per wave and list
+//   k_grid_splat       the small list: 16 lanes per surfel, four surfels per wave.  The 16 lanes take 16 voxels along x from a
+//                      multiple of 16, so they share one word of the bit set: the wave's ballot gives each group its 16 bits
+//                      and one lane ORs them in -- or every lane does its atomicMin on 16 contiguous ints of the index plane
+//   k_grid_splat_big   the large list: a workgroup per surfel in turn (grid-stride); a wave takes 64 voxels along x from a
+//                      multiple of 64 (two words of a ballot), the four waves take rows
+//   k_grid_bits        with an index plane: the bit set from index != -1, a wave per 64 voxels of a row (every word is written)
+//   k_grid_inflate     bit-parallel dilation on 32-voxel words, a tile of row words with its y/z halo and one word of x halo
+//                      each side in LDS; for each (dy, dz) inside the radius the source row dilated along x by the table's width
+//   k_grid_cell_count / k_cloud_scan / k_grid_cell_scatter   popcount per word, scan, ordered scatter of the linear indices
+// A voxel does a plain load first and skips the atomic when nothing would change: bits only get set and indices only decrease,
+// so a stale value can cost an atomic, never a wrong skip.  The atomics are atomicOr / atomicMin / atomicAdd on 32-bit integers,
+// plain C++.  What has been measured on this chip (MI355X_MICROARCH.md, global float atomics) is the no-return fp32 add; the
+// rates of the 32-bit integer OR and min are NOT measured there -- the lanes of a surfel lie along x on the assumption that
+// they coalesce like the adds.  Every loop is bounded by a clipped box or by the grid; the lists cannot overflow (the array
+// is as long as the sequence); no workgroup waits on another.
+#pragma once
+#include "dsm_k_cloud.h"
+
+namespace dsm {
+
+__global__ __launch_bounds__(256) void k_grid_clear(uint32_t *__restrict__ plane, int64_t n, uint32_t value, int32_t *__restrict__ counts) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) plane[i] = value;
+    if (blockIdx.x == 0 && threadIdx.x < 2) counts[threadIdx.x] = 0;
+}
+
+struct GridSetupArgs {
+    GridSpec g;
+    int32_t n_seq; // length of the splat array = an upper bound of the sequence's length
+};
+
+// called by whole waves; `valid` lanes hold record r with sequence number `number`
+__device__ __forceinline__ void grid_emit(const GridSetupArgs &a, bool valid, const dsm_surfel *__restrict__ r, int number,
+                                          GridSplat *__restrict__ splats, int32_t *__restrict__ counts) {
+    GridSplat s = {};
+    bool keep = false;
+    if (valid) keep = grid_setup(a.g, *r, number, s);
+    const int64_t rows = (int64_t)(s.hi[1] - s.lo[1]) * (s.hi[2] - s.lo[2]);
+    const bool small = keep && s.hi[0] - s.lo[0] <= kGridSmallW && rows <= kGridSmallRows;
+    const bool big = keep && !small;
+    const unsigned long long m_small = __ballot(small), m_big = __ballot(big);
+    const int lane = lane_id();
+    int base_small = 0, base_big = 0;
+    if (lane == 0) {
+        if (m_small) base_small = atomicAdd(&counts[0], __popcll(m_small));
+        if (m_big) base_big = atomicAdd(&counts[1], __popcll(m_big));
+    }
+    base_small = __shfl(base_small, 0, 64);
+    base_big = __shfl(base_big, 0, 64);
+    if (keep) {
+        const int slot = small ? base_small + rank_below(m_small) : a.n_seq - 1 - (base_big + rank_below(m_big));
+        if (slot >= 0 && slot < a.n_seq) splats[slot] = s; // (always: survivors <= sequence <= n_seq)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_grid_setup_map(const dsm_surfel *__restrict__ rec, const int32_t *__restrict__ n_ptr, int n_upper, int select,
+                                                        const int32_t *__restrict__ tile_off, int base, const GridSetupArgs a,
+                                                        GridSplat *__restrict__ splats, int32_t *__restrict__ counts) {
+    __shared__ int s_cnt[4];
+    const int n = cloud_map_size(n_ptr, n_upper);
+    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int first = blockIdx.x * kCloudTile + wv * 64 * kCloudChunks;
+    unsigned long long mask[kCloudChunks];
+    int cnt = 0;
+#pragma unroll
+    for (int c = 0; c < kCloudChunks; c++) {
+        const int i = first + c * 64 + lane;
+        mask[c] = __ballot(i < n && cloud_pass(select, rec[i].update_times));
+        cnt += __popcll(mask[c]);
+    }
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    int at = base + tile_off[blockIdx.x];
+    for (int k = 0; k < wv; k++) at += s_cnt[k];
+#pragma unroll
+    for (int c = 0; c < kCloudChunks; c++) {
+        const unsigned long long m = mask[c];
+        if (m) // (wave-uniform)
+            grid_emit(a, (m >> lane) & 1ull, rec + first + c * 64 + lane, at + rank_below(m), splats, counts);
+        at += __popcll(m);
+    }
+}
+
+// seg: k_cloud_gather's table; output j of the runs is surfel j of the sequence.  A wave takes 64 consecutive outputs at a time.
+__global__ __launch_bounds__(256) void k_grid_setup_run(const dsm_surfel *__restrict__ src, const int32_t *__restrict__ seg, int n_seg, int total,
+                                                        const GridSetupArgs a, GridSplat *__restrict__ splats, int32_t *__restrict__ counts) {
+    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    for (int64_t j0 = ((int64_t)blockIdx.x * 4 + wv) * 64; j0 < total; j0 += (int64_t)gridDim.x * 256) {
+        const int j = (int)j0 + lane;
+        const bool valid = j < total;
+        const dsm_surfel *r = src;
+        if (valid) {
+            int lo = 0, hi = n_seg; // last run whose offset is <= j
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (seg[3 * mid + 2] <= j) lo = mid; else hi = mid;
+            }
+            r = src + ((int64_t)seg[3 * lo] + (j - seg[3 * lo + 2]));
+        }
+        grid_emit(a, valid, r, j, splats, counts);
+    }
+}
+
+struct GridTarget {
+    GridSpec g;
+    int wx;          // words per row of the bit set
+    uint32_t *index; // [nz][ny][nx] as unsigned: -1 = 0xffffffff is the largest, so atomicMin keeps the lowest number; or null
+    uint32_t *bits;  // [nz][ny][wx]: splatted into when index is null
+};
+
+// box inside the grid, whatever the record holds
+__device__ __forceinline__ void grid_box(const GridSpec &g, const GridSplat &s, int lo[3], int hi[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        lo[a] = s.lo[a] > 0 ? s.lo[a] : 0;
+        hi[a] = s.hi[a] < g.n[a] ? s.hi[a] : g.n[a];
+    }
+}
+
+__device__ __forceinline__ void grid_index_min(const GridTarget &t, int x, int y, int z, uint32_t number) {
+    uint32_t *p = t.index + (((int64_t)z * t.g.n[1] + y) * t.g.n[0] + x);
+    if (*p > number) atomicMin(p, number);
+}
+
+__device__ __forceinline__ void grid_bits_or(const GridTarget &t, int xw, int y, int z, uint32_t bits) {
+    uint32_t *p = t.bits + (((int64_t)z * t.g.n[1] + y) * t.wx + xw);
+    if (bits & ~*p) atomicOr(p, bits);
+}
+
+// 16 lanes per surfel.  The wave's loop is uniform (the ballot needs every lane): a group that has run out of surfels or of
+// rows goes along with nothing covered.
+__global__ __launch_bounds__(256) void k_grid_splat(const GridSplat *__restrict__ splats, const int32_t *__restrict__ counts, int n_seq, const GridTarget t) {
+    const int n = counts[0] < n_seq ? counts[0] : n_seq;
+    const int sub = threadIdx.x >> 4, l = threadIdx.x & 15, grp = (threadIdx.x >> 4) & 3;
+    for (int64_t i0 = (int64_t)blockIdx.x * 16; i0 < n; i0 += (int64_t)gridDim.x * 16) {
+        const int64_t i = i0 + sub;
+        const bool have = i < n;
+        GridSplat s = {};
+        if (have) s = splats[i];
+        int lo[3], hi[3];
+        grid_box(t.g, s, lo, hi);
+        const int xa = lo[0] & ~15; // chunks of 16 voxels from a multiple of 16: inside one word
+        const int chunks = have && hi[0] > lo[0] ? (hi[0] - xa + 15) >> 4 : 0;
+        int c = 0, y = lo[1], z = lo[2];
+        bool live = chunks > 0 && y < hi[1] && z < hi[2];
+        while (__ballot(live)) {
+            bool covered = false;
+            const int x = xa + c * 16 + l;
+            if (live && x >= lo[0] && x < hi[0])
+                covered = grid_covers(s, grid_centre(t.g.origin[0], t.g.voxel, x), grid_centre(t.g.origin[1], t.g.voxel, y),
+                                      grid_centre(t.g.origin[2], t.g.voxel, z));
+            if (t.index) {
+                if (covered) grid_index_min(t, x, y, z, (uint32_t)s.number);
+            } else {
+                const unsigned long long m = __ballot(covered);
+                const uint32_t mine = (uint32_t)(m >> (grp * 16)) & 0xffffu;
+                if (l == 0 && mine) grid_bits_or(t, x >> 5, y, z, mine << (x & 31));
+            }
+            if (live) { // the next chunk, row, slice of this group's box
+                if (++c == chunks) {
+                    c = 0;
+                    if (++y == hi[1]) {
+                        y = lo[1];
+                        if (++z == hi[2]) live = false;
+                    }
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_grid_splat_big(const GridSplat *__restrict__ splats, const int32_t *__restrict__ counts, int n_seq, const GridTarget t) {
+    const int n = counts[1] < n_seq ? counts[1] : n_seq;
+    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const GridSplat s = splats[n_seq - 1 - i];
+        int lo[3], hi[3];
+        grid_box(t.g, s, lo, hi);
+        if (lo[0] >= hi[0] || lo[1] >= hi[1] || lo[2] >= hi[2]) continue; // (block-uniform)
+        const int xa = lo[0] & ~63;
+        const int64_t rows = (int64_t)(hi[1] - lo[1]) * (hi[2] - lo[2]);
+        for (int64_t row = wv; row < rows; row += 4) { // (wave-uniform)
+            const int y = lo[1] + (int)(row % (hi[1] - lo[1])), z = lo[2] + (int)(row / (hi[1] - lo[1]));
+            const float cy = grid_centre(t.g.origin[1], t.g.voxel, y), cz = grid_centre(t.g.origin[2], t.g.voxel, z);
+            for (int xb = xa; xb < hi[0]; xb += 64) {
+                const int x = xb + lane;
+                const bool covered = x >= lo[0] && x < hi[0] && grid_covers(s, grid_centre(t.g.origin[0], t.g.voxel, x), cy, cz);
+                if (t.index) {
+                    if (covered) grid_index_min(t, x, y, z, (uint32_t)s.number);
+                } else {
+                    const unsigned long long m = __ballot(covered);
+                    const uint32_t mine = (uint32_t)(m >> (lane & 32));
+                    if ((lane & 31) == 0 && mine) grid_bits_or(t, x >> 5, y, z, mine);
+                }
+            }
+        }
+    }
+}
+
+// the bit set from the index plane: a wave per 64 voxels of a row, every word of the set written (pad bits 0)
+__global__ __launch_bounds__(256) void k_grid_bits(const uint32_t *__restrict__ index, uint32_t *__restrict__ bits, int nx, int wx, int64_t rows) {
+    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int per_row = (nx + 63) >> 6;
+    const int64_t units = rows * per_row;
+    for (int64_t u = (int64_t)blockIdx.x * 4 + wv; u < units; u += (int64_t)gridDim.x * 4) {
+        const int64_t row = u / per_row;
+        const int x = (int)(u % per_row) * 64 + lane;
+        const bool set = x < nx && index[row * nx + x] != 0xffffffffu;
+        const unsigned long long m = __ballot(set);
+        if ((lane & 31) == 0 && (x >> 5) < wx) bits[row * wx + (x >> 5)] = (uint32_t)(m >> (lane & 32));
+    }
+}
+
+// ---- inflation
+constexpr int kGridTileW = 8, kGridTileY = 8, kGridTileZ = 4; // output words per workgroup: 8 along x, 8 rows, 4 slices = 256
+struct GridInflateArgs {
+    int nx, ny, nz, wx, r;
+    uint8_t width[kGridMaxInflate * kGridMaxInflate + 1]; // by dy^2 + dz^2: grid_inflate_width (host-built)
+};
+
+// OR of v << s for s = 0 .. k (k <= 16) by doubling: after the loop v holds the shifts 0 .. have - 1, and 2 have > k + 1
+__device__ __forceinline__ unsigned long long grid_smear_up(unsigned long long v, int k) {
+    int have = 1;
+    while (2 * have <= k + 1) {
+        v |= v << have;
+        have *= 2;
+    }
+    return v | (v << (k + 1 - have));
+}
+__device__ __forceinline__ unsigned long long grid_smear_down(unsigned long long v, int k) {
+    int have = 1;
+    while (2 * have <= k + 1) {
+        v |= v >> have;
+        have *= 2;
+    }
+    return v | (v >> (k + 1 - have));
+}
+
+// LDS: [tz + 2r][ty + 2r][tw + 2] source words, pad bits and everything outside the grid 0
+__global__ __launch_bounds__(256) void k_grid_inflate(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, const GridInflateArgs a) {
+    extern __shared__ uint32_t s_tile[];
+    const int r = a.r;
+    const int lw = kGridTileW + 2, ly = kGridTileY + 2 * r, lz = kGridTileZ + 2 * r;
+    const int tiles_x = (a.wx + kGridTileW - 1) / kGridTileW, tiles_y = (a.ny + kGridTileY - 1) / kGridTileY;
+    const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x % tiles_y, bz = blockIdx.x / tiles_x / tiles_y;
+    const int w0 = bx * kGridTileW - 1, y0 = by * kGridTileY - r, z0 = bz * kGridTileZ - r;
+    const uint32_t last_mask = (a.nx & 31) ? (1u << (a.nx & 31)) - 1u : 0xffffffffu;
+    for (int i = threadIdx.x; i < lw * ly * lz; i += 256) {
+        const int w = w0 + i % lw, y = y0 + i / lw % ly, z = z0 + i / lw / ly;
+        uint32_t v = 0;
+        if (w >= 0 && w < a.wx && y >= 0 && y < a.ny && z >= 0 && z < a.nz) {
+            v = src[((int64_t)z * a.ny + y) * a.wx + w];
+            if (w == a.wx - 1) v &= last_mask;
+        }
+        s_tile[i] = v;
+    }
+    __syncthreads();
+    const int tw = threadIdx.x % kGridTileW, ty = threadIdx.x / kGridTileW % kGridTileY, tz = threadIdx.x / kGridTileW / kGridTileY;
+    const int w = bx * kGridTileW + tw, y = by * kGridTileY + ty, z = bz * kGridTileZ + tz;
+    if (w >= a.wx || y >= a.ny || z >= a.nz) return;
+    uint32_t out = 0;
+    for (int dz = -r; dz <= r; dz++)
+        for (int dy = -r; dy <= r; dy++) {
+            const int d2 = dy * dy + dz * dz;
+            if (d2 > r * r) continue;
+            const int k = a.width[d2];
+            const uint32_t *row = s_tile + ((tz + r + dz) * ly + (ty + r + dy)) * lw + tw; // row[0] = the word below, [1] = this, [2] = above
+            const unsigned long long below = ((unsigned long long)row[1] << 32) | row[0], above = ((unsigned long long)row[2] << 32) | row[1];
+            out |= (uint32_t)(grid_smear_up(below, k) >> 32) | (uint32_t)grid_smear_down(above, k);
+        }
+    if (w == a.wx - 1) out &= last_mask;
+    dst[((int64_t)z * a.ny + y) * a.wx + w] = out;
+}
+
+// ---- the cell list: 256 words per workgroup
+__global__ __launch_bounds__(256) void k_grid_cell_count(const uint32_t *__restrict__ bits, int64_t n_words, int32_t *__restrict__ tile_cnt) {
+    __shared__ int s_cnt[4];
+    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    for (int64_t tile = blockIdx.x; tile * 256 < n_words; tile += gridDim.x) {
+        const int64_t i = tile * 256 + threadIdx.x;
+        const int c = wave_sum(i < n_words ? __popc(bits[i]) : 0);
+        if (lane == 0) s_cnt[wv] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) tile_cnt[tile] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+        __syncthreads();
+    }
+}
+
+// tile_off: the exclusive prefix of the counts.  Linear indices (z ny + y) nx + x ascending, none at or beyond cap.
+__global__ __launch_bounds__(256) void k_grid_cell_scatter(const uint32_t *__restrict__ bits, int64_t n_words, int nx, int wx,
+                                                           const int32_t *__restrict__ tile_off, int32_t *__restrict__ cells, int cap) {
+    __shared__ int s_cnt[4];
+    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    for (int64_t tile = blockIdx.x; tile * 256 < n_words; tile += gridDim.x) {
+        const int64_t i = tile * 256 + threadIdx.x;
+        uint32_t v = i < n_words ? bits[i] : 0u;
+        const int c = __popc(v);
+        int incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) s_cnt[wv] = incl;
+        __syncthreads();
+        int at = tile_off[tile] + (incl - c);
+        for (int k = 0; k < wv; k++) at += s_cnt[k];
+        const int64_t row = i / wx;
+        const int32_t first = (int32_t)(row * nx + (i % wx) * 32);
+        while (v && at < cap) {
+            cells[at++] = first + (__ffs((int)v) - 1);
+            v &= v - 1;
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int ny, int nz, int r, hipStream_t st) {
+    GridInflateArgs a;
+    a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32; a.r = r;
+    for (int s = 0; s <= kGridMaxInflate * kGridMaxInflate; s++) a.width[s] = (uint8_t)(s <= r * r ? grid_inflate_width(r, s) : 0);
+    const int64_t tiles = (int64_t)((a.wx + kGridTileW - 1) / kGridTileW) * ((ny + kGridTileY - 1) / kGridTileY) * ((nz + kGridTileZ - 1) / kGridTileZ);
+    if (tiles > INT32_MAX) return hipErrorInvalidValue; // (never: at most 2^28 voxels, a tile holds at least one)
+    const size_t lds = (size_t)(kGridTileW + 2) * (kGridTileY + 2 * r) * (kGridTileZ + 2 * r) * sizeof(uint32_t); // <= 57600 bytes at r = 16
+    hipLaunchKernelGGL(k_grid_inflate, dim3((unsigned)tiles), dim3(256), lds, st, src, dst, a);
+    return hipGetLastError();
+}
+
+// the clear, then the lists, then the planes derived from them: launched in this order on one stream
+hipError_t launch_grid(const dsm_surfel *store, const int32_t *seg, int n_seg, int runs_total, const dsm_surfel *rec, const int32_t *n_ptr, int n_upper,
+                       int select, int32_t *tile_cnt, int32_t *total, const GridSpec &g, int inflate, const GridScratch &sc, const GridOut &out,
+                       hipStream_t st) {
+    const int wx = (g.n[0] + 31) / 32;
+    const int64_t rows = (int64_t)g.n[1] * g.n[2], n_vox = rows * g.n[0], n_words = rows * wx; // <= 2^28 each
+    {
+        const int64_t n = out.index ? n_vox : n_words;
+        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+        hipLaunchKernelGGL(k_grid_clear, dim3(blocks), dim3(256), 0, st, out.index ? (uint32_t *)out.index : out.occupied, n, out.index ? 0xffffffffu : 0u,
+                           sc.counts);
+    }
+    GridSetupArgs a;
+    a.g = g;
+    a.n_seq = sc.n_seq;
+    if (n_seg > 0 && runs_total > 0) {
+        int blocks = (runs_total + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(k_grid_setup_run, dim3(blocks), dim3(256), 0, st, store, seg, n_seg, runs_total, a, sc.splats, sc.counts);
+    }
+    const int tiles = (n_upper + kCloudTile - 1) / kCloudTile;
+    if (tiles == 0) {
+        const hipError_t e = hipMemsetAsync(total, 0, sizeof(int32_t), st);
+        if (e != hipSuccess) return e;
+    } else {
+        hipLaunchKernelGGL(k_cloud_count, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, tile_cnt);
+        hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, tile_cnt, tiles, total);
+        hipLaunchKernelGGL(k_grid_setup_map, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, (const int32_t *)tile_cnt, runs_total, a, sc.splats,
+                           sc.counts);
+    }
+    GridTarget t;
+    t.g = g;
+    t.wx = wx;
+    t.index = (uint32_t *)out.index;
+    t.bits = out.occupied;
+    if (sc.n_seq > 0) {
+        int blocks = (int)(((int64_t)sc.n_seq + 15) / 16 < 16384 ? ((int64_t)sc.n_seq + 15) / 16 : 16384);
+        hipLaunchKernelGGL(k_grid_splat, dim3(blocks), dim3(256), 0, st, (const GridSplat *)sc.splats, (const int32_t *)sc.counts, sc.n_seq, t);
+        blocks = sc.n_seq < 2048 ? sc.n_seq : 2048;
+        hipLaunchKernelGGL(k_grid_splat_big, dim3(blocks), dim3(256), 0, st, (const GridSplat *)sc.splats, (const int32_t *)sc.counts, sc.n_seq, t);
+    }
+    if (out.index) {
+        const int64_t units = rows * ((g.n[0] + 63) / 64);
+        const int blocks = (int)((units + 3) / 4 < 8192 ? (units + 3) / 4 : 8192);
+        hipLaunchKernelGGL(k_grid_bits, dim3(blocks), dim3(256), 0, st, (const uint32_t *)out.index, out.occupied, g.n[0], wx, rows);
+    }
+    if (out.inflated) {
+        const hipError_t e = launch_grid_inflate(out.occupied, out.inflated, g.n[0], g.n[1], g.n[2], inflate, st);
+        if (e != hipSuccess) return e;
+    }
+    if (out.cells_total) {
+        const uint32_t *of = out.cells_of_inflated ? out.inflated : out.occupied;
+        const int64_t cell_tiles = (n_words + 255) / 256; // <= 2^20
+        const int blocks = (int)(cell_tiles < 8192 ? cell_tiles : 8192);
+        hipLaunchKernelGGL(k_grid_cell_count, dim3(blocks), dim3(256), 0, st, of, n_words, sc.cell_tiles);
+        hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, sc.cell_tiles, (int)cell_tiles, out.cells_total);
+        if (out.cells && out.cells_cap > 0)
+            hipLaunchKernelGGL(k_grid_cell_scatter, dim3(blocks), dim3(256), 0, st, of, n_words, g.n[0], wx, (const int32_t *)sc.cell_tiles, out.cells,
+                               out.cells_cap);
+    }
+    return hipGetLastError();
+}
+
+} // namespace dsm

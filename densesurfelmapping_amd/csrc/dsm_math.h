@@ -914,6 +914,102 @@ DSM_HD bool render_hit(const RenderSplat &s, float rx, float ry, float near_d, f
 constexpr uint64_t kRenderEmpty = ~0ull;
 DSM_HD uint64_t render_key(float z, int number) { return ((uint64_t)__builtin_bit_cast(uint32_t, z) << 32) | (uint32_t)number; }
 
+// ---------------------------------------------------------------- the map as a voxel grid (dsm_k_grid.h, tests/grid_host.cpp)
+// A world-aligned grid: origin = the low corner of voxel (0, 0, 0), edge `voxel`, nx x ny x nz voxels; the centre of voxel i
+// along an axis is grid_centre.  A surfel is the renderer's disc in world coordinates.  grid_setup is the per-surfel part (the
+// rejects, the constants of the test, the voxel box), grid_covers the per-voxel test: the disc's plane cuts the cube
+// (|n . d| <= h |n|_1, squared) and the centre's distance from the disc's axis is at most size + h (|n x d|^2 <= (size + h)^2
+// |n|^2, by Lagrange's identity, so no division and no square root).  fp32, non-fused; every parenthesis is part of the definition.
+struct GridSpec {
+    float origin[3];
+    float voxel;
+    int n[3]; // nx, ny, nz
+};
+struct GridSplat {        // 64 bytes
+    float p[3], nrm[3];   // centre and normal, world
+    float nn, ta, rb;     // |n|^2; (h |n|_1)^2; (size + h)^2 |n|^2
+    int32_t number;       // position in the surfel sequence
+    int32_t lo[3], hi[3]; // the voxel box [lo, hi) per axis, inside the grid
+};
+constexpr int kGridMaxInflate = 16;
+constexpr int64_t kGridMaxVoxels = (int64_t)1 << 28;
+constexpr uint32_t kGridCellsOfInflated = 1u; // DSM_GRID_CELLS_OF_INFLATED
+
+DSM_HD float grid_centre(float origin, float voxel, int i) { return origin + ((float)i + 0.5f) * voxel; }
+
+// One axis of the box, in double.  A covered voxel has, in exact arithmetic, |c - p| <= size + 3h on every axis: the two tests give
+// |d|^2 |n|^2 = (n . d)^2 + |n x d|^2 <= h^2 |n|_1^2 + (size + h)^2 |n|^2 <= (3 h^2 + (size + h)^2) |n|^2 <= (size + 3h)^2 |n|^2.
+// The fp32 test rounds: a handful of roundings of 2^-24 each on terms no larger than q nn, so a passing voxel has |d| <= (size +
+// 3h) (1 + 1e-6) as long as q nn keeps its relative precision, i.e. stays above the denormals (~1e-39): with nn >= 1e-30 (below
+// that the box is the grid, see grid_setup) that is |d| >= 3e-5 m, hence the 1e-4 m added to the reach.  The centre the test
+// sees is grid_centre's fp32 value, off the exact origin + (i + 0.5) voxel by at most 2^-23 (|origin| + 2 n voxel) (three
+// roundings, and (float)i for i >= 2^24): the 4e-7 term.  One more voxel each side is slack.  The ends are clipped to [0, n]
+// as doubles, so no value outside the grid, infinite or NaN, reaches the casts.
+DSM_HD void grid_box_axis(float p, float reach, float origin, float voxel, int n, int32_t &lo, int32_t &hi) {
+    const double ext = (double)n * (double)voxel;
+    const double R = (double)reach * 1.00001 + 1e-4 + 4e-7 * (fabs((double)origin) + 2.0 * ext + fabs((double)p));
+    double a = ((double)p - R - (double)origin) / (double)voxel - 0.5 - 1.0; // i >= a
+    double b = ((double)p + R - (double)origin) / (double)voxel - 0.5 + 2.0; // i <  b
+    if (!(a > 0.0)) a = 0.0;       // (a NaN opens the side to the grid's)
+    if (!(b < (double)n)) b = (double)n;
+    if (a > (double)n) a = (double)n;
+    if (b < 0.0) b = 0.0;
+    lo = (int32_t)a;               // floor: a >= 0
+    hi = (int32_t)b == b ? (int32_t)b : (int32_t)b + 1; // ceil
+    if (hi > n) hi = n;
+}
+
+// S = dsm_surfel (or Surfel).  False: the surfel covers no voxel of this grid.
+template <typename S> DSM_HD bool grid_setup(const GridSpec &g, const S &s, int number, GridSplat &o) {
+    o.p[0] = s.px; o.p[1] = s.py; o.p[2] = s.pz;
+    o.nrm[0] = s.nx; o.nrm[1] = s.ny; o.nrm[2] = s.nz;
+    o.number = number;
+    o.nn = o.ta = o.rb = 0.0f;
+    for (int a = 0; a < 3; a++) o.lo[a] = o.hi[a] = 0;
+    const float inf = __builtin_inff();
+    if (!(fabsf(s.px) < inf && fabsf(s.py) < inf && fabsf(s.pz) < inf)) return false;
+    if (!(s.size >= 0.0f)) return false;
+    const float nn = (s.nx * s.nx + s.ny * s.ny) + s.nz * s.nz;
+    if (!(nn < inf) || !(nn > 0.0f)) return false;
+    const float h = g.voxel * 0.5f;
+    const float l1 = (fabsf(s.nx) + fabsf(s.ny)) + fabsf(s.nz);
+    const float hl = h * l1;
+    const float r = s.size + h;
+    o.nn = nn;
+    o.ta = hl * hl;
+    o.rb = (r * r) * nn;
+    // the box: the whole grid where the derivation above does not hold (a reach or a bound that overflowed, a normal so short
+    // that its square is near the denormals)
+    const float reach = s.size + 3.0f * h;
+    const bool wide = !(reach < inf) || !(o.rb < inf) || nn < 1e-30f;
+    for (int a = 0; a < 3; a++) {
+        if (wide) {
+            o.lo[a] = 0;
+            o.hi[a] = g.n[a];
+        } else {
+            grid_box_axis(o.p[a], reach, g.origin[a], g.voxel, g.n[a], o.lo[a], o.hi[a]);
+        }
+        if (o.lo[a] >= o.hi[a]) return false;
+    }
+    return true;
+}
+
+// (cx, cy, cz) = grid_centre of the voxel on each axis
+DSM_HD bool grid_covers(const GridSplat &s, float cx, float cy, float cz) {
+    const float dx = cx - s.p[0], dy = cy - s.p[1], dz = cz - s.p[2];
+    const float e = (s.nrm[0] * dx + s.nrm[1] * dy) + s.nrm[2] * dz;
+    const float e2 = e * e;
+    const float q = (dx * dx + dy * dy) + dz * dz;
+    return e2 <= s.ta && q * s.nn - e2 <= s.rb;
+}
+
+// the x-dilation width of the source rows at offset (dy, dz) of an inflation by r: floor(sqrt(r^2 - dy^2 - dz^2)), by s = dy^2 + dz^2
+DSM_HD int grid_inflate_width(int r, int s) {
+    int k = 0;
+    while ((k + 1) * (k + 1) <= r * r - s) k++;
+    return k;
+}
+
 // worker k's [begin,end) over n items, FF.cpp:198-202 / 392-396 / 471-475
 DSM_HD int chunk_of(int n, int i) {
     int step = n / kWorkers;

@@ -15,6 +15,9 @@ tests/cpp/node_replay_test.cpp reads the same format through include/dsm_surfel_
 
     python -m densesurfelmapping_amd.msglog LOG --save-cloud map.PCD --save-mesh map_mesh.PLY
 
+--save-grid PATH.npz writes the whole map as an occupancy voxel grid around the final fuse pose (--grid-voxel V, --grid-dims NX NY NZ,
+--grid-inflate R): origin, voxel, dims, inflate, the occupied and inflated bit sets and the occupied cells.
+
 --eigen-products 3.3 fuses with the 3x3 products in the order of a reference built against Eigen >= 3.3
 (DSM_FLAG_EIGEN33_PRODUCTS); the default, 3.2, is the order of Eigen 3.2, as without the flag.
 """
@@ -87,10 +90,12 @@ def read_log(path):
 EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-products -> SurfelMap(engine_flags=...)
 
 
-def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None, align=None):
+def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None, align=None,
+           save_grid=None, grid_voxel=0.1, grid_dims=(64, 64, 32), grid_inflate=0):
     """Feed a log to a SurfelMap on the GPU; returns a summary dict.  align = a cloud kind: after every fused frame that frame is
     aligned against the surfels of that kind at the pose it was fused with (SurfelMap.align_last, the library's defaults) and a
-    JSON line says how it went; the poses fed to the map are not changed."""
+    JSON line says how it went; the poses fed to the map are not changed.  save_grid: the whole map as an occupancy grid of grid_dims voxels
+    of grid_voxel metres around the final fuse pose (SurfelMap.grid), as an .npz."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
     node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity,
@@ -118,6 +123,12 @@ def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, e
     if render:  # the whole map as the node's camera sees it from the final fuse pose
         planes = node.render("all")
         np.savez(render, **{k: planes[k] for k in api.RENDER_PLANES})
+    if save_grid:  # the whole map as a voxel grid around the final fuse pose
+        g = node.grid("all", voxel=grid_voxel, dims=tuple(grid_dims), inflate=grid_inflate)
+        sp = g["spec"]
+        np.savez(save_grid, origin=np.array(sp.origin[:], np.float32), voxel=np.float32(sp.voxel), dims=np.array([sp.nx, sp.ny, sp.nz], np.int32),
+                 inflate=np.int32(sp.inflate), occupied=g["occupied"], inflated=g["inflated"], cells=g["cells"])
+        out["grid_cells"] = int(g["n_cells"])
     node.close()
     return out
 
@@ -131,6 +142,11 @@ def main():
     ap.add_argument("--render", metavar="PATH.npz", help="depth, index, normal and intensity images of the whole map at the final fuse pose")
     ap.add_argument("--align", metavar="KIND", choices=("active", "inactive", "all", "neighbor"),
                     help="after every fused frame, align it against the surfels of this cloud kind and print status, iterations, pixels, rms and the size of the correction")
+    ap.add_argument("--save-grid", metavar="PATH.npz", help="the whole map as an occupancy voxel grid around the final fuse pose: origin, voxel, dims, "
+                    "inflate, the occupied and inflated bit sets [nz][ny][(nx + 31) / 32] and the linear indices of the occupied cells")
+    ap.add_argument("--grid-voxel", type=float, default=0.1, metavar="V", help="voxel edge in metres (default 0.1)")
+    ap.add_argument("--grid-dims", type=int, nargs=3, default=(64, 64, 32), metavar=("NX", "NY", "NZ"), help="voxels per axis (default 64 64 32)")
+    ap.add_argument("--grid-inflate", type=int, default=0, metavar="R", help="inflation radius in voxels, 0..16 (default 0)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
                     help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
@@ -140,7 +156,8 @@ def main():
         cam = synth.KITTI_1226
         write_log(args.log, cam, 10, synth.node_messages(cam, synth.Scene(), args.synth, lap=120))
     print(json.dumps(replay(args.log, args.save_cloud, args.save_mesh, device=args.device, eigen_products=args.eigen_products,
-                            save_mesh_binary=args.save_mesh_binary, render=args.render, align=args.align)))
+                            save_mesh_binary=args.save_mesh_binary, render=args.render, align=args.align,
+                            save_grid=args.save_grid, grid_voxel=args.grid_voxel, grid_dims=args.grid_dims, grid_inflate=args.grid_inflate)))
 
 
 if __name__ == "__main__":

@@ -25,6 +25,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_get_mesh", "dsm_surfel_map_get_mesh_device", "dsm_surfel_map_save_mesh_binary",
     "dsm_surfel_map_render", "dsm_surfel_map_render_device",
     "dsm_surfel_map_align_last", "dsm_surfel_map_last_pose16",
+    "dsm_surfel_map_grid", "dsm_surfel_map_grid_device",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -102,6 +103,9 @@ def _bind(lib):
             lib.dsm_surfel_map_align_last.argtypes = [_vp, C.c_int, _vp, C.POINTER(api._AlignParams), C.POINTER(api._AlignResult)]
         if hasattr(lib, "dsm_surfel_map_last_pose16"):
             lib.dsm_surfel_map_last_pose16.argtypes = [_vp, _vp]
+        if hasattr(lib, "dsm_surfel_map_grid"):  # (nor the voxel grid)
+            for name in ("dsm_surfel_map_grid", "dsm_surfel_map_grid_device"):
+                getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._GridSpec), C.c_uint32, C.POINTER(api._GridPlanes), _vp, _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -239,6 +243,39 @@ class SurfelMap:
         if dst_ptrs is not None:
             return n.value
         out["n_surfels"] = n.value
+        return out
+
+    # ---- the map as a voxel grid (dsm_grid_compose)
+    def grid(self, kind="all", voxel=0.1, dims=(64, 64, 32), centre=None, inflate=0, spec=None, flags=0, planes=("occupied", "inflated", "cells"),
+             dst_ptrs=None, cells_cap=None):
+        """The surfels of cloud `kind` ("active" / "inactive" / "all" / "neighbor" or CLOUD_*) as an occupancy grid of `dims` voxels of
+        edge `voxel` around `centre` (None: the translation of the latest fuse's pose), on the lattice of multiples of `voxel`
+        (api.grid_spec_around) and inflated by `inflate` voxels -- or in the grid `spec` (api.grid_spec).  Returns api.FusionFunctions.grid's
+        dict with the spec used as "spec" -- or, with dst_ptrs = {plane: device pointer}, (n_surfels, n_cells).  More cells than
+        cells_cap: DsmError with code DSM_E_CAPACITY and .n_cells = the count needed."""
+        k = self._kind(kind)
+        if spec is None:
+            if centre is None:
+                centre = self.last_pose()[:3, 3]
+            spec = api.grid_spec_around(centre, voxel, dims, inflate)
+        n, nc = C.c_int32(0), C.c_int32(0)
+        auto = dst_ptrs is None and cells_cap is None and "cells" in planes
+        st, out = api.grid_outputs(spec, planes, dst_ptrs, 4096 if auto else cells_cap)
+        fn = self._lib.dsm_surfel_map_grid if dst_ptrs is None else self._lib.dsm_surfel_map_grid_device
+        rc = fn(self._h, k, C.byref(spec), flags, C.byref(st), C.byref(n), C.byref(nc))
+        if rc == api.DSM_E_CAPACITY and auto:
+            st, out = api.grid_outputs(spec, planes, None, nc.value)
+            rc = fn(self._h, k, C.byref(spec), flags, C.byref(st), C.byref(n), C.byref(nc))
+        if rc == api.DSM_E_CAPACITY:  # (as FusionFunctions.grid: the count needed travels with the error)
+            e = api.DsmError(rc, self._lib.dsm_surfel_map_last_error(self._h).decode())
+            e.n_cells, e.n_surfels, e.planes = nc.value, n.value, out
+            raise e
+        self._check(rc)
+        if dst_ptrs is not None:
+            return n.value, nc.value
+        if "cells" in out:
+            out["cells"] = out["cells"][: nc.value]
+        out["n_surfels"], out["n_cells"], out["spec"] = n.value, nc.value, spec
         return out
 
     # ---- the latest frame against the map (dsm_align_frame)

@@ -306,6 +306,61 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
                        const dsm_render_camera *camera, const float *pose16, const float *pose_inv16, uint32_t flags,
                        const dsm_render_planes *planes, int dst_on_device, int32_t *n_surfels);
 
+/* ---- the map as an occupancy voxel grid: what a planner or a collision checker consumes (no counterpart in the reference) ----
+ * The grid is fixed to the world: origin = the low corner of voxel (0, 0, 0), `voxel` the edge in metres, nx x ny x nz voxels;
+ * the centre of voxel i along axis a is c_a = origin_a + ((float)i + 0.5f) * voxel.  The surfel sequence is dsm_render_compose's
+ * (the store's RECORD runs in list order, then the map part chosen by `select`); a surfel is the renderer's disc -- centre p,
+ * normal n (not assumed unit), radius `size`, in world coordinates as stored; no pose is involved.  fp32, non-fused, in the
+ * order written.  Per surfel: rejected unless px, py, pz are finite, size >= 0 (a NaN fails, +inf stays) and
+ * nn = (nx nx + ny ny) + nz nz is finite and > 0; then h = voxel * 0.5f, l1 = (|nx| + |ny|) + |nz|, ta = (h l1) (h l1),
+ * r = size + h, rb = (r r) nn.  Per voxel: d = c - p, e = (nx dx + ny dy) + nz dz, e2 = e e, q = (dx dx + dy dy) + dz dz; the
+ * voxel is COVERED iff e2 <= ta and q nn - e2 <= rb: the disc's plane cuts the cube, and the centre's distance from the disc's
+ * axis is at most size + h.  No division, no square root; a NaN fails every comparison; an infinite size covers its whole slab.
+ * Every output is a minimum or an OR over a total order: the result does not depend on the order the GPU finds the covers in
+ * and is reproducible bit for bit. */
+typedef struct dsm_grid_spec {
+    uint32_t struct_size; /* sizeof(dsm_grid_spec) */
+    float origin[3];      /* finite */
+    float voxel;          /* finite, > 0 */
+    int32_t nx, ny, nz;   /* >= 1 each, nx * ny * nz <= 2^28 */
+    int32_t inflate;      /* radius of the inflation in voxels, 0 .. 16 */
+} dsm_grid_spec;
+/* origin 0, voxel 0.1 m, 1 x 1 x 1, inflate 0 */
+void dsm_grid_spec_init(dsm_grid_spec *spec);
+/* A grid of nx x ny x nz voxels around `centre` on the lattice of multiples of `voxel`: origin_a = (float)(floor((double)centre_a
+ * / voxel - n_a / 2.0) * (double)voxel), so that grids taken around successive poses share one lattice.  struct_size and inflate
+ * are left as they are.  Nothing is checked here: dsm_grid_compose does. */
+void dsm_grid_spec_around(dsm_grid_spec *spec, const float *centre /* 3 */, float voxel, int32_t nx, int32_t ny, int32_t nz);
+/* tight row-major planes, host or device memory; any may be NULL (not written), not all; no two may be the same memory, and
+ * device planes are 4-byte aligned.  wx = (nx + 31) / 32. */
+typedef struct dsm_grid_planes {
+    uint32_t *occupied; /* [nz][ny][wx]  bit x & 31 of word x >> 5 is set iff voxel (x, y, z) is covered; pad bits (x >= nx) are 0 */
+    uint32_t *inflated; /* [nz][ny][wx]  set iff some occupied voxel lies at an integer offset with dx^2 + dy^2 + dz^2 <= inflate^2
+                                         (outside the grid everything is free; inflate = 0 gives a copy): the configuration-space map
+                                         of a robot of radius inflate * voxel */
+    int32_t *index;     /* [nz][ny][nx]  the lowest surfel number among the surfels covering the voxel; -1 */
+    int32_t *cells;     /* [cells_cap]   the linear indices (z ny + y) nx + x of the set voxels of `occupied` (of `inflated` with
+                                         DSM_GRID_CELLS_OF_INFLATED), ascending: the voxel-down-sampled cloud */
+    int32_t cells_cap;  /* >= 0 when cells is not NULL */
+} dsm_grid_planes;
+#define DSM_GRID_CELLS_OF_INFLATED 1u
+/* *n_surfels = the length of the sequence (index values are below it), *n_cells = the number of cells (0 without `cells`).  More
+ * cells than cells_cap: DSM_E_CAPACITY with *n_cells = the count needed; the other planes are complete and nothing is written
+ * past the cap.  Checked before any device work (DSM_E_INVALID, nothing written): a run outside the store, a wrong struct_size,
+ * a non-finite origin, voxel not finite or not positive, a dimension < 1, nx * ny * nz > 2^28, inflate outside 0..16, all four
+ * planes NULL, two planes the same pointer, a device plane not 4-byte aligned, cells with cells_cap < 0, unknown flags.  The map, the store and the frame slots are not changed.  Launched
+ * eagerly on the handle's stream behind the frames enqueued so far; a device destination is ordered like dsm_cloud_compose's.
+ * Synchronises. */
+int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                     const dsm_grid_spec *spec, uint32_t flags, const dsm_grid_planes *planes, int dst_on_device, int32_t *n_surfels,
+                     int32_t *n_cells);
+/* The inflation alone, on a caller's bit set in DEVICE memory ([nz][ny][wx] words each, read and written behind the work
+ * enqueued on the null stream so far): dst = src dilated by the voxels within `radius` (0 .. 16).  Pad bits of src are ignored,
+ * pad bits of dst are 0.  src and dst overlapping (src == dst included) or not 4-byte aligned, a NULL, a dimension < 1, more than
+ * 2^28 voxels, a radius outside 0..16: DSM_E_INVALID
+ * before any device work.  Synchronises. */
+int dsm_grid_inflate(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t radius, const void *src_device, void *dst_device);
+
 /* ---- a depth frame against the map: projective association and point-to-plane alignment (no counterpart in the reference) ----
  * What dsm_render_compose predicts for a camera (the MODEL camera: depth plane Zm, camera-frame normal plane Nm) is compared with
  * the depth plane of a frame slot, whichever upload wrote it.  T is a rigid transform from the frame camera to the model camera,

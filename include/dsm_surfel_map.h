@@ -171,6 +171,17 @@ int dsm_surfel_map_render(dsm_surfel_map *m, int kind, const dsm_render_camera *
 int dsm_surfel_map_render_device(dsm_surfel_map *m, int kind, const dsm_render_camera *camera, const float *pose16, uint32_t flags,
                                  const dsm_render_planes *planes_device, int32_t *n_surfels);
 
+/* ---- the map as an occupancy voxel grid (dsm_grid_compose of dsm.h, where a grid is defined) ----
+ * kind = DSM_CLOUD_ACTIVE / INACTIVE / ALL / NEIGHBOR with the surfel sets, runs and numbering of dsm_surfel_map_render (for ALL,
+ * index i is surfel i of dsm_surfel_map_get_mesh); DSM_CLOUD_RAW: DSM_E_INVALID.  spec, flags, planes, *n_surfels, *n_cells and
+ * DSM_E_CAPACITY as for dsm_grid_compose; dsm_grid_spec_around with the translation of dsm_surfel_map_last_pose16 centres the
+ * grid on the robot.  DSM_E_STATE before the first fuse.  The map is not changed.  Synchronises. */
+int dsm_surfel_map_grid(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, uint32_t flags, const dsm_grid_planes *planes, int32_t *n_surfels,
+                        int32_t *n_cells);
+/* the same with the planes in device memory of the node's GPU */
+int dsm_surfel_map_grid_device(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, uint32_t flags, const dsm_grid_planes *planes_device,
+                               int32_t *n_surfels, int32_t *n_cells);
+
 /* ---- the latest frame against the map (dsm_align_frame of dsm.h, where the alignment is defined) ----
  * Aligns the depth frame of the latest fuse, still in its engine slot, against the surfel set of `kind` with the rules and runs of
  * dsm_surfel_map_render (ACTIVE: refine or judge a pose; INACTIVE: verify a loop closure against the inactive map), seen by the

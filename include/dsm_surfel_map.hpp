@@ -228,6 +228,46 @@ class SurfelMap {
         return rc;
     }
 
+    // the map as an occupancy voxel grid (dsm_grid_compose of dsm.h): the surfels of cloud `kind` in the grid `spec`.  The vectors that
+    // are not nullptr are resized and filled: occupied / inflated to nz * ny * ((nx + 31) / 32) words, index to nz * ny * nx, cells
+    // to the number of set voxels (of `inflated` with DSM_GRID_CELLS_OF_INFLATED): the voxel-down-sampled cloud as linear indices.
+    int grid(dsm_cloud_kind kind, const dsm_grid_spec &spec, uint32_t flags, std::vector<uint32_t> *occupied, std::vector<uint32_t> *inflated,
+             std::vector<int32_t> *index, std::vector<int32_t> *cells, int32_t *n_surfels = nullptr) {
+        const size_t nx = spec.nx > 0 ? (size_t)spec.nx : 0, rows = (size_t)(spec.ny > 0 ? spec.ny : 0) * (size_t)(spec.nz > 0 ? spec.nz : 0);
+        const size_t words = rows * ((nx + 31) / 32), vox = rows * nx;
+        dsm_grid_planes planes = {nullptr, nullptr, nullptr, nullptr, 0};
+        if (vox <= ((size_t)1 << 28)) { // (a larger grid is refused by the library; nothing is sized for it)
+            if (occupied) { occupied->resize(words); planes.occupied = occupied->data(); }
+            if (inflated) { inflated->resize(words); planes.inflated = inflated->data(); }
+            if (index) { index->resize(vox); planes.index = index->data(); }
+        }
+        std::vector<int32_t> none(1);
+        if (cells) { // count first, then fetch: the list is as long as the map is wide
+            planes.cells = cells->empty() ? none.data() : cells->data();
+            planes.cells_cap = (int32_t)(cells->size() < vox ? cells->size() : vox);
+        }
+        int32_t n = 0, n_cells = 0;
+        int rc = dsm_surfel_map_grid(m_, kind, &spec, flags, &planes, &n, &n_cells);
+        if (rc == DSM_E_CAPACITY && cells) {
+            cells->resize((size_t)n_cells);
+            planes.cells = cells->data();
+            planes.cells_cap = n_cells;
+            rc = dsm_surfel_map_grid(m_, kind, &spec, flags, &planes, &n, &n_cells);
+        }
+        if (rc == DSM_OK && cells) cells->resize((size_t)n_cells);
+        if (n_surfels) *n_surfels = n;
+        return check(rc);
+    }
+    // the same into device memory of the node's GPU
+    int grid_device(dsm_cloud_kind kind, const dsm_grid_spec &spec, uint32_t flags, const dsm_grid_planes &planes_device, int32_t *n_surfels = nullptr,
+                    int32_t *n_cells = nullptr) {
+        int32_t n = 0, c = 0;
+        const int rc = dsm_surfel_map_grid_device(m_, kind, &spec, flags, &planes_device, &n, &c);
+        if (n_surfels) *n_surfels = n;
+        if (n_cells) *n_cells = c;
+        return check(rc);
+    }
+
     // the frame of the latest fuse aligned, point to plane, against the surfels of cloud `kind` seen from pose16_guess (cam -> world,
     // column-major; nullptr: the latest fuse's pose): dsm_align_frame of dsm.h.  params nullptr: dsm_align_params_init's defaults.
     // Nothing is changed: what to do with result.pose16 is the caller's decision.
