@@ -47,7 +47,7 @@ struct GnHeader {
     float far2;        // squared superpixel radius (FF.cpp:820-824)
 };
 constexpr int kGnCap = 232;
-constexpr int kRestListCap = 127; // = kLaneCap of k_update_seeds: the longest list a lane keeps in LDS
+constexpr int kRestListCap = 127; // = kLaneCap of k_update_seeds: rows of a queued list; a lane keeps 123 depths in LDS, the rows up to 127 are spare (a list of 124 or more gets a wave of its own)
 constexpr int kFitSmallCap = 120; // longest list the short-column tier of k_seed_fit takes (batched launches)
 
 // Everything a kernel needs.  Passed to every kernel BY VALUE (kernel-argument segment): the pointers and

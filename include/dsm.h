@@ -658,10 +658,15 @@ int dsm_debug_wave_stamps(dsm_handle *h, int64_t *out);
 int dsm_debug_set_fit_small_cap(dsm_handle *h, int32_t cap);
 
 /* debug tap: occupancy of the second tiers of the lane-per-seed kernels (launches batched over >= 8 frames) in the LATEST
- * frame of this handle: out[2 s + 0] = superpixels whose robust mean depth (FF.cpp:530-556) needed more than one Huber pass in
- * sweep s, out[2 s + 1] = superpixels whose depth list outgrew its 127-entry LDS row in sweep s, out[6] = groups of four
+ * frame of this handle, counted over the superpixels sweep s recomputes (the ones not stable when it begins) by the length of
+ * their depth list -- the member depths above 0.1 inside the statistics window, FF.cpp:508 -- and only where that list holds
+ * no +inf (such a superpixel's robust mean is +inf and is finished in place, whatever the length):
+ * out[2 s + 0] = lists of 1 to 123 depths whose robust mean (FF.cpp:530-556) needed more than one Huber pass, the first
+ * stepping by 0.01 or more; out[2 s + 1] = lists of 124 depths or more, queued for a wave of their own (a lane keeps 123 depths
+ * in its LDS row; the spare rows up to 127 only take what a quad adds before the end is clamped); out[6] = groups of four
  * superpixels the plane fit (FF.cpp:128-180) took in its full-length tier, out[7] = 0 (reserved).  All zero after a frame that
- * ran the wave-per-seed kernels.  Synchronises. */
+ * ran the wave-per-seed kernels.  Both counts are exact: the test suite holds them to a census of the CPU restatement's
+ * state per handle, frame and sweep.  Synchronises. */
 int dsm_debug_tier_counts(dsm_handle *h, int32_t *out /* 8 */);
 
 /* debug tap: the drop-in calls (dsm_fuse_map / dsm_fuse_initialize_map) bring back only the 64-record groups of the map a frame
