@@ -74,6 +74,8 @@ ABI_SYMBOLS = (
     "dsm_align_params_init", "dsm_align_equations", "dsm_align_frame",
     # the map as an occupancy voxel grid with inflation and a cell list
     "dsm_grid_spec_init", "dsm_grid_spec_around", "dsm_grid_compose", "dsm_grid_inflate",
+    # the truncated Euclidean distance field of the grid
+    "dsm_grid_distance", "dsm_field_compose",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -162,6 +164,13 @@ GRID_CELLS_OF_INFLATED = 1
 GRID_PLANES = ("occupied", "inflated", "index", "cells")
 GRID_MAX_VOXELS = 1 << 28
 GRID_MAX_INFLATE = 16
+# dsm_grid_distance / dsm_field_compose (include/dsm.h): dist2 where no set voxel lies within max_dist, the largest max_dist and grid,
+# the planes in the order of dsm_field_planes and their element types
+FIELD_FAR = 65535
+FIELD_MAX_DIST = 64
+FIELD_MAX_VOXELS = 1 << 26
+FIELD_PLANES = ("dist2", "nearest", "distance")
+FIELD_PLANE_TYPES = {"dist2": np.uint16, "nearest": np.int32, "distance": np.float32}
 
 
 # dsm_align_status, and the layout of the 29 sums (include/dsm.h)
@@ -202,6 +211,10 @@ class _GridSpec(C.Structure):
 
 class _GridPlanes(C.Structure):
     _fields_ = [("occupied", C.c_void_p), ("inflated", C.c_void_p), ("index", C.c_void_p), ("cells", C.c_void_p), ("cells_cap", C.c_int32)]
+
+
+class _FieldPlanes(C.Structure):
+    _fields_ = [("dist2", C.c_void_p), ("nearest", C.c_void_p), ("distance", C.c_void_p)]
 
 
 class _AlignParams(C.Structure):
@@ -303,6 +316,32 @@ def grid_outputs(spec, planes, dst_ptrs, cells_cap):
             else:
                 out[k] = np.zeros((nz, ny, nx) if k == "index" else (nz, ny, (nx + 31) // 32), np.int32 if k == "index" else np.uint32)
             setattr(st, k, out[k].ctypes.data)
+    return st, out
+
+
+def field_distance_table(voxel, max_dist) -> np.ndarray:
+    """the metres of the `distance` plane by squared distance in voxels, float32 [max_dist^2 + 1], as the library builds it on the
+    host: table[k] = (float)((double)(float)voxel * sqrt((double)k)); a voxel with no set voxel within max_dist holds table[-1]"""
+    k = np.arange(int(max_dist) ** 2 + 1, dtype=np.float64)
+    return (np.float64(np.float32(voxel)) * np.sqrt(k)).astype(np.float32)
+
+
+def field_outputs(spec, planes, dst_ptrs):
+    """(the dsm_field_planes struct, the numpy arrays behind it or None for device pointers)"""
+    unknown = set(planes) - set(FIELD_PLANES) if dst_ptrs is None else set(dst_ptrs) - set(FIELD_PLANES)
+    if unknown:
+        raise ValueError("no such field plane: %s" % sorted(unknown))
+    st = _FieldPlanes()
+    if dst_ptrs is not None:
+        for k, p in dst_ptrs.items():
+            setattr(st, k, p)
+        return st, None
+    # (a size the library will refuse still gets arrays to point at: the refusal is the library's to make)
+    ok = 1 <= spec.nx and 1 <= spec.ny and 1 <= spec.nz and spec.nx * spec.ny * spec.nz <= FIELD_MAX_VOXELS
+    shape = (spec.nz, spec.ny, spec.nx) if ok else (1, 1, 1)
+    out = {k: np.zeros(shape, FIELD_PLANE_TYPES[k]) for k in FIELD_PLANES if k in planes}
+    for k, a in out.items():
+        setattr(st, k, a.ctypes.data)
     return st, out
 
 
@@ -408,6 +447,8 @@ def load_library():
     lib.dsm_grid_spec_around.restype = None
     lib.dsm_grid_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_GridSpec), C.c_uint32, C.POINTER(_GridPlanes), C.c_int, _vp, _vp]
     lib.dsm_grid_inflate.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
+    lib.dsm_grid_distance.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _vp, C.POINTER(_FieldPlanes)]
+    lib.dsm_field_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_GridSpec), C.c_int32, C.c_uint32, C.POINTER(_FieldPlanes), C.c_int, _vp]
     lib.dsm_align_params_init.argtypes = [C.POINTER(_AlignParams)]
     lib.dsm_align_params_init.restype = None
     lib.dsm_align_equations.argtypes = [_vp, C.c_int, C.POINTER(_RenderCamera), _vp, _vp, _vp, C.POINTER(_AlignParams), _vp, _vp]
@@ -779,6 +820,33 @@ class FusionFunctions:
         """dsm_grid_inflate: the inflation alone on a bit set [nz, ny, wx] in device memory (pointers, e.g. torch data_ptr()):
         dst = src dilated by the voxels within `radius`; dims = (nx, ny, nz)"""
         self._check(self._lib.dsm_grid_inflate(self._h, int(dims[0]), int(dims[1]), int(dims[2]), int(radius), _vp(src_ptr), _vp(dst_ptr)))
+
+    # ---- the distance field of the voxel grid ------------------------------------------------------
+    def grid_distance(self, dims, max_dist, voxel, src_ptr, dst_ptrs):
+        """dsm_grid_distance: the truncated Euclidean distance field of a bit set [nz, ny, wx] in device memory (pointers, e.g. torch
+        data_ptr()) into the device planes dst_ptrs = {"dist2" uint16 / "nearest" int32 / "distance" float32: pointer}, [nz, ny, nx]
+        each; dims = (nx, ny, nz), max_dist in voxels (1 .. FIELD_MAX_DIST), voxel the edge in metres"""
+        st, _ = field_outputs(None, (), dict(dst_ptrs))
+        self._check(self._lib.dsm_grid_distance(self._h, int(dims[0]), int(dims[1]), int(dims[2]), int(max_dist), float(voxel), _vp(src_ptr), C.byref(st)))
+
+    def field(self, select, segs, spec, max_dist, planes=FIELD_PLANES, dst_ptrs=None, flags=0):
+        """dsm_field_compose: the distance field, out to max_dist voxels, of the occupied set that grid(select, segs, spec) gives.
+        Returns a dict of the `planes` asked for, [nz, ny, nx] each -- "dist2" uint16 (the squared distance in voxels to the nearest
+        occupied voxel, FIELD_FAR where none lies within max_dist), "nearest" int32 (its linear index (z ny + y) nx + x, -1),
+        "distance" float32 (metres: field_distance_table(spec.voxel, max_dist)[dist2], its last entry where none) -- plus
+        "n_surfels".  With dst_ptrs = {plane: device pointer} the planes named there are written on the device and n_surfels is
+        returned."""
+        seg = np.ascontiguousarray(np.asarray(segs, np.int32).reshape(-1, 2))
+        b = np.ascontiguousarray(seg[:, 0]) if len(seg) else np.zeros(1, np.int32)
+        c = np.ascontiguousarray(seg[:, 1]) if len(seg) else np.zeros(1, np.int32)
+        st, out = field_outputs(spec, planes, dst_ptrs)
+        n = C.c_int32(0)
+        self._check(self._lib.dsm_field_compose(self._h, select, len(seg), _ptr(b), _ptr(c), C.byref(spec), int(max_dist), flags, C.byref(st),
+                                                0 if dst_ptrs is None else 1, C.byref(n)))
+        if dst_ptrs is not None:
+            return n.value
+        out["n_surfels"] = n.value
+        return out
 
     # ---- a depth frame against the rendered map -----------------------------------------------------
     def align_equations(self, slot, model_cam, model_depth_ptr, model_normal_ptr, T, params=None):

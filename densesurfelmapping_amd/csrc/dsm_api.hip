@@ -274,6 +274,12 @@ struct dsm_handle {
     size_t grid_seq = 0;
     void *d_grid_planes = nullptr;
     size_t grid_bytes = 0;
+    // dsm_grid_distance / dsm_field_compose: grow-only device scratch, none before the first field (field_bytes bytes) -- the
+    // distance table, the byte plane of the x pass, the word plane of the y pass, then (dsm_field_compose) the composed bit set and the
+    // planes that go to host memory; the table as built on the host stays here until the call has synchronised
+    void *d_field = nullptr;
+    size_t field_bytes = 0;
+    std::vector<float> field_table;
     // dsm_align_equations / dsm_align_frame: none before the first call -- the 29 sums on the device and their page-locked landing
     // place, and (dsm_align_frame, grow-only) the rendered model planes: align_px depths, then 3 * align_px normal components
     unsigned long long *d_align_sums = nullptr;
@@ -1408,6 +1414,7 @@ void dsm_destroy(dsm_handle *h) {
     if (h->d_render_splats) (void)hipFree(h->d_render_splats);
     if (h->d_grid_splats) (void)hipFree(h->d_grid_splats);
     if (h->d_grid_planes) (void)hipFree(h->d_grid_planes);
+    if (h->d_field) (void)hipFree(h->d_field);
     if (h->d_align_sums) (void)hipFree(h->d_align_sums);
     if (h->d_align_planes) (void)hipFree(h->d_align_planes);
     if (h->h_align_sums) (void)hipHostFree(h->h_align_sums);
@@ -2179,11 +2186,23 @@ int grid_reserve(dsm_handle *h, size_t seq, size_t bytes) {
     return DSM_OK;
 }
 
-// a dimension < 1 or more than kGridMaxVoxels voxels: false
-bool grid_dims_ok(int32_t nx, int32_t ny, int32_t nz) {
+// a dimension < 1 or more than `limit` voxels: false
+bool grid_dims_ok(int32_t nx, int32_t ny, int32_t nz, int64_t limit = kGridMaxVoxels) {
     if (nx < 1 || ny < 1 || nz < 1) return false;
     const int64_t xy = (int64_t)nx * ny; // < 2^62
-    return xy <= kGridMaxVoxels && xy * nz <= kGridMaxVoxels;
+    return xy <= limit && xy * nz <= limit;
+}
+
+// what dsm_grid_compose and dsm_field_compose ask of a dsm_grid_spec
+int grid_spec_check(dsm_handle *h, const dsm_grid_spec *spec) {
+    if (spec->struct_size != sizeof(dsm_grid_spec)) return fail(h, DSM_E_INVALID, "dsm_grid_spec struct_size %u, not %zu", spec->struct_size, sizeof(dsm_grid_spec));
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(spec->origin[a])) return fail(h, DSM_E_INVALID, "grid origin %d is not finite", a);
+    if (!std::isfinite(spec->voxel) || !(spec->voxel > 0.0f)) return fail(h, DSM_E_INVALID, "grid voxel %g", (double)spec->voxel);
+    if (!grid_dims_ok(spec->nx, spec->ny, spec->nz))
+        return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", spec->nx, spec->ny, spec->nz);
+    if (spec->inflate < 0 || spec->inflate > kGridMaxInflate) return fail(h, DSM_E_INVALID, "grid inflate %d outside 0..%d", spec->inflate, kGridMaxInflate);
+    return DSM_OK;
 }
 
 } // namespace
@@ -2210,14 +2229,8 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
                      uint32_t flags, const dsm_grid_planes *planes, int dst_on_device, int32_t *n_surfels, int32_t *n_cells) {
     if (!h || !n_surfels || !n_cells) return DSM_E_INVALID;
     if (!spec || !planes) return fail(h, DSM_E_INVALID, "null grid spec or planes");
-    if (spec->struct_size != sizeof(dsm_grid_spec)) return fail(h, DSM_E_INVALID, "dsm_grid_spec struct_size %u, not %zu", spec->struct_size, sizeof(dsm_grid_spec));
     if (flags & ~(uint32_t)DSM_GRID_CELLS_OF_INFLATED) return fail(h, DSM_E_INVALID, "grid flags 0x%x", flags);
-    for (int a = 0; a < 3; a++)
-        if (!std::isfinite(spec->origin[a])) return fail(h, DSM_E_INVALID, "grid origin %d is not finite", a);
-    if (!std::isfinite(spec->voxel) || !(spec->voxel > 0.0f)) return fail(h, DSM_E_INVALID, "grid voxel %g", (double)spec->voxel);
-    if (!grid_dims_ok(spec->nx, spec->ny, spec->nz))
-        return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", spec->nx, spec->ny, spec->nz);
-    if (spec->inflate < 0 || spec->inflate > kGridMaxInflate) return fail(h, DSM_E_INVALID, "grid inflate %d outside 0..%d", spec->inflate, kGridMaxInflate);
+    if (int bad = grid_spec_check(h, spec)) return bad;
     if (!planes->occupied && !planes->inflated && !planes->index && !planes->cells) return fail(h, DSM_E_INVALID, "no output plane");
     if (planes->cells && planes->cells_cap < 0) return fail(h, DSM_E_INVALID, "cells_cap %d", planes->cells_cap);
     if (dst_on_device && ((((uintptr_t)planes->occupied | (uintptr_t)planes->inflated | (uintptr_t)planes->index | (uintptr_t)planes->cells) & 3)))
@@ -2311,6 +2324,133 @@ int dsm_grid_inflate(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t 
     const hipError_t e = launch_grid_inflate((const uint32_t *)src_device, (uint32_t *)dst_device, nx, ny, nz, radius, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "grid inflate launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ the distance field of a bit set (dsm_k_field.h)
+
+namespace {
+
+// what both entry points ask of max_dist, the voxel edge and the planes; null: nothing wrong
+const char *field_request_error(int32_t max_dist, float voxel, const dsm_field_planes *p, bool on_device) {
+    if (max_dist < 1 || max_dist > kFieldMaxDist) return "max_dist outside 1..64";
+    if (!p->dist2 && !p->nearest && !p->distance) return "no output plane";
+    if (p->distance && (!std::isfinite(voxel) || !(voxel > 0.0f))) return "voxel not finite or not positive";
+    const void *q[3] = {p->dist2, p->nearest, p->distance};
+    for (int a = 0; a < 3; a++)
+        for (int b = a + 1; b < 3; b++)
+            if (q[a] && q[a] == q[b]) return "two output planes are the same memory";
+    if (on_device && ((((uintptr_t)p->nearest | (uintptr_t)p->distance) & 3) || ((uintptr_t)p->dist2 & 1))) return "a device plane is not aligned to its element";
+    return nullptr;
+}
+
+// the scratch, every part from a 256-byte boundary: what is not there has size 0
+struct FieldLayout {
+    size_t table, ox, mid, bits, dist2, nearest, distance, bytes;
+};
+FieldLayout field_layout(size_t n_vox, size_t n_words, bool with_bits, const dsm_field_planes *p, bool on_device) {
+    FieldLayout l;
+    size_t at = 0;
+    const auto take = [&](bool here, size_t n) { const size_t was = at; if (here) at += (n + 255) & ~(size_t)255; return was; };
+    l.table = take(true, (size_t)(kFieldMaxDist * kFieldMaxDist + 1) * sizeof(float));
+    l.ox = take(true, n_vox);
+    l.mid = take(true, n_vox * sizeof(uint32_t));
+    l.bits = take(with_bits, n_words * sizeof(uint32_t));
+    l.dist2 = take(p->dist2 && !on_device, n_vox * sizeof(uint16_t));
+    l.nearest = take(p->nearest && !on_device, n_vox * sizeof(int32_t));
+    l.distance = take(p->distance && !on_device, n_vox * sizeof(float));
+    l.bytes = at;
+    return l;
+}
+
+int field_reserve(dsm_handle *h, size_t bytes) {
+    if (bytes > h->field_bytes) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_field) (void)hipFree(h->d_field);
+        h->d_field = nullptr;
+        h->field_bytes = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        HIP_TRY(h, hipMalloc(&h->d_field, want));
+        h->field_bytes = want;
+    }
+    return DSM_OK;
+}
+
+// the table, the three passes, the copies to host planes; synchronises.  The scratch is reserved for `l`.
+int field_run(dsm_handle *h, const uint32_t *bits, int nx, int ny, int nz, int r, float voxel, const dsm_field_planes *p, bool on_device, const FieldLayout &l) {
+    uint8_t *sc = (uint8_t *)h->d_field;
+    const size_t n_vox = (size_t)nx * ny * nz;
+    if (p->distance) {
+        h->field_table.resize((size_t)(r * r + 1));
+        for (int k = 0; k <= r * r; k++) h->field_table[(size_t)k] = field_table_entry(voxel, k);
+        HIP_TRY(h, hipMemcpyAsync(sc + l.table, h->field_table.data(), h->field_table.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    uint16_t *dist2 = !p->dist2 ? nullptr : on_device ? p->dist2 : (uint16_t *)(sc + l.dist2);
+    int32_t *nearest = !p->nearest ? nullptr : on_device ? p->nearest : (int32_t *)(sc + l.nearest);
+    float *distance = !p->distance ? nullptr : on_device ? p->distance : (float *)(sc + l.distance);
+    const hipError_t e = launch_field(bits, nx, ny, nz, r, (const float *)(sc + l.table), (int8_t *)(sc + l.ox), (uint32_t *)(sc + l.mid), dist2, nearest, distance, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "field launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!on_device) {
+        if (p->dist2) HIP_TRY(h, hipMemcpy(p->dist2, dist2, n_vox * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        if (p->nearest) HIP_TRY(h, hipMemcpy(p->nearest, nearest, n_vox * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (p->distance) HIP_TRY(h, hipMemcpy(p->distance, distance, n_vox * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return DSM_OK;
+}
+
+} // namespace
+
+int dsm_grid_distance(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t max_dist, float voxel, const void *src_device,
+                      const dsm_field_planes *planes_device) {
+    if (!h) return DSM_E_INVALID;
+    if (!src_device || !planes_device) return fail(h, DSM_E_INVALID, "grid distance: null source or planes");
+    if (((uintptr_t)src_device & 3)) return fail(h, DSM_E_INVALID, "grid distance: the bit set is not 4-byte aligned");
+    if (!grid_dims_ok(nx, ny, nz, kFieldMaxVoxels)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^26 voxels", nx, ny, nz);
+    if (const char *bad = field_request_error(max_dist, voxel, planes_device, true)) return fail(h, DSM_E_INVALID, "grid distance: %s", bad);
+    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
+    {
+        const uintptr_t a = (uintptr_t)src_device, a_end = a + n_words * sizeof(uint32_t);
+        const uintptr_t q[3] = {(uintptr_t)planes_device->dist2, (uintptr_t)planes_device->nearest, (uintptr_t)planes_device->distance};
+        const size_t elem[3] = {sizeof(uint16_t), sizeof(int32_t), sizeof(float)};
+        for (int k = 0; k < 3; k++)
+            if (q[k] && q[k] < a_end && a < q[k] + n_vox * elem[k]) return fail(h, DSM_E_INVALID, "grid distance: a plane overlaps the source");
+    }
+    int rc = bind_device(h);
+    if (rc) return rc;
+    const FieldLayout l = field_layout(n_vox, n_words, false, planes_device, true);
+    if ((rc = field_reserve(h, l.bytes))) return rc;
+    if ((rc = pub_order_dst(h))) return rc;
+    return field_run(h, (const uint32_t *)src_device, nx, ny, nz, max_dist, voxel, planes_device, true, l);
+}
+
+int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, const dsm_grid_spec *spec,
+                      int32_t max_dist, uint32_t flags, const dsm_field_planes *planes, int dst_on_device, int32_t *n_surfels) {
+    if (!h || !n_surfels) return DSM_E_INVALID;
+    if (!spec || !planes) return fail(h, DSM_E_INVALID, "null grid spec or field planes");
+    if (flags) return fail(h, DSM_E_INVALID, "field flags 0x%x", flags);
+    if (int bad = grid_spec_check(h, spec)) return bad;
+    if (!grid_dims_ok(spec->nx, spec->ny, spec->nz, kFieldMaxVoxels))
+        return fail(h, DSM_E_INVALID, "field of %d x %d x %d: more than 2^26 voxels", spec->nx, spec->ny, spec->nz);
+    if (const char *bad = field_request_error(max_dist, spec->voxel, planes, dst_on_device != 0)) return fail(h, DSM_E_INVALID, "field: %s", bad);
+    {
+        const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; // the sequence is checked here, before the scratch grows
+        RenderSequence sq;
+        if (int bad = render_check_sequence(h, select, n_segments, store_begin, store_count, identity, nullptr, sq)) return bad;
+    }
+    int rc = bind_device(h);
+    if (rc) return rc;
+    const int nx = spec->nx, ny = spec->ny, nz = spec->nz;
+    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
+    const FieldLayout l = field_layout(n_vox, n_words, true, planes, dst_on_device != 0);
+    if ((rc = field_reserve(h, l.bytes))) return rc;
+    // the occupied set by dsm_grid_compose itself, into the scratch as a device destination
+    uint32_t *bits = (uint32_t *)((uint8_t *)h->d_field + l.bits);
+    const dsm_grid_planes occupied = {bits, nullptr, nullptr, nullptr, 0};
+    int32_t n = 0, cells = 0;
+    if ((rc = dsm_grid_compose(h, select, n_segments, store_begin, store_count, spec, 0, &occupied, 1, &n, &cells))) return rc;
+    if ((rc = field_run(h, bits, nx, ny, nz, max_dist, spec->voxel, planes, dst_on_device != 0, l))) return rc;
+    *n_surfels = n;
     return DSM_OK;
 }
 

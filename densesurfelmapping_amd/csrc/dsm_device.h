@@ -266,6 +266,13 @@ hipError_t launch_grid(const dsm_surfel *store, const int32_t *seg, int n_seg, i
 // dst = src dilated by the voxels within radius r; pad bits of src ignored, of dst 0.  src != dst.
 hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int ny, int nz, int r, hipStream_t st);
 
+// ---- the distance field of a bit set (dsm_k_field.h; the definition is field_key of dsm_math.h)
+// bits: [nz][ny][wx] words, pad bits ignored.  1 <= r <= kFieldMaxDist, at most kFieldMaxVoxels voxels.  table: [r^2 + 1] metres by
+// squared distance (field_table_entry).  ox: [voxels] bytes and mid: [voxels] words of scratch.  dist2 / nearest / distance: tight
+// [nz][ny][nx] planes, any may be null.
+hipError_t launch_field(const uint32_t *bits, int nx, int ny, int nz, int r, const float *table, int8_t *ox, uint32_t *mid, uint16_t *dist2,
+                        int32_t *nearest, float *distance, hipStream_t st);
+
 // ---- a depth frame against the rendered map (dsm_k_align.h; the definition is align_pixel of dsm_align.h)
 // One evaluation: clears sums[29] on `st`, then adds the fixed-point terms of every sampled pixel of the frame plane `depth`
 // ([h][pitch]) that passes align_pixel against the model planes zm [mh][mw] and nm [mh][mw][3].  c from align_prepare, with T set.

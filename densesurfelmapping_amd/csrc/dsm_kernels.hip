@@ -22,6 +22,7 @@
 //   k_mesh_*        save_mesh's hexagons as vertex and index buffers               SM.cpp:1176-1280 (dsm_k_mesh.h)
 //   k_render_*      the map as depth / index / normal / intensity images from any pose (no reference counterpart; dsm_k_render.h)
 //   k_grid_*        the map as a world-aligned occupancy voxel grid with inflation and a cell list (no reference counterpart; dsm_k_grid.h)
+//   k_field_*       the truncated Euclidean distance field of the grid's bit set (no reference counterpart; dsm_k_field.h)
 //   k_align         the normal equations of a depth frame against the rendered map (no reference counterpart; dsm_k_align.h)
 //
 // One translation unit; the kernels by stage: dsm_k_superpixel.h (k_init_seeds .. k_commit_seeds), dsm_k_planes.h (k_seed_points,
@@ -44,6 +45,7 @@
 #include "dsm_k_mesh.h"
 #include "dsm_k_render.h"
 #include "dsm_k_grid.h"
+#include "dsm_k_field.h"
 #include "dsm_k_align.h"
 
 namespace dsm {

@@ -1010,6 +1010,20 @@ DSM_HD int grid_inflate_width(int r, int s) {
     return k;
 }
 
+// ---------------------------------------------------------------- the distance field of a bit set (dsm_k_field.h, tests/field_host.cpp)
+// For voxel v the result is the minimum of field_key over the set voxels o with |v - o|^2 <= R^2 (integer squared distance in
+// voxels, lin(o) = (oz ny + oy) nx + ox): the nearest set voxel, on a tie the one with the lowest linear index.  A minimum over a
+// total order: it does not depend on how the passes split it.
+constexpr int kFieldMaxDist = 64;
+constexpr int64_t kFieldMaxVoxels = (int64_t)1 << 26;
+constexpr uint16_t kFieldFar = 65535; // dist2 of a voxel with no set voxel within R; its `nearest` is -1
+
+DSM_HD uint64_t field_key(uint32_t d2, uint32_t lin) { return ((uint64_t)d2 << 32) | lin; }
+
+// the metres of the `distance` plane by squared distance in voxels, k = 0 .. R^2: built on the host and uploaded, so that no
+// square root is taken on the device and the plane is the same bits everywhere
+static inline float field_table_entry(float voxel, int k) { return (float)((double)voxel * sqrt((double)k)); }
+
 // worker k's [begin,end) over n items, FF.cpp:198-202 / 392-396 / 471-475
 DSM_HD int chunk_of(int n, int i) {
     int step = n / kWorkers;

@@ -18,6 +18,9 @@ tests/cpp/node_replay_test.cpp reads the same format through include/dsm_surfel_
 --save-grid PATH.npz writes the whole map as an occupancy voxel grid around the final fuse pose (--grid-voxel V, --grid-dims NX NY NZ,
 --grid-inflate R): origin, voxel, dims, inflate, the occupied and inflated bit sets and the occupied cells.
 
+--save-field PATH.npz writes the truncated Euclidean distance field of that grid's occupied set out to --field-max-dist R voxels
+(same --grid-voxel and --grid-dims): origin, voxel, dims, max_dist, dist2, nearest, distance.
+
 --eigen-products 3.3 fuses with the 3x3 products in the order of a reference built against Eigen >= 3.3
 (DSM_FLAG_EIGEN33_PRODUCTS); the default, 3.2, is the order of Eigen 3.2, as without the flag.
 """
@@ -91,11 +94,12 @@ EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-pro
 
 
 def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None, align=None,
-           save_grid=None, grid_voxel=0.1, grid_dims=(64, 64, 32), grid_inflate=0):
+           save_grid=None, grid_voxel=0.1, grid_dims=(64, 64, 32), grid_inflate=0, save_field=None, field_max_dist=16):
     """Feed a log to a SurfelMap on the GPU; returns a summary dict.  align = a cloud kind: after every fused frame that frame is
     aligned against the surfels of that kind at the pose it was fused with (SurfelMap.align_last, the library's defaults) and a
     JSON line says how it went; the poses fed to the map are not changed.  save_grid: the whole map as an occupancy grid of grid_dims voxels
-    of grid_voxel metres around the final fuse pose (SurfelMap.grid), as an .npz."""
+    of grid_voxel metres around the final fuse pose (SurfelMap.grid), as an .npz.  save_field: the distance field of that grid's occupied
+    set out to field_max_dist voxels (SurfelMap.field), as an .npz."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
     node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity,
@@ -129,6 +133,12 @@ def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, e
         np.savez(save_grid, origin=np.array(sp.origin[:], np.float32), voxel=np.float32(sp.voxel), dims=np.array([sp.nx, sp.ny, sp.nz], np.int32),
                  inflate=np.int32(sp.inflate), occupied=g["occupied"], inflated=g["inflated"], cells=g["cells"])
         out["grid_cells"] = int(g["n_cells"])
+    if save_field:  # the distance field of the same grid's occupied set
+        f = node.field("all", voxel=grid_voxel, dims=tuple(grid_dims), max_dist=field_max_dist)
+        sp = f["spec"]
+        np.savez(save_field, origin=np.array(sp.origin[:], np.float32), voxel=np.float32(sp.voxel), dims=np.array([sp.nx, sp.ny, sp.nz], np.int32),
+                 max_dist=np.int32(field_max_dist), dist2=f["dist2"], nearest=f["nearest"], distance=f["distance"])
+        out["field_near"] = int((f["dist2"] != api.FIELD_FAR).sum())
     node.close()
     return out
 
@@ -147,6 +157,9 @@ def main():
     ap.add_argument("--grid-voxel", type=float, default=0.1, metavar="V", help="voxel edge in metres (default 0.1)")
     ap.add_argument("--grid-dims", type=int, nargs=3, default=(64, 64, 32), metavar=("NX", "NY", "NZ"), help="voxels per axis (default 64 64 32)")
     ap.add_argument("--grid-inflate", type=int, default=0, metavar="R", help="inflation radius in voxels, 0..16 (default 0)")
+    ap.add_argument("--save-field", metavar="PATH.npz", help="the truncated Euclidean distance field of the occupied set of the --grid-voxel / --grid-dims "
+                    "grid around the final fuse pose: origin, voxel, dims, max_dist and the planes dist2, nearest, distance [nz][ny][nx]")
+    ap.add_argument("--field-max-dist", type=int, default=16, metavar="R", help="truncation radius of --save-field in voxels, 1..64 (default 16)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
                     help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
@@ -157,7 +170,8 @@ def main():
         write_log(args.log, cam, 10, synth.node_messages(cam, synth.Scene(), args.synth, lap=120))
     print(json.dumps(replay(args.log, args.save_cloud, args.save_mesh, device=args.device, eigen_products=args.eigen_products,
                             save_mesh_binary=args.save_mesh_binary, render=args.render, align=args.align,
-                            save_grid=args.save_grid, grid_voxel=args.grid_voxel, grid_dims=args.grid_dims, grid_inflate=args.grid_inflate)))
+                            save_grid=args.save_grid, grid_voxel=args.grid_voxel, grid_dims=args.grid_dims, grid_inflate=args.grid_inflate,
+                            save_field=args.save_field, field_max_dist=args.field_max_dist)))
 
 
 if __name__ == "__main__":

@@ -26,6 +26,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_render", "dsm_surfel_map_render_device",
     "dsm_surfel_map_align_last", "dsm_surfel_map_last_pose16",
     "dsm_surfel_map_grid", "dsm_surfel_map_grid_device",
+    "dsm_surfel_map_field", "dsm_surfel_map_field_device",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -106,6 +107,9 @@ def _bind(lib):
         if hasattr(lib, "dsm_surfel_map_grid"):  # (nor the voxel grid)
             for name in ("dsm_surfel_map_grid", "dsm_surfel_map_grid_device"):
                 getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._GridSpec), C.c_uint32, C.POINTER(api._GridPlanes), _vp, _vp]
+        if hasattr(lib, "dsm_surfel_map_field"):  # (nor the distance field)
+            for name in ("dsm_surfel_map_field", "dsm_surfel_map_field_device"):
+                getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._GridSpec), C.c_int32, C.c_uint32, C.POINTER(api._FieldPlanes), _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -276,6 +280,26 @@ class SurfelMap:
         if "cells" in out:
             out["cells"] = out["cells"][: nc.value]
         out["n_surfels"], out["n_cells"], out["spec"] = n.value, nc.value, spec
+        return out
+
+    # ---- the map as a distance field (dsm_field_compose)
+    def field(self, kind="all", voxel=0.1, dims=(64, 64, 32), centre=None, max_dist=16, spec=None, flags=0, planes=api.FIELD_PLANES, dst_ptrs=None):
+        """The truncated Euclidean distance field, out to `max_dist` voxels, of the occupied set that grid() gives for the same `kind`
+        and grid: `dims` voxels of edge `voxel` around `centre` (None: the translation of the latest fuse's pose), or the grid `spec`.
+        Returns api.FusionFunctions.field's dict with the spec used as "spec" -- or, with dst_ptrs = {plane: device pointer},
+        n_surfels."""
+        k = self._kind(kind)
+        if spec is None:
+            if centre is None:
+                centre = self.last_pose()[:3, 3]
+            spec = api.grid_spec_around(centre, voxel, dims)
+        st, out = api.field_outputs(spec, planes, dst_ptrs)
+        n = C.c_int32(0)
+        fn = self._lib.dsm_surfel_map_field if dst_ptrs is None else self._lib.dsm_surfel_map_field_device
+        self._check(fn(self._h, k, C.byref(spec), int(max_dist), flags, C.byref(st), C.byref(n)))
+        if dst_ptrs is not None:
+            return n.value
+        out["n_surfels"], out["spec"] = n.value, spec
         return out
 
     # ---- the latest frame against the map (dsm_align_frame)

@@ -361,6 +361,44 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
  * before any device work.  Synchronises. */
 int dsm_grid_inflate(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t radius, const void *src_device, void *dst_device);
 
+/* ---- the truncated Euclidean distance field of the grid: what a planner or a trajectory optimiser consumes ----
+ * Input: a bit set O in the grid layout ([nz][ny][wx] words, wx = (nx + 31) / 32, pad bits ignored) and a truncation radius
+ * max_dist = R in voxels, 1 <= R <= DSM_FIELD_MAX_DIST.  Outside the grid everything is free, as for the inflation.  For voxel
+ * v = (x, y, z) let key(o) = (uint64)|v - o|^2 << 32 | lin(o) over the set voxels o with |v - o|^2 <= R^2, where |.|^2 is the
+ * integer squared distance in voxels and lin(o) = (oz ny + oy) nx + ox.  The result for v is the MINIMUM key: the nearest occupied
+ * voxel, on an exact tie the one with the lowest linear index.  A minimum over a total order: it does not depend on how the GPU
+ * arranges its passes and is reproducible bit for bit.  An occupied voxel has dist2 0 and nearest = itself;
+ * inflated(r) == (dist2 <= r * r) for every r <= R.  `distance` is table[dist2] with table[k] = (float)((double)voxel *
+ * sqrt((double)k)), k = 0 .. R^2, built on the host and uploaded: no square root is taken on the device.  A voxel with no key gets
+ * table[R^2], "at least this far"; dist2 tells the two cases apart.
+ * Not provided: a signed field (the distance to free space inside obstacles), gradients, and the field of the inflated set. */
+#define DSM_FIELD_MAX_DIST 64
+#define DSM_FIELD_FAR 65535u
+/* tight row-major [nz][ny][nx] planes; any may be NULL (not written), not all; no two may be the same memory; device planes are
+ * aligned to their element */
+typedef struct dsm_field_planes {
+    uint16_t *dist2;  /* the high half of the minimum key (<= 4096); DSM_FIELD_FAR when no key exists */
+    int32_t *nearest; /* the low half of the minimum key: the linear index of the nearest set voxel; -1 */
+    float *distance;  /* metres: table[dist2]; table[R^2] when no key exists */
+} dsm_field_planes;
+/* The field of a caller's bit set in DEVICE memory into device planes, ordered and synchronised as dsm_grid_inflate.  `voxel` is
+ * the edge in metres (read only when `distance` is asked for).  The intermediates cost up to 8 bytes a voxel of grow-only handle
+ * scratch, hence the limit of 2^26 voxels.  DSM_E_INVALID before any device work, nothing written: a NULL handle, source or
+ * planes; a dimension < 1; more than 2^26 voxels; max_dist outside 1..64; voxel not finite or not > 0 while `distance` is asked
+ * for; all three planes NULL; two planes the same pointer; a plane overlapping the source; the source, `nearest` or `distance`
+ * not 4-byte aligned, `dist2` not 2-byte aligned.  Synchronises. */
+int dsm_grid_distance(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t max_dist, float voxel, const void *src_device,
+                      const dsm_field_planes *planes_device);
+/* The field of the map: the occupied set of dsm_grid_compose for the same sequence and `spec` (composed into handle scratch), then
+ * its field into host or device planes (dst_on_device as for dsm_grid_compose; the alignment rule holds for device planes).
+ * spec->inflate is validated as always and otherwise unused; at most 2^26 voxels; flags must be 0.  *n_surfels = the length of the
+ * sequence, as dsm_grid_compose reports it.  Checked before any device work (DSM_E_INVALID, nothing written): what
+ * dsm_grid_compose checks of the sequence and the spec, and what dsm_grid_distance checks of max_dist, the voxel and the planes.
+ * The map, the store and the frame slots are not changed.  Synchronises. */
+int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
+                      const dsm_grid_spec *spec, int32_t max_dist, uint32_t flags, const dsm_field_planes *planes, int dst_on_device,
+                      int32_t *n_surfels);
+
 /* ---- a depth frame against the map: projective association and point-to-plane alignment (no counterpart in the reference) ----
  * What dsm_render_compose predicts for a camera (the MODEL camera: depth plane Zm, camera-frame normal plane Nm) is compared with
  * the depth plane of a frame slot, whichever upload wrote it.  T is a rigid transform from the frame camera to the model camera,

@@ -182,6 +182,16 @@ int dsm_surfel_map_grid(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, 
 int dsm_surfel_map_grid_device(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, uint32_t flags, const dsm_grid_planes *planes_device,
                                int32_t *n_surfels, int32_t *n_cells);
 
+/* ---- the map as a truncated Euclidean distance field (dsm_field_compose of dsm.h, where the field is defined) ----
+ * The field of the occupied set of dsm_surfel_map_grid for the same kind and spec: kinds, runs and numbering as there; DSM_CLOUD_RAW
+ * and unknown kinds: DSM_E_INVALID.  spec, max_dist, flags, planes and *n_surfels as for dsm_field_compose.  DSM_E_STATE before the
+ * first fuse.  The map is not changed.  Synchronises. */
+int dsm_surfel_map_field(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, int32_t max_dist, uint32_t flags, const dsm_field_planes *planes,
+                         int32_t *n_surfels);
+/* the same with the planes in device memory of the node's GPU */
+int dsm_surfel_map_field_device(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, int32_t max_dist, uint32_t flags,
+                                const dsm_field_planes *planes_device, int32_t *n_surfels);
+
 /* ---- the latest frame against the map (dsm_align_frame of dsm.h, where the alignment is defined) ----
  * Aligns the depth frame of the latest fuse, still in its engine slot, against the surfel set of `kind` with the rules and runs of
  * dsm_surfel_map_render (ACTIVE: refine or judge a pose; INACTIVE: verify a loop closure against the inactive map), seen by the

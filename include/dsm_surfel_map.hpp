@@ -268,6 +268,31 @@ class SurfelMap {
         return check(rc);
     }
 
+    // the map as a truncated Euclidean distance field (dsm_field_compose of dsm.h): the field, out to max_dist voxels, of the occupied
+    // set that grid() gives for the same kind and spec.  The vectors that are not nullptr are resized to nz * ny * nx and filled.
+    int field(dsm_cloud_kind kind, const dsm_grid_spec &spec, int32_t max_dist, uint32_t flags, std::vector<uint16_t> *dist2, std::vector<int32_t> *nearest,
+              std::vector<float> *distance, int32_t *n_surfels = nullptr) {
+        const size_t vox = (size_t)(spec.nx > 0 ? spec.nx : 0) * (size_t)(spec.ny > 0 ? spec.ny : 0) * (size_t)(spec.nz > 0 ? spec.nz : 0);
+        dsm_field_planes planes = {nullptr, nullptr, nullptr};
+        if (vox <= ((size_t)1 << 26)) { // (a larger grid is refused by the library; nothing is sized for it)
+            if (dist2) { dist2->resize(vox); planes.dist2 = dist2->data(); }
+            if (nearest) { nearest->resize(vox); planes.nearest = nearest->data(); }
+            if (distance) { distance->resize(vox); planes.distance = distance->data(); }
+        }
+        int32_t n = 0;
+        const int rc = dsm_surfel_map_field(m_, kind, &spec, max_dist, flags, &planes, &n);
+        if (n_surfels) *n_surfels = n;
+        return check(rc);
+    }
+    // the same into device memory of the node's GPU
+    int field_device(dsm_cloud_kind kind, const dsm_grid_spec &spec, int32_t max_dist, uint32_t flags, const dsm_field_planes &planes_device,
+                     int32_t *n_surfels = nullptr) {
+        int32_t n = 0;
+        const int rc = dsm_surfel_map_field_device(m_, kind, &spec, max_dist, flags, &planes_device, &n);
+        if (n_surfels) *n_surfels = n;
+        return check(rc);
+    }
+
     // the frame of the latest fuse aligned, point to plane, against the surfels of cloud `kind` seen from pose16_guess (cam -> world,
     // column-major; nullptr: the latest fuse's pose): dsm_align_frame of dsm.h.  params nullptr: dsm_align_params_init's defaults.
     // Nothing is changed: what to do with result.pose16 is the caller's decision.
