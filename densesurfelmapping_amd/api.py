@@ -76,6 +76,8 @@ ABI_SYMBOLS = (
     "dsm_grid_spec_init", "dsm_grid_spec_around", "dsm_grid_compose", "dsm_grid_inflate",
     # the truncated Euclidean distance field of the grid
     "dsm_grid_distance", "dsm_field_compose",
+    # free space carved by depth frames, the three-state map and its frontier
+    "dsm_carve_params_init", "dsm_grid_carve", "dsm_grid_classify",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -171,6 +173,13 @@ FIELD_MAX_DIST = 64
 FIELD_MAX_VOXELS = 1 << 26
 FIELD_PLANES = ("dist2", "nearest", "distance")
 FIELD_PLANE_TYPES = {"dist2": np.uint16, "nearest": np.int32, "distance": np.float32}
+# dsm_grid_carve / dsm_grid_classify (include/dsm.h): the most frames of one carve, its flags, the states of a voxel, the planes in the
+# order of dsm_space_planes
+CARVE_MAX_FRAMES = 32
+CARVE_REPLACE = 1
+CARVE_TRUST_INFINITE = 2
+SPACE_UNKNOWN, SPACE_FREE, SPACE_OCCUPIED = 0, 1, 2
+SPACE_PLANES = ("state", "known_free", "frontier", "cells")
 
 
 # dsm_align_status, and the layout of the 29 sums (include/dsm.h)
@@ -217,6 +226,14 @@ class _FieldPlanes(C.Structure):
     _fields_ = [("dist2", C.c_void_p), ("nearest", C.c_void_p), ("distance", C.c_void_p)]
 
 
+class _CarveParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("near_dist", C.c_float), ("far_dist", C.c_float), ("margin", C.c_float)]
+
+
+class _SpacePlanes(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("known_free", C.c_void_p), ("frontier", C.c_void_p), ("cells", C.c_void_p), ("cells_cap", C.c_int32)]
+
+
 class _AlignParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_iterations", C.c_int32), ("stride", C.c_int32), ("dist_max", C.c_float),
                 ("min_view_cos", C.c_float), ("huber", C.c_float), ("min_pixels", C.c_int32), ("stop_translation", C.c_float),
@@ -248,6 +265,40 @@ def align_result(r: _AlignResult) -> dict:
     return {"pose": np.array(r.pose16, np.float32).reshape(4, 4).T.copy(), "T": np.array(r.T16, np.float32).reshape(4, 4).T.copy(),
             "status": r.status, "iterations": r.iterations, "n_pixels": r.n_pixels, "rms": r.rms, "scale_log2": r.scale_log2,
             "sums": np.array(r.sums, np.int64)}
+
+
+def carve_params(params=None, **kw) -> _CarveParams:
+    """a dsm_carve_params: one passed through, or the library's defaults (dsm_carve_params_init: near_dist 0.1 m, far_dist 10 m, margin
+    0.1732051 m = one voxel diagonal of a 0.1 m grid) with the fields named in kw replaced"""
+    if isinstance(params, _CarveParams):
+        return params
+    p = _CarveParams()
+    load_library().dsm_carve_params_init(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if k not in dict(_CarveParams._fields_):
+            raise ValueError("no such carve parameter: %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+def space_outputs(spec, planes, dst_ptrs, cells_cap):
+    """(the dsm_space_planes struct, the numpy arrays behind it or None for device pointers)"""
+    unknown = set(planes) - set(SPACE_PLANES) if dst_ptrs is None else set(dst_ptrs) - set(SPACE_PLANES)
+    if unknown:
+        raise ValueError("no such space plane: %s" % sorted(unknown))
+    st = _SpacePlanes()
+    st.cells_cap = 0 if cells_cap is None else int(cells_cap)
+    if dst_ptrs is not None:
+        for k, p in dst_ptrs.items():
+            setattr(st, k, p)
+        return st, None
+    wx, words, voxels = grid_shapes(spec)
+    out = {}
+    for k in SPACE_PLANES:
+        if k in planes:
+            out[k] = np.zeros(max(st.cells_cap, 1), np.int32) if k == "cells" else np.zeros(voxels, np.uint8) if k == "state" else np.zeros(words, np.uint32)
+            setattr(st, k, out[k].ctypes.data)
+    return st, out
 
 
 def grid_spec(origin=(0.0, 0.0, 0.0), voxel=0.1, dims=(1, 1, 1), inflate=0) -> _GridSpec:
@@ -449,6 +500,10 @@ def load_library():
     lib.dsm_grid_inflate.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]
     lib.dsm_grid_distance.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _vp, C.POINTER(_FieldPlanes)]
     lib.dsm_field_compose.argtypes = [_vp, C.c_int, C.c_int32, _vp, _vp, C.POINTER(_GridSpec), C.c_int32, C.c_uint32, C.POINTER(_FieldPlanes), C.c_int, _vp]
+    lib.dsm_carve_params_init.argtypes = [C.POINTER(_CarveParams)]
+    lib.dsm_carve_params_init.restype = None
+    lib.dsm_grid_carve.argtypes = [_vp, C.POINTER(_GridSpec), C.POINTER(_CarveParams), C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]
+    lib.dsm_grid_classify.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_SpacePlanes), _vp]
     lib.dsm_align_params_init.argtypes = [C.POINTER(_AlignParams)]
     lib.dsm_align_params_init.restype = None
     lib.dsm_align_equations.argtypes = [_vp, C.c_int, C.POINTER(_RenderCamera), _vp, _vp, _vp, C.POINTER(_AlignParams), _vp, _vp]
@@ -847,6 +902,38 @@ class FusionFunctions:
             return n.value
         out["n_surfels"] = n.value
         return out
+
+    # ---- free space, the three states, the frontier ------------------------------------------------
+    def grid_carve(self, spec, slots, poses, free_ptr, params=None, flags=0, poses_inv=None):
+        """dsm_grid_carve: the voxels of the grid `spec` that the depth frames in the frame slots `slots` see through, OR-ed into the bit
+        set [nz, ny, wx] at the device pointer free_ptr (CARVE_REPLACE: stored over it).  poses: one 4x4 cam -> world matrix per slot
+        (row-major numpy, as everywhere here), poses_inv their inverses or None (the library's closed form); params a carve_params()
+        or a dict of its fields.  Returns the population count of the set after the call."""
+        sl = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+        ps = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
+        pi = None if poses_inv is None else np.ascontiguousarray(np.asarray(poses_inv, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
+        if len(ps) != len(sl) or (pi is not None and len(pi) != len(sl)):
+            raise ValueError("one pose (and one inverse) per slot")
+        p = carve_params(params)
+        n = C.c_int64(0)
+        self._check(self._lib.dsm_grid_carve(self._h, C.byref(spec), C.byref(p), int(flags), len(sl), _ptr(sl) if len(sl) else None, _ptr(ps) if len(sl) else None,
+                                             None if pi is None else _ptr(pi), _vp(free_ptr), C.byref(n)))
+        return n.value
+
+    def grid_classify(self, dims, occupied_ptr, free_ptr, dst_ptrs, cells_cap=0):
+        """dsm_grid_classify: the three states and the frontier of the bit sets [nz, ny, wx] at the device pointers occupied_ptr and
+        free_ptr, into the device planes dst_ptrs = {"state" uint8 [nz, ny, nx] (SPACE_UNKNOWN / _FREE / _OCCUPIED) / "known_free" /
+        "frontier" uint32 [nz, ny, wx] / "cells" int32 [cells_cap]: pointer}; dims = (nx, ny, nz).  Returns the number of frontier
+        voxels.  More than cells_cap with a cells plane: DsmError with code DSM_E_CAPACITY and .n_frontier = the count needed."""
+        st, _ = space_outputs(None, (), dict(dst_ptrs), cells_cap)
+        n = C.c_int32(0)
+        rc = self._lib.dsm_grid_classify(self._h, int(dims[0]), int(dims[1]), int(dims[2]), _vp(occupied_ptr), _vp(free_ptr), C.byref(st), C.byref(n))
+        if rc == DSM_E_CAPACITY:
+            e = DsmError(rc, self._lib.dsm_last_error(self._h).decode())
+            e.n_frontier = n.value
+            raise e
+        self._check(rc)
+        return n.value
 
     # ---- a depth frame against the rendered map -----------------------------------------------------
     def align_equations(self, slot, model_cam, model_depth_ptr, model_normal_ptr, T, params=None):

@@ -168,7 +168,7 @@ struct dsm_handle {
     std::vector<void *> allocs; // every hipMalloc of this handle
     std::vector<hipGraphExec_t> retired; // graphs replaced while possibly in flight (map_grows): destroyed at the next synchronisation point
     FrameParams *h_params = nullptr; // pinned staging ring
-    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size, [6] grid cells; [64..127] the device's scalar block as it came
+    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size, [6] grid cells, [7] frontier cells, [8..9] carved voxels (64 bits); [64..127] the device's scalar block as it came
     int32_t *d_scalars = nullptr;    // the device's scalar block (64 ints: n_local @8, n_local_next @16, n_new @24, n_holes @32, status @48, delta count @56)
     FrameParams *d_params = nullptr;
     uint8_t *d_stage_img = nullptr; // one tightly packed frame on its way into a pitched slot
@@ -280,6 +280,9 @@ struct dsm_handle {
     void *d_field = nullptr;
     size_t field_bytes = 0;
     std::vector<float> field_table;
+    // dsm_grid_carve: the frames' matrices and plane offsets as built on the host, until the call has synchronised (the device copy
+    // lies in d_pub)
+    std::vector<CarveFrame> carve_frames;
     // dsm_align_equations / dsm_align_frame: none before the first call -- the 29 sums on the device and their page-locked landing
     // place, and (dsm_align_frame, grow-only) the rendered model planes: align_px depths, then 3 * align_px normal components
     unsigned long long *d_align_sums = nullptr;
@@ -2451,6 +2454,121 @@ int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32
     if ((rc = dsm_grid_compose(h, select, n_segments, store_begin, store_count, spec, 0, &occupied, 1, &n, &cells))) return rc;
     if ((rc = field_run(h, bits, nx, ny, nz, max_dist, spec->voxel, planes, dst_on_device != 0, l))) return rc;
     *n_surfels = n;
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ free space, the three states, the frontier (dsm_k_carve.h)
+
+void dsm_carve_params_init(dsm_carve_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = (uint32_t)sizeof(dsm_carve_params);
+    p->near_dist = 0.1f;
+    p->far_dist = 10.0f;
+    p->margin = 0.1732051f; // one voxel diagonal of a 0.1 m grid
+}
+
+int dsm_grid_carve(dsm_handle *h, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags, int32_t n_frames,
+                   const int32_t *slots, const float *poses16, const float *poses_inv16, void *free_device, int64_t *n_free) {
+    if (!h) return DSM_E_INVALID;
+    if (!spec || !params || !slots || !poses16) return fail(h, DSM_E_INVALID, "grid carve: null spec, params, slots or poses");
+    if (!free_device || ((uintptr_t)free_device & 3)) return fail(h, DSM_E_INVALID, "grid carve: the free set is null or not 4-byte aligned");
+    if (flags & ~(uint32_t)(DSM_CARVE_REPLACE | DSM_CARVE_TRUST_INFINITE)) return fail(h, DSM_E_INVALID, "carve flags 0x%x", flags);
+    if (int bad = grid_spec_check(h, spec)) return bad;
+    if (params->struct_size != sizeof(dsm_carve_params))
+        return fail(h, DSM_E_INVALID, "dsm_carve_params struct_size %u, not %zu", params->struct_size, sizeof(dsm_carve_params));
+    if (!(params->near_dist > 0.0f) || !(params->near_dist < params->far_dist) || !std::isfinite(params->far_dist))
+        return fail(h, DSM_E_INVALID, "carve depth range (%g, %g)", (double)params->near_dist, (double)params->far_dist);
+    if (!(params->margin >= 0.0f) || !std::isfinite(params->margin)) return fail(h, DSM_E_INVALID, "carve margin %g", (double)params->margin);
+    if (n_frames < 1 || n_frames > kCarveMaxFrames) return fail(h, DSM_E_INVALID, "carve of %d frames, outside 1..%d", n_frames, kCarveMaxFrames);
+    for (int f = 0; f < n_frames; f++) {
+        if (slots[f] < 0 || slots[f] >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slots[f], h->hc.n_slots);
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(poses16[16 * f + k]) || (poses_inv16 && !std::isfinite(poses_inv16[16 * f + k])))
+                return fail(h, DSM_E_INVALID, "carve frame %d: pose entry %d is not finite", f, k);
+    }
+    int rc = bind_device(h);
+    if (rc) return rc;
+    constexpr size_t kFrameInts = sizeof(CarveFrame) / sizeof(int32_t);
+    if ((rc = pub_reserve(h, 64 + kFrameInts * kCarveMaxFrames, 0))) return rc;
+    if ((rc = pub_order_dst(h))) return rc;
+    {   // behind the asynchronous uploads that wrote the slots (the fuses only read them)
+        int lo, hi;
+        slot_range(slots, n_frames, &lo, &hi);
+        const ReadSlots reads(h, lo, hi);
+        if ((rc = wait_uploads(h, h->stream, kSerialBit))) return rc;
+    }
+    h->carve_frames.resize((size_t)n_frames);
+    for (int f = 0; f < n_frames; f++) {
+        CarveFrame &cf = h->carve_frames[(size_t)f];
+        if (poses_inv16) memcpy(cf.inv, poses_inv16 + 16 * f, sizeof cf.inv);
+        else inverse4<float>(poses16 + 16 * f, cf.inv);
+        cf.depth_off = (int64_t)slots[f] * h->hc.slot_elems;
+    }
+    unsigned long long *d_count = (unsigned long long *)h->d_pub;
+    CarveFrame *d_frames = (CarveFrame *)(h->d_pub + 64);
+    HIP_TRY(h, hipMemcpyAsync(d_frames, h->carve_frames.data(), sizeof(CarveFrame) * (size_t)n_frames, hipMemcpyHostToDevice, h->stream));
+    CarveConst c;
+    memset(&c, 0, sizeof c);
+    for (int a = 0; a < 3; a++) c.origin[a] = spec->origin[a];
+    c.voxel = spec->voxel;
+    c.w = h->hc.w; c.h = h->hc.h; c.pitch = h->hc.pitch;
+    c.fx = h->cfg.fx; c.fy = h->cfg.fy; c.cx = h->cfg.cx; c.cy = h->cfg.cy;
+    c.near_d = params->near_dist; c.far_d = params->far_dist; c.margin = params->margin;
+    c.flags = flags;
+    const hipError_t e = launch_carve((const float *)h->hc.depth_base, d_frames, n_frames, c, spec->nx, spec->ny, spec->nz, (uint32_t *)free_device, d_count,
+                                      h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "carve launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[8], d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    // the call returns when the set is there: nothing enqueued later (an upload into one of the slots) can overtake the reads
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (n_free) memcpy(n_free, &h->h_scalars[8], sizeof(int64_t));
+    return DSM_OK;
+}
+
+int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const void *occupied_device, const void *free_device,
+                      const dsm_space_planes *planes_device, int32_t *n_frontier) {
+    if (!h || !n_frontier) return DSM_E_INVALID;
+    if (!occupied_device || !free_device || !planes_device) return fail(h, DSM_E_INVALID, "grid classify: null source or planes");
+    if ((((uintptr_t)occupied_device | (uintptr_t)free_device) & 3)) return fail(h, DSM_E_INVALID, "grid classify: a bit set is not 4-byte aligned");
+    if (!grid_dims_ok(nx, ny, nz)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", nx, ny, nz);
+    const dsm_space_planes &p = *planes_device;
+    if (!p.state && !p.known_free && !p.frontier && !p.cells) return fail(h, DSM_E_INVALID, "grid classify: no output plane");
+    if (p.cells && p.cells_cap < 0) return fail(h, DSM_E_INVALID, "cells_cap %d", p.cells_cap);
+    if ((((uintptr_t)p.known_free | (uintptr_t)p.frontier | (uintptr_t)p.cells) & 3)) return fail(h, DSM_E_INVALID, "grid classify: a device plane is not 4-byte aligned");
+    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
+    const size_t cells_cap = p.cells ? ((size_t)p.cells_cap < n_vox ? (size_t)p.cells_cap : n_vox) : 0; // (no more cells than voxels)
+    {
+        const uintptr_t q[4] = {(uintptr_t)p.state, (uintptr_t)p.known_free, (uintptr_t)p.frontier, (uintptr_t)p.cells};
+        const size_t bytes[4] = {n_vox, n_words * sizeof(uint32_t), n_words * sizeof(uint32_t), cells_cap * sizeof(int32_t)};
+        const uintptr_t src[2] = {(uintptr_t)occupied_device, (uintptr_t)free_device};
+        for (int a = 0; a < 4; a++) {
+            if (!q[a]) continue;
+            for (int b = a + 1; b < 4; b++)
+                if (q[a] == q[b]) return fail(h, DSM_E_INVALID, "grid classify: two output planes are the same memory");
+            for (int s = 0; s < 2; s++)
+                if (q[a] < src[s] + n_words * sizeof(uint32_t) && src[s] < q[a] + (bytes[a] ? bytes[a] : 1))
+                    return fail(h, DSM_E_INVALID, "grid classify: a plane overlaps a source");
+        }
+    }
+    int rc = bind_device(h);
+    if (rc) return rc;
+    // scratch: the frontier words where the caller takes none, then the tile counts of the cell list
+    const size_t tiles = (n_words + 255) / 256;
+    const size_t at_tiles = p.frontier ? 0 : (n_words + 3) & ~(size_t)3;
+    if ((rc = pub_reserve(h, 64, 0))) return rc;
+    if ((rc = grid_reserve(h, 0, (at_tiles + tiles) * sizeof(uint32_t)))) return rc;
+    if ((rc = pub_order_dst(h))) return rc;
+    uint32_t *scratch = (uint32_t *)h->d_grid_planes;
+    int32_t *d_total = h->d_pub + 32;
+    const hipError_t e = launch_space((const uint32_t *)occupied_device, (const uint32_t *)free_device, nx, ny, nz, p.state, p.known_free,
+                                      p.frontier ? p.frontier : scratch, p.cells, (int)cells_cap, (int32_t *)(scratch + at_tiles), d_total, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "classify launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[7], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const int32_t cells = h->h_scalars[7];
+    *n_frontier = cells;
+    if (p.cells && cells > p.cells_cap) return fail(h, DSM_E_CAPACITY, "%d frontier cells, room for %d", cells, p.cells_cap);
     return DSM_OK;
 }
 

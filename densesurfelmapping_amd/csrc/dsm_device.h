@@ -273,6 +273,21 @@ hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int n
 hipError_t launch_field(const uint32_t *bits, int nx, int ny, int nz, int r, const float *table, int8_t *ox, uint32_t *mid, uint16_t *dist2,
                         int32_t *nearest, float *distance, hipStream_t st);
 
+// ---- free space carved by depth frames, the three-state map and its frontier (dsm_k_carve.h; the definition is carve_voxel of dsm_carve.h)
+struct CarveFrame {    // 72 bytes, in device memory: one per frame of the call
+    float inv[16];     // world -> camera, column-major
+    int64_t depth_off; // elements from the depth base to the frame's plane
+};
+// bits |= the voxels that carve_voxel frees against any of the n_frames frames (c.flags & kCarveReplace: bits = those voxels); pad bits
+// are written 0.  c: everything but inv.  *count = the population of bits afterwards (cleared on `st` first).
+hipError_t launch_carve(const float *depth_base, const CarveFrame *frames, int n_frames, const CarveConst &c, int nx, int ny, int nz, uint32_t *bits,
+                        unsigned long long *count, hipStream_t st);
+// occ / fre: [nz][ny][wx] words, pad bits ignored.  frontier ([nz][ny][wx]) is always written: the list and the count are taken from
+// it; state ([nz][ny][nx] bytes), known_free and cells may be null.  cell_tiles: (words + 255) / 256 ints of scratch; *cells_total =
+// the number of frontier voxels; no cell is written at or beyond cells_cap.
+hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, int nx, int ny, int nz, uint8_t *state, uint32_t *known_free, uint32_t *frontier,
+                        int32_t *cells, int cells_cap, int32_t *cell_tiles, int32_t *cells_total, hipStream_t st);
+
 // ---- a depth frame against the rendered map (dsm_k_align.h; the definition is align_pixel of dsm_align.h)
 // One evaluation: clears sums[29] on `st`, then adds the fixed-point terms of every sampled pixel of the frame plane `depth`
 // ([h][pitch]) that passes align_pixel against the model planes zm [mh][mw] and nm [mh][mw][3].  c from align_prepare, with T set.

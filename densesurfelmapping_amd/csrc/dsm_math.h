@@ -1036,3 +1036,5 @@ DSM_HD int chunk_of(int n, int i) {
 
 // a depth frame against the rendered map: align_pixel and the 29 fixed-point sums, the 6x6 step and the loop
 #include "dsm_align.h"
+// free space carved out of the grid by depth frames: carve_voxel, and the three states of a voxel
+#include "dsm_carve.h"

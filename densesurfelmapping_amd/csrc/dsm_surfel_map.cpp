@@ -286,6 +286,7 @@ int warp_surfels(dsm_surfel_map *m) {
         ENGINE_TRY(m, dsm_store_warp(m->engine, n_groups, offsets.data(), mats.data(), changed.data()));
     }
     ENGINE_TRY(m, dsm_map_warp(m->engine, warp_pose)); // :750-789, :815-819
+    if (m->on_warped) return m->on_warped(m); // (dsm_surfel_map_set_free_space: space carved with the old poses is stale)
     return DSM_OK;
 }
 
@@ -359,6 +360,9 @@ int synchronize_msgs(dsm_surfel_map *m) {
     m->pose_reference_buffer.pop_front(); // :163
     m->frames_fused++;
     // :189-197 publish results (dsm_surfel_map_set_publish; nothing to do unless it installed a publisher)
+    if (m->on_carve) { // (dsm_surfel_map_set_free_space: the frame just fused into the accumulated free set)
+        if (const int bad = m->on_carve(m)) return bad;
+    }
     if (m->on_fused) return m->on_fused(m);
     return DSM_OK;
 }
@@ -475,6 +479,7 @@ int dsm_surfel_map_create(const dsm_surfel_map_config *cfg, dsm_surfel_map **out
 
 void dsm_surfel_map_destroy(dsm_surfel_map *m) {
     if (!m) return;
+    if (m->release_space) m->release_space(m);
     dsm_destroy(m->engine);
     for (const Frame &f : m->image_buffer) m->image_pool.release(f);
     for (const Frame &f : m->depth_buffer) m->depth_pool.release(f);

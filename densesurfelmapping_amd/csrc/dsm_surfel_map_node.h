@@ -1,6 +1,7 @@
 // dsm_surfel_map_node.h -- the state of the node (include/dsm_surfel_map.h), shared by its two translation units:
 // dsm_surfel_map.cpp (the host logic of class SurfelMap), dsm_surfel_map_clouds.cpp (the point-cloud publications),
-// dsm_surfel_map_mesh.cpp, dsm_surfel_map_render.cpp and dsm_surfel_map_align.cpp (the mesh, the rendered images, the alignment).
+// dsm_surfel_map_mesh.cpp, dsm_surfel_map_render.cpp and dsm_surfel_map_align.cpp (the mesh, the rendered images, the alignment),
+// dsm_surfel_map_grid.cpp, dsm_surfel_map_field.cpp and dsm_surfel_map_space.cpp (the voxel grid, its distance field, free space).
 // dsm_surfel_map.cpp calls only the engine entry points it always called; the publications reach it through the function
 // pointers of struct dsm_surfel_map.  Internal: not installed, not part of the C ABI.
 #pragma once
@@ -144,6 +145,14 @@ struct dsm_surfel_map {
     int (*on_fused)(dsm_surfel_map *m) = nullptr;
     void (*release_publish)(dsm_surfel_map *m) = nullptr;
     void *publish = nullptr; // the publisher's own state
+    // dsm_surfel_map_set_free_space (dsm_surfel_map_space.cpp) installs these: on_carve at the fuse site, before on_fused (the fused
+    // frame into the accumulated free set); on_warped after a warp_surfels that went through (the set is stale: cleared and counted);
+    // release_space by dsm_surfel_map_destroy.  Null (the default): no extra work, no synchronisation.
+    int (*on_carve)(dsm_surfel_map *m) = nullptr;
+    int (*on_warped)(dsm_surfel_map *m) = nullptr;
+    void (*release_space)(dsm_surfel_map *m) = nullptr;
+    void *space = nullptr; // the accumulator's own state
+    int64_t free_space_resets = 0;
 };
 
 namespace dsm_node {

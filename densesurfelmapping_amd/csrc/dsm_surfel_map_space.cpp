@@ -1,0 +1,246 @@
+// dsm_surfel_map_space.cpp -- the node's free and unknown space (include/dsm_surfel_map.h: dsm_surfel_map_set_free_space,
+// _free_space*, _space*, _carve_last) over the engine's dsm_grid_carve and dsm_grid_classify.  The accumulator is a bit set in
+// device memory that this file owns; dsm_surfel_map.cpp reaches it through the function pointers of struct dsm_surfel_map
+// (on_carve at the fuse site, on_warped after a warp, release_space at destruction), all null until dsm_surfel_map_set_free_space
+// installs them.  The per-fuse carve is the SYNCHRONISING dsm_grid_carve: it is enqueued behind the fuse on the engine's stream and
+// has returned before the slot's next upload is issued.  The set is cleared and copied on the null stream; dsm_grid_carve orders
+// itself behind that stream (a caller's device memory), so a clear cannot overtake or be overtaken by a carve.
+#include "dsm_surfel_map_node.h"
+
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+namespace {
+
+using namespace dsm_node;
+
+struct Space {
+    dsm_grid_spec spec;
+    dsm_carve_params params;
+    uint32_t flags = 0;
+    size_t n_words = 0, n_vox = 0;
+    uint32_t *d_free = nullptr; // the accumulated set, [nz][ny][wx]
+    uint32_t *d_occ = nullptr;  // dsm_surfel_map_space: the occupied set of the same spec (allocated at its first call)
+    uint8_t *d_tmp = nullptr;   // dsm_surfel_map_space with host planes: their device staging, grow-only
+    size_t tmp_bytes = 0;
+    int64_t n_free = 0;
+    int64_t frames = 0; // frames carved since the set was last cleared
+};
+
+int space_fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    m->err = buf;
+    return code;
+}
+
+#define SPACE_HIP(m, call)                                                                                     \
+    do {                                                                                                       \
+        const hipError_t e_ = (call);                                                                          \
+        if (e_ != hipSuccess) return space_fail(m, DSM_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+void release(dsm_surfel_map *m) {
+    Space *s = (Space *)m->space;
+    if (!s) return;
+    if (hipSetDevice(m->cfg.device) == hipSuccess) {
+        if (s->d_free) (void)hipFree(s->d_free);
+        if (s->d_occ) (void)hipFree(s->d_occ);
+        if (s->d_tmp) (void)hipFree(s->d_tmp);
+    }
+    delete s;
+    m->space = nullptr;
+    m->on_carve = nullptr;
+    m->on_warped = nullptr;
+    m->release_space = nullptr;
+}
+
+int clear(dsm_surfel_map *m, Space *s) {
+    SPACE_HIP(m, hipSetDevice(m->cfg.device));
+    SPACE_HIP(m, hipMemset(s->d_free, 0, s->n_words * sizeof(uint32_t)));
+    s->n_free = 0;
+    s->frames = 0;
+    return DSM_OK;
+}
+
+// the fuse site of synchronize_msgs: m->last is the frame just fused
+int carve_fused(dsm_surfel_map *m) {
+    Space *s = (Space *)m->space;
+    const int32_t slot = m->last.slot;
+    const int rc = dsm_grid_carve(m->engine, &s->spec, &s->params, s->flags, 1, &slot, m->last.pose16, nullptr, s->d_free, &s->n_free);
+    if (rc) return space_fail(m, rc, "dsm_grid_carve: %s", dsm_last_error(m->engine));
+    s->frames++;
+    return DSM_OK;
+}
+
+// after warp_surfels: what was carved with the old poses is stale
+int warped(dsm_surfel_map *m) {
+    Space *s = (Space *)m->space;
+    m->free_space_resets++;
+    return clear(m, s);
+}
+
+// what dsm_grid_carve would refuse of these, before anything is changed
+const char *request_error(const dsm_grid_spec *spec, const dsm_carve_params *p, uint32_t flags) {
+    if (spec->struct_size != sizeof(dsm_grid_spec)) return "dsm_grid_spec struct_size";
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(spec->origin[a])) return "grid origin not finite";
+    if (!std::isfinite(spec->voxel) || !(spec->voxel > 0.0f)) return "grid voxel not finite or not positive";
+    if (spec->nx < 1 || spec->ny < 1 || spec->nz < 1) return "a grid dimension below 1";
+    const int64_t xy = (int64_t)spec->nx * spec->ny, limit = (int64_t)1 << 28;
+    if (xy > limit || xy * spec->nz > limit) return "more than 2^28 voxels";
+    if (spec->inflate < 0 || spec->inflate > 16) return "grid inflate outside 0..16";
+    if (p->struct_size != sizeof(dsm_carve_params)) return "dsm_carve_params struct_size";
+    if (!(p->near_dist > 0.0f) || !(p->near_dist < p->far_dist) || !std::isfinite(p->far_dist)) return "carve depth range";
+    if (!(p->margin >= 0.0f) || !std::isfinite(p->margin)) return "carve margin";
+    if (flags & ~(uint32_t)DSM_CARVE_TRUST_INFINITE) return "flags other than DSM_CARVE_TRUST_INFINITE";
+    return nullptr;
+}
+
+// the accumulator, or null with the error set
+Space *ready(dsm_surfel_map *m, int *rc) {
+    if (!m->space) {
+        *rc = space_fail(m, DSM_E_STATE, "free space is not switched on (dsm_surfel_map_set_free_space)");
+        return nullptr;
+    }
+    if (!m->last.valid) {
+        *rc = space_fail(m, DSM_E_STATE, "no frame fused yet");
+        return nullptr;
+    }
+    return (Space *)m->space;
+}
+
+int space(dsm_surfel_map *m, int kind, const dsm_space_planes *planes, int on_device, int32_t *n_surfels, int32_t *n_frontier) {
+    if (!m || !planes) return DSM_E_INVALID;
+    int rc = DSM_OK;
+    Space *s = ready(m, &rc);
+    if (!s) return rc;
+    int select = DSM_CLOUD_SELECT_NONE;
+    std::vector<int32_t> begin, count;
+    if (!render_runs(m, kind, select, begin, count)) return space_fail(m, DSM_E_INVALID, "space kind %d", kind);
+    if (!planes->state && !planes->known_free && !planes->frontier && !planes->cells) return space_fail(m, DSM_E_INVALID, "no output plane");
+    if (planes->cells && planes->cells_cap < 0) return space_fail(m, DSM_E_INVALID, "cells_cap %d", planes->cells_cap);
+    SPACE_HIP(m, hipSetDevice(m->cfg.device));
+    if (!s->d_occ) SPACE_HIP(m, hipMalloc((void **)&s->d_occ, s->n_words * sizeof(uint32_t)));
+    const dsm_grid_planes occupied = {s->d_occ, nullptr, nullptr, nullptr, 0};
+    int32_t n = 0, cells = 0, nf = 0;
+    rc = dsm_grid_compose(m->engine, select, (int32_t)begin.size(), begin.data(), count.data(), &s->spec, 0, &occupied, 1, &n, &cells);
+    if (rc) return space_fail(m, rc, "dsm_grid_compose: %s", dsm_last_error(m->engine));
+    if (n_surfels) *n_surfels = n;
+    const int nx = s->spec.nx, ny = s->spec.ny, nz = s->spec.nz;
+    if (on_device) {
+        rc = dsm_grid_classify(m->engine, nx, ny, nz, s->d_occ, s->d_free, planes, &nf);
+        if (n_frontier) *n_frontier = nf;
+        return rc ? space_fail(m, rc, "dsm_grid_classify: %s", dsm_last_error(m->engine)) : DSM_OK;
+    }
+    // host planes: staged on the device, each part from a 256-byte boundary
+    const size_t cap = planes->cells ? ((size_t)planes->cells_cap < s->n_vox ? (size_t)planes->cells_cap : s->n_vox) : 0;
+    size_t at = 0;
+    const auto take = [&](bool here, size_t bytes) { const size_t was = at; if (here) at += (bytes + 255) & ~(size_t)255; return was; };
+    const size_t at_state = take(planes->state != nullptr, s->n_vox);
+    const size_t at_kf = take(planes->known_free != nullptr, s->n_words * sizeof(uint32_t));
+    const size_t at_fr = take(planes->frontier != nullptr, s->n_words * sizeof(uint32_t));
+    const size_t at_cells = take(planes->cells != nullptr, (cap ? cap : 1) * sizeof(int32_t));
+    if (at > s->tmp_bytes) {
+        if (s->d_tmp) (void)hipFree(s->d_tmp);
+        s->d_tmp = nullptr;
+        s->tmp_bytes = 0;
+        SPACE_HIP(m, hipMalloc((void **)&s->d_tmp, at));
+        s->tmp_bytes = at;
+    }
+    dsm_space_planes dev = {nullptr, nullptr, nullptr, nullptr, 0};
+    if (planes->state) dev.state = s->d_tmp + at_state;
+    if (planes->known_free) dev.known_free = (uint32_t *)(s->d_tmp + at_kf);
+    if (planes->frontier) dev.frontier = (uint32_t *)(s->d_tmp + at_fr);
+    if (planes->cells) { dev.cells = (int32_t *)(s->d_tmp + at_cells); dev.cells_cap = (int32_t)cap; }
+    rc = dsm_grid_classify(m->engine, nx, ny, nz, s->d_occ, s->d_free, &dev, &nf);
+    if (n_frontier) *n_frontier = nf;
+    if (rc && rc != DSM_E_CAPACITY) return space_fail(m, rc, "dsm_grid_classify: %s", dsm_last_error(m->engine));
+    if (planes->state) SPACE_HIP(m, hipMemcpy(planes->state, dev.state, s->n_vox, hipMemcpyDeviceToHost));
+    if (planes->known_free) SPACE_HIP(m, hipMemcpy(planes->known_free, dev.known_free, s->n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (planes->frontier) SPACE_HIP(m, hipMemcpy(planes->frontier, dev.frontier, s->n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const size_t n_out = (size_t)nf < cap ? (size_t)nf : cap;
+    if (planes->cells && n_out) SPACE_HIP(m, hipMemcpy(planes->cells, dev.cells, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (planes->cells && nf > planes->cells_cap) return space_fail(m, DSM_E_CAPACITY, "%d frontier cells, room for %d", nf, planes->cells_cap);
+    return DSM_OK;
+}
+
+int free_space(dsm_surfel_map *m, void *dst, int on_device, int64_t *n_free) {
+    if (!m || !dst) return DSM_E_INVALID;
+    int rc = DSM_OK;
+    Space *s = ready(m, &rc);
+    if (!s) return rc;
+    if (on_device && ((uintptr_t)dst & 3)) return space_fail(m, DSM_E_INVALID, "the destination is not 4-byte aligned");
+    SPACE_HIP(m, hipSetDevice(m->cfg.device));
+    SPACE_HIP(m, hipMemcpy(dst, s->d_free, s->n_words * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    if (on_device) SPACE_HIP(m, hipStreamSynchronize(nullptr));
+    if (n_free) *n_free = s->n_free;
+    return DSM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int dsm_surfel_map_set_free_space(dsm_surfel_map *m, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags) {
+    if (!m) return DSM_E_INVALID;
+    if (!spec) {
+        release(m);
+        return DSM_OK;
+    }
+    dsm_carve_params p;
+    if (params) p = *params;
+    else dsm_carve_params_init(&p);
+    if (const char *bad = request_error(spec, &p, flags)) return space_fail(m, DSM_E_INVALID, "set_free_space: %s", bad);
+    const size_t n_words = (size_t)((spec->nx + 31) / 32) * (size_t)spec->ny * (size_t)spec->nz;
+    if (hipSetDevice(m->cfg.device) != hipSuccess) return space_fail(m, DSM_E_HIP, "set_free_space: cannot select device %d", m->cfg.device);
+    uint32_t *d_free = nullptr;
+    SPACE_HIP(m, hipMalloc((void **)&d_free, n_words * sizeof(uint32_t)));
+    release(m); // (the old accumulator, if any: a new spec starts from an empty set)
+    Space *s = new Space();
+    s->spec = *spec;
+    s->params = p;
+    s->flags = flags;
+    s->n_words = n_words;
+    s->n_vox = (size_t)spec->nx * (size_t)spec->ny * (size_t)spec->nz;
+    s->d_free = d_free;
+    m->space = s;
+    m->on_carve = carve_fused;
+    m->on_warped = warped;
+    m->release_space = release;
+    return clear(m, s);
+}
+
+int64_t dsm_surfel_map_free_space_resets(const dsm_surfel_map *m) { return m ? m->free_space_resets : 0; }
+
+int dsm_surfel_map_free_space(dsm_surfel_map *m, uint32_t *free_out, int64_t *n_free) { return free_space(m, free_out, 0, n_free); }
+
+int dsm_surfel_map_free_space_device(dsm_surfel_map *m, void *free_device, int64_t *n_free) { return free_space(m, free_device, 1, n_free); }
+
+int dsm_surfel_map_space(dsm_surfel_map *m, int kind, const dsm_space_planes *planes, int32_t *n_surfels, int32_t *n_frontier) {
+    return space(m, kind, planes, 0, n_surfels, n_frontier);
+}
+
+int dsm_surfel_map_space_device(dsm_surfel_map *m, int kind, const dsm_space_planes *planes_device, int32_t *n_surfels, int32_t *n_frontier) {
+    return space(m, kind, planes_device, 1, n_surfels, n_frontier);
+}
+
+int dsm_surfel_map_carve_last(dsm_surfel_map *m, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags, void *free_device) {
+    if (!m || !spec || !free_device) return DSM_E_INVALID;
+    if (!m->last.valid) return space_fail(m, DSM_E_STATE, "no frame fused yet");
+    dsm_carve_params p;
+    if (params) p = *params;
+    else dsm_carve_params_init(&p);
+    const int32_t slot = m->last.slot;
+    const int rc = dsm_grid_carve(m->engine, spec, &p, flags, 1, &slot, m->last.pose16, nullptr, free_device, nullptr);
+    return rc ? space_fail(m, rc, "dsm_grid_carve: %s", dsm_last_error(m->engine)) : DSM_OK;
+}
+
+} // extern "C"

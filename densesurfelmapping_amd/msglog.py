@@ -21,6 +21,11 @@ tests/cpp/node_replay_test.cpp reads the same format through include/dsm_surfel_
 --save-field PATH.npz writes the truncated Euclidean distance field of that grid's occupied set out to --field-max-dist R voxels
 (same --grid-voxel and --grid-dims): origin, voxel, dims, max_dist, dist2, nearest, distance.
 
+--save-space PATH.npz switches the node's free-space accumulator on before the replay, in a grid of --grid-dims voxels of --grid-voxel
+metres around the FIRST pose of the log (--carve-near N, --carve-far F, --carve-margin M: the carve's range and clearance), and writes
+origin, voxel, dims, near, far, margin, state [nz][ny][nx] (0 unknown, 1 free, 2 occupied), frontier_cells, free, n_free and resets
+(how often a loop closure cleared the set: after one it holds only the frames fused since).
+
 --eigen-products 3.3 fuses with the 3x3 products in the order of a reference built against Eigen >= 3.3
 (DSM_FLAG_EIGEN33_PRODUCTS); the default, 3.2, is the order of Eigen 3.2, as without the flag.
 """
@@ -94,16 +99,22 @@ EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-pro
 
 
 def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None, align=None,
-           save_grid=None, grid_voxel=0.1, grid_dims=(64, 64, 32), grid_inflate=0, save_field=None, field_max_dist=16):
+           save_grid=None, grid_voxel=0.1, grid_dims=(64, 64, 32), grid_inflate=0, save_field=None, field_max_dist=16,
+           save_space=None, carve_near=None, carve_far=None, carve_margin=None):
     """Feed a log to a SurfelMap on the GPU; returns a summary dict.  align = a cloud kind: after every fused frame that frame is
     aligned against the surfels of that kind at the pose it was fused with (SurfelMap.align_last, the library's defaults) and a
     JSON line says how it went; the poses fed to the map are not changed.  save_grid: the whole map as an occupancy grid of grid_dims voxels
     of grid_voxel metres around the final fuse pose (SurfelMap.grid), as an .npz.  save_field: the distance field of that grid's occupied
-    set out to field_max_dist voxels (SurfelMap.field), as an .npz."""
+    set out to field_max_dist voxels (SurfelMap.field), as an .npz.  save_space: the free-space accumulator is switched on before the
+    replay, in a grid of grid_dims voxels around the first pose of the log, and the three-state map and its frontier are written as an
+    .npz (SurfelMap.set_free_space / space)."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
     node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity,
                                 engine_flags=EIGEN_PRODUCTS[eigen_products])
+    if save_space:  # (the node turns the SLAM frame so that the first camera sits at the world's origin: the grid lies around it)
+        carve = {k: v for k, v in (("near_dist", carve_near), ("far_dist", carve_far), ("margin", carve_margin)) if v is not None}
+        node.set_free_space(api.grid_spec_around((0.0, 0.0, 0.0), grid_voxel, tuple(grid_dims)), carve)
     n = 0
     for ev in events:
         fused = node.frames_fused
@@ -139,6 +150,14 @@ def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, e
         np.savez(save_field, origin=np.array(sp.origin[:], np.float32), voxel=np.float32(sp.voxel), dims=np.array([sp.nx, sp.ny, sp.nz], np.int32),
                  max_dist=np.int32(field_max_dist), dist2=f["dist2"], nearest=f["nearest"], distance=f["distance"])
         out["field_near"] = int((f["dist2"] != api.FIELD_FAR).sum())
+    if save_space:  # the three states and the frontier of the accumulator's grid
+        sp = node.space("all")
+        free, n_free = node.free_space()
+        g, p = sp["spec"], api.carve_params(carve)
+        np.savez(save_space, origin=np.array(g.origin[:], np.float32), voxel=np.float32(g.voxel), dims=np.array([g.nx, g.ny, g.nz], np.int32),
+                 near=np.float32(p.near_dist), far=np.float32(p.far_dist), margin=np.float32(p.margin), state=sp["state"], frontier_cells=sp["cells"],
+                 free=free, n_free=np.int64(n_free), resets=np.int64(node.free_space_resets))
+        out["free_voxels"], out["frontier_cells"], out["free_space_resets"] = int(n_free), int(sp["n_frontier"]), node.free_space_resets
     node.close()
     return out
 
@@ -160,6 +179,12 @@ def main():
     ap.add_argument("--save-field", metavar="PATH.npz", help="the truncated Euclidean distance field of the occupied set of the --grid-voxel / --grid-dims "
                     "grid around the final fuse pose: origin, voxel, dims, max_dist and the planes dist2, nearest, distance [nz][ny][nx]")
     ap.add_argument("--field-max-dist", type=int, default=16, metavar="R", help="truncation radius of --save-field in voxels, 1..64 (default 16)")
+    ap.add_argument("--save-space", metavar="PATH.npz", help="accumulate free space from every fused frame in the --grid-voxel / --grid-dims grid around the "
+                    "first pose: origin, voxel, dims, state [nz][ny][nx] (0 unknown, 1 free, 2 occupied), frontier_cells, free, n_free, resets")
+    ap.add_argument("--carve-near", type=float, default=None, metavar="N", help="nearest depth carved, metres (default: the library's, 0.1)")
+    ap.add_argument("--carve-far", type=float, default=None, metavar="F", help="farthest depth carved, metres (default: the library's, 10)")
+    ap.add_argument("--carve-margin", type=float, default=None, metavar="M", help="clearance kept in front of the measured surface, metres "
+                    "(default: the library's, one voxel diagonal of a 0.1 m grid)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
                     help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
@@ -171,7 +196,8 @@ def main():
     print(json.dumps(replay(args.log, args.save_cloud, args.save_mesh, device=args.device, eigen_products=args.eigen_products,
                             save_mesh_binary=args.save_mesh_binary, render=args.render, align=args.align,
                             save_grid=args.save_grid, grid_voxel=args.grid_voxel, grid_dims=args.grid_dims, grid_inflate=args.grid_inflate,
-                            save_field=args.save_field, field_max_dist=args.field_max_dist)))
+                            save_field=args.save_field, field_max_dist=args.field_max_dist,
+                            save_space=args.save_space, carve_near=args.carve_near, carve_far=args.carve_far, carve_margin=args.carve_margin)))
 
 
 if __name__ == "__main__":

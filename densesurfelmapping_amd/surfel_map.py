@@ -27,6 +27,8 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_align_last", "dsm_surfel_map_last_pose16",
     "dsm_surfel_map_grid", "dsm_surfel_map_grid_device",
     "dsm_surfel_map_field", "dsm_surfel_map_field_device",
+    "dsm_surfel_map_set_free_space", "dsm_surfel_map_free_space_resets", "dsm_surfel_map_free_space", "dsm_surfel_map_free_space_device",
+    "dsm_surfel_map_space", "dsm_surfel_map_space_device", "dsm_surfel_map_carve_last",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -110,6 +112,15 @@ def _bind(lib):
         if hasattr(lib, "dsm_surfel_map_field"):  # (nor the distance field)
             for name in ("dsm_surfel_map_field", "dsm_surfel_map_field_device"):
                 getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._GridSpec), C.c_int32, C.c_uint32, C.POINTER(api._FieldPlanes), _vp]
+        if hasattr(lib, "dsm_surfel_map_set_free_space"):  # (nor free space)
+            lib.dsm_surfel_map_set_free_space.argtypes = [_vp, C.POINTER(api._GridSpec), C.POINTER(api._CarveParams), C.c_uint32]
+            lib.dsm_surfel_map_free_space_resets.argtypes = [_vp]
+            lib.dsm_surfel_map_free_space_resets.restype = C.c_int64
+            lib.dsm_surfel_map_free_space.argtypes = [_vp, _vp, _vp]
+            lib.dsm_surfel_map_free_space_device.argtypes = [_vp, _vp, _vp]
+            for name in ("dsm_surfel_map_space", "dsm_surfel_map_space_device"):
+                getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._SpacePlanes), _vp, _vp]
+            lib.dsm_surfel_map_carve_last.argtypes = [_vp, C.POINTER(api._GridSpec), C.POINTER(api._CarveParams), C.c_uint32, _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -301,6 +312,70 @@ class SurfelMap:
             return n.value
         out["n_surfels"], out["spec"] = n.value, spec
         return out
+
+    # ---- free and unknown space (dsm_grid_carve, dsm_grid_classify)
+    def set_free_space(self, spec=None, params=None, flags=0):
+        """From the next fuse on every fused frame is carved into a device bit set the node owns, in the grid `spec` (api.grid_spec /
+        grid_spec_around; None: switched off, the default).  params: api.carve_params' forms; flags: 0 or api.CARVE_TRUST_INFINITE.
+        A new spec clears the set, and so does every loop-closure warp (free_space_resets counts those)."""
+        if spec is None:
+            self._space_spec = None
+            self._check(self._lib.dsm_surfel_map_set_free_space(self._h, None, None, 0))
+            return
+        p = api.carve_params(params)
+        self._check(self._lib.dsm_surfel_map_set_free_space(self._h, C.byref(spec), C.byref(p), int(flags)))
+        self._space_spec = spec
+
+    @property
+    def free_space_resets(self) -> int:
+        return int(self._lib.dsm_surfel_map_free_space_resets(self._h))
+
+    def free_space(self, dst_ptr=None):
+        """The accumulated free set: (uint32 [nz, ny, wx], its population count) -- or, with a device pointer, the count."""
+        n = C.c_int64(0)
+        if dst_ptr is not None:
+            self._check(self._lib.dsm_surfel_map_free_space_device(self._h, _vp(dst_ptr), C.byref(n)))
+            return n.value
+        spec = getattr(self, "_space_spec", None)
+        out = np.zeros(api.grid_shapes(spec)[1] if spec is not None else (1, 1, 1), np.uint32)
+        self._check(self._lib.dsm_surfel_map_free_space(self._h, _ptr(out), C.byref(n)))
+        return out, n.value
+
+    def space(self, kind="all", planes=api.SPACE_PLANES, dst_ptrs=None, cells_cap=None):
+        """The occupied set of grid(kind) in the accumulator's grid classified against the accumulated free set.  Returns a dict of
+        the `planes` asked for -- "state" uint8 [nz, ny, nx] (api.SPACE_UNKNOWN / _FREE / _OCCUPIED), "known_free" and "frontier"
+        uint32 [nz, ny, wx], "cells" int32 [n_frontier] (the frontier's linear indices, ascending) -- plus "n_surfels", "n_frontier"
+        and "spec"; cells_cap None: the list is sized by a second call.  With dst_ptrs = {plane: device pointer}: (n_surfels,
+        n_frontier).  More frontier voxels than cells_cap: DsmError with code DSM_E_CAPACITY and .n_frontier = the count needed."""
+        k = self._kind(kind)
+        spec = getattr(self, "_space_spec", None)
+        n, nf = C.c_int32(0), C.c_int32(0)
+        auto = dst_ptrs is None and cells_cap is None and "cells" in planes
+        fn = self._lib.dsm_surfel_map_space if dst_ptrs is None else self._lib.dsm_surfel_map_space_device
+        if spec is None and dst_ptrs is None:  # (the library refuses: nothing to size the arrays by)
+            self._check(fn(self._h, k, C.byref(api._SpacePlanes()), C.byref(n), C.byref(nf)))
+        st, out = api.space_outputs(spec, planes, dst_ptrs, 4096 if auto else cells_cap)
+        rc = fn(self._h, k, C.byref(st), C.byref(n), C.byref(nf))
+        if rc == api.DSM_E_CAPACITY and auto:
+            st, out = api.space_outputs(spec, planes, None, nf.value)
+            rc = fn(self._h, k, C.byref(st), C.byref(n), C.byref(nf))
+        if rc == api.DSM_E_CAPACITY:
+            e = api.DsmError(rc, self._lib.dsm_surfel_map_last_error(self._h).decode())
+            e.n_frontier, e.n_surfels, e.planes = nf.value, n.value, out
+            raise e
+        self._check(rc)
+        if dst_ptrs is not None:
+            return n.value, nf.value
+        if "cells" in out:
+            out["cells"] = out["cells"][: nf.value]
+        out["n_surfels"], out["n_frontier"], out["spec"] = n.value, nf.value, spec
+        return out
+
+    def carve_last(self, spec, free_ptr, params=None, flags=0):
+        """One carve of the latest fused frame, with the pose it was fused with, into the caller's bit set [nz, ny, wx] of the grid
+        `spec` at the device pointer free_ptr (api.FusionFunctions.grid_carve's rules)."""
+        p = api.carve_params(params)
+        self._check(self._lib.dsm_surfel_map_carve_last(self._h, C.byref(spec), C.byref(p), int(flags), _vp(free_ptr)))
 
     # ---- the latest frame against the map (dsm_align_frame)
     def align_last(self, kind="active", pose_guess=None, params=None):

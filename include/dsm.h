@@ -399,6 +399,68 @@ int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32
                       const dsm_grid_spec *spec, int32_t max_dist, uint32_t flags, const dsm_field_planes *planes, int dst_on_device,
                       int32_t *n_surfels);
 
+/* ---- free and unknown space: the grid carved by depth frames, the three-state map and its frontier ----
+ * The occupied set and its field say where surfaces are; they cannot tell a voxel the sensor has seen through from one it has
+ * never observed.  dsm_grid_carve answers "which voxels of this grid does this depth frame see through?" for the frames in the
+ * handle's frame slots.  It is defined PER VOXEL, so no order of execution matters; fp32, non-fused, in the order written:
+ *   1. c = the voxel's centre (c_a = origin_a + ((float)i + 0.5f) * voxel, as for the grid).
+ *   2. q = inv c, with inv the world -> camera matrix: the caller's pose_inv16 bit for bit, or, with NULL, the closed-form inverse
+ *      of pose16 (the rule of dsm_render_compose); q_i = ((inv[i] cx + inv[4 + i] cy) + inv[8 + i] cz) + inv[12 + i].
+ *   3. unless near_dist < q.z && q.z < far_dist (the carve's own range; a NaN fails): not carved.
+ *   4. u = int((q.x * fx) / q.z + cx + 0.5) (in double after the fp32 sum, as the fuse rounds to a pixel), v likewise with fy, cy;
+ *      unless 0 <= u < width && 0 <= v < height: not carved.  The camera is the handle's; a pad column is never read.
+ *   5. d = depth[v][u]; unless d > 0 (a NaN fails): not carved.  d == +inf: not carved, unless DSM_CARVE_TRUST_INFINITE is given
+ *      (a zero disparity then frees the whole range along that ray).
+ *   6. FREE iff (q.z + margin) < d.
+ * Two limits, stated plainly.  (a) The voxel is CENTRE-SAMPLED: one ray, the one through its centre, decides.  A voxel whose
+ * centre projects outside the image or onto a pixel without a measurement stays as it was however much of its volume other pixels
+ * see through; the margin (metres kept clear in front of the measured surface) is what keeps the voxels holding the surface itself
+ * from being freed, so it should not be smaller than a voxel diagonal.  (b) The set is only as good as the poses it was carved
+ * with: a caller that moves its map (a loop closure) has to clear the set and carve again. */
+#define DSM_CARVE_MAX_FRAMES 32
+#define DSM_CARVE_REPLACE 1u        /* the old contents of the set are ignored instead of OR-ed in */
+#define DSM_CARVE_TRUST_INFINITE 2u /* a depth of +inf is a measurement: nothing within far_dist */
+typedef struct dsm_carve_params {
+    uint32_t struct_size; /* sizeof(dsm_carve_params) */
+    float near_dist;      /* 0 < near_dist < far_dist, finite */
+    float far_dist;
+    float margin;         /* >= 0, finite: metres of clearance kept in front of the measured surface */
+} dsm_carve_params;
+/* near_dist 0.1 m, far_dist 10 m, margin 0.1732051 m = one voxel diagonal of a 0.1 m grid */
+void dsm_carve_params_init(dsm_carve_params *p);
+/* free_device |= the union over the n_frames frames of FREE (with DSM_CARVE_REPLACE: free_device = that union).  free_device:
+ * [nz][ny][wx] words in DEVICE memory, read and written; pad bits (x >= nx) are written 0.  slots[i]: the frame slot of frame i,
+ * poses16 + 16 i its cam -> world matrix, poses_inv16 + 16 i (poses_inv16 may be NULL) its inverse.  *n_free (may be NULL) = the
+ * population count of the set after the call.  All frames are tested inside one pass over the set.  Checked before any device work
+ * (DSM_E_INVALID, nothing written): what dsm_grid_compose checks of the spec (inflate is validated and unused), a wrong
+ * struct_size, near_dist / far_dist / margin out of range or not finite, a pose entry that is not finite, a slot outside the
+ * handle's, n_frames outside 1..32, a NULL or not 4-byte aligned set, unknown flags.  Ordered and synchronised like
+ * dsm_grid_inflate, and behind the handle's work so far, the uploads and fuses that touch the slots included.  Synchronises. */
+int dsm_grid_carve(dsm_handle *h, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags, int32_t n_frames,
+                   const int32_t *slots, const float *poses16, const float *poses_inv16, void *free_device, int64_t *n_free);
+
+#define DSM_SPACE_UNKNOWN 0
+#define DSM_SPACE_FREE 1
+#define DSM_SPACE_OCCUPIED 2
+/* device memory; any may be NULL (not written), not all; no two the same memory; the word planes and cells 4-byte aligned */
+typedef struct dsm_space_planes {
+    uint8_t *state;       /* [nz][ny][nx]  DSM_SPACE_UNKNOWN / _FREE / _OCCUPIED; occupied wins over free */
+    uint32_t *known_free; /* [nz][ny][wx]  free & ~occupied; pad bits 0 */
+    uint32_t *frontier;   /* [nz][ny][wx]  the known-free voxels with at least one of the six face neighbours INSIDE the grid
+                                           unknown; pad bits 0 */
+    int32_t *cells;       /* [cells_cap]   the linear indices (z ny + y) nx + x of the frontier voxels, ascending */
+    int32_t cells_cap;    /* >= 0 when cells is not NULL */
+} dsm_space_planes;
+/* The three states and the frontier of two bit sets in DEVICE memory: `occupied` (dsm_grid_compose's) and `free` (carved), both
+ * [nz][ny][wx], pad bits ignored.  Outside the grid nothing is unknown: the grid's own border makes no frontier.  *n_frontier =
+ * the number of frontier voxels, whichever planes are asked for.  More than cells_cap: DSM_E_CAPACITY with *n_frontier = the
+ * count needed; the other planes are complete and nothing is written past the cap.  DSM_E_INVALID before any device work: a NULL
+ * handle, source, planes or n_frontier, a dimension < 1, more than 2^28 voxels, all planes NULL, two planes the same pointer, a
+ * plane overlapping a source, a source, word plane or cells not 4-byte aligned, cells with cells_cap < 0.  Ordered and
+ * synchronised like dsm_grid_inflate.  Synchronises. */
+int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const void *occupied_device, const void *free_device,
+                      const dsm_space_planes *planes_device, int32_t *n_frontier);
+
 /* ---- a depth frame against the map: projective association and point-to-plane alignment (no counterpart in the reference) ----
  * What dsm_render_compose predicts for a camera (the MODEL camera: depth plane Zm, camera-frame normal plane Nm) is compared with
  * the depth plane of a frame slot, whichever upload wrote it.  T is a rigid transform from the frame camera to the model camera,

@@ -192,6 +192,36 @@ int dsm_surfel_map_field(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec,
 int dsm_surfel_map_field_device(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, int32_t max_dist, uint32_t flags,
                                 const dsm_field_planes *planes_device, int32_t *n_surfels);
 
+/* ---- free and unknown space (dsm_grid_carve / dsm_grid_classify of dsm.h, where both are defined) ----
+ * Which voxels the sensor has seen through can only be told from the depth frames while they pass through the node, and the node
+ * decides when a frame is fused and keeps only two of them: so the node accumulates itself, opt-in.  From the next fuse on every
+ * fused frame is carved, with the slot and the pose it was fused with, into a device bit set the node owns (before the
+ * publications of that fuse).  spec NULL: switched off, the memory released (the default: the node then does exactly what it did
+ * without this call).  A new spec -- any call with one -- clears the set.  params NULL: dsm_carve_params_init's.  flags:
+ * DSM_CARVE_TRUST_INFINITE only.  spec, params and flags are checked here as dsm_grid_carve checks them (DSM_E_INVALID, nothing
+ * changed).
+ * LIMIT, a loop closure: the warp that follows one moves the map and rewrites the keyframe poses, so what was carved with the old
+ * poses is stale.  The set is CLEARED at every warp that changes a pose, and dsm_surfel_map_free_space_resets counts how often:
+ * after a reset the set holds only the frames fused since.  Carving again would need the old frames, which the node does not keep.
+ * LIMIT, centre sampling: see dsm_grid_carve. */
+int dsm_surfel_map_set_free_space(dsm_surfel_map *m, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags);
+int64_t dsm_surfel_map_free_space_resets(const dsm_surfel_map *m);
+/* A copy of the accumulated set, [nz][ny][wx] words of the accumulator's spec, into host memory; *n_free (may be NULL) = its
+ * population count.  DSM_E_STATE before dsm_surfel_map_set_free_space or before the first fuse.  Synchronises. */
+int dsm_surfel_map_free_space(dsm_surfel_map *m, uint32_t *free_out, int64_t *n_free);
+/* the same into device memory of the node's GPU (4-byte aligned), ordered like the grid's device destination */
+int dsm_surfel_map_free_space_device(dsm_surfel_map *m, void *free_device, int64_t *n_free);
+/* The occupied set of dsm_surfel_map_grid for `kind` and the accumulator's spec, classified against the accumulated free set:
+ * planes, *n_frontier and DSM_E_CAPACITY as for dsm_grid_classify, but the planes in HOST memory; *n_surfels as for
+ * dsm_surfel_map_grid (either count may be NULL).  DSM_E_STATE before dsm_surfel_map_set_free_space or before the first fuse.
+ * Synchronises. */
+int dsm_surfel_map_space(dsm_surfel_map *m, int kind, const dsm_space_planes *planes, int32_t *n_surfels, int32_t *n_frontier);
+/* the same with the planes in device memory of the node's GPU */
+int dsm_surfel_map_space_device(dsm_surfel_map *m, int kind, const dsm_space_planes *planes_device, int32_t *n_surfels, int32_t *n_frontier);
+/* The stateless counterpart, for callers with their own grid: one dsm_grid_carve of the latest fused frame, with the pose it was
+ * fused with, into the caller's set in device memory.  params NULL: the defaults.  DSM_E_STATE before the first fuse. */
+int dsm_surfel_map_carve_last(dsm_surfel_map *m, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags, void *free_device);
+
 /* ---- the latest frame against the map (dsm_align_frame of dsm.h, where the alignment is defined) ----
  * Aligns the depth frame of the latest fuse, still in its engine slot, against the surfel set of `kind` with the rules and runs of
  * dsm_surfel_map_render (ACTIVE: refine or judge a pose; INACTIVE: verify a loop closure against the inactive map), seen by the

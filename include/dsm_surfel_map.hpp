@@ -293,6 +293,28 @@ class SurfelMap {
         return check(rc);
     }
 
+    // free and unknown space (dsm_grid_carve / dsm_grid_classify of dsm.h; the limits are stated in dsm_surfel_map.h): from the next
+    // fuse on every fused frame is carved into a device bit set the node owns.  spec nullptr: off (the default).  A new spec, and
+    // every loop-closure warp, clears the set; free_space_resets() counts the latter.
+    int set_free_space(const dsm_grid_spec *spec, const dsm_carve_params *params = nullptr, uint32_t flags = 0) {
+        return check(dsm_surfel_map_set_free_space(m_, spec, params, flags));
+    }
+    int64_t free_space_resets() const { return dsm_surfel_map_free_space_resets(m_); }
+    // a copy of the accumulated set, [nz][ny][wx] words of the spec given to set_free_space (the caller sizes the memory)
+    int free_space(uint32_t *free_out, int64_t *n_free = nullptr) { return check(dsm_surfel_map_free_space(m_, free_out, n_free)); }
+    int free_space_device(void *free_device, int64_t *n_free = nullptr) { return check(dsm_surfel_map_free_space_device(m_, free_device, n_free)); }
+    // the occupied set of grid(kind) in the accumulator's grid classified against the accumulated free set; planes in host memory
+    int space(dsm_cloud_kind kind, const dsm_space_planes &planes, int32_t *n_surfels = nullptr, int32_t *n_frontier = nullptr) {
+        return check(dsm_surfel_map_space(m_, kind, &planes, n_surfels, n_frontier));
+    }
+    int space_device(dsm_cloud_kind kind, const dsm_space_planes &planes_device, int32_t *n_surfels = nullptr, int32_t *n_frontier = nullptr) {
+        return check(dsm_surfel_map_space_device(m_, kind, &planes_device, n_surfels, n_frontier));
+    }
+    // one carve of the latest fused frame into a caller's set in device memory: the stateless counterpart
+    int carve_last(const dsm_grid_spec &spec, const dsm_carve_params *params, uint32_t flags, void *free_device) {
+        return check(dsm_surfel_map_carve_last(m_, &spec, params, flags, free_device));
+    }
+
     // the frame of the latest fuse aligned, point to plane, against the surfels of cloud `kind` seen from pose16_guess (cam -> world,
     // column-major; nullptr: the latest fuse's pose): dsm_align_frame of dsm.h.  params nullptr: dsm_align_params_init's defaults.
     // Nothing is changed: what to do with result.pose16 is the caller's decision.
