@@ -24,6 +24,7 @@
 #include "dsm_device.h"
 #include "dsm_frame_copy.h"
 #include "dsm_frame_format.h"
+#include "dsm_ranges.h"
 
 using namespace dsm;
 
@@ -131,6 +132,14 @@ class HostPool {
     Job *job_ = nullptr;
     unsigned gen_ = 0;
     bool stop_ = false;
+};
+
+// Grow-only device scratch of a handle's synchronous calls (scratch_grow): nothing before the first call that needs it, freed by
+// dsm_destroy.  What lies in it lasts for one call: growth drops the contents.
+struct DevScratch {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <typename T> T *as() const { return (T *)p; }
 };
 
 struct dsm_handle {
@@ -252,43 +261,26 @@ struct dsm_handle {
     // shadow the reference publishes and saves (`inactive_pointcloud`)
     dsm_surfel *d_store = nullptr;
     float4 *d_cloud = nullptr;
-    void *d_store_tmp = nullptr;
-    size_t store_tmp_bytes = 0;
     int store_cap = 0, store_n = 0;
-    // point-cloud publications (dsm_cloud_compose / dsm_frame_cloud): grow-only device scratch -- the map part's count, the
-    // tile counts of the compaction and the run table -- and the points on their way to a host destination
-    int32_t *d_pub = nullptr;
-    size_t pub_ints = 0;
-    float4 *d_pub_out = nullptr;
-    size_t pub_out_cap = 0;
+    // the scratch of the synchronous calls, each DevScratch grown by scratch_grow with the headroom its call site states:
+    //   store_tmp      tail copy of dsm_store_erase, argument blocks of the warps
+    //   pub            the words of the map products (PubWords): counts, tile counts of the compaction, the run table
+    //   pub_out        what a product writes on its way to a HOST destination: points, vertices, indices, render planes
+    //   render_keys    dsm_render_compose: the key plane with the ray tables behind it
+    //   render_splats  ... its splat records with the number -> record table behind them
+    //   grid_splats    dsm_grid_compose: the surfel records
+    //   grid_planes    ... the planes the caller did not pass or passed as host memory, the cell list's scan counts behind them
+    //   field          dsm_grid_distance / dsm_field_compose: the distance table, the byte plane of the x pass, the word plane of the
+    //                  y pass, then (dsm_field_compose) the composed bit set and the planes that go to host memory
+    //   align_planes   dsm_align_frame: the rendered model, px depths and then 3 * px normal components
+    //   align_sums     dsm_align_equations / dsm_align_frame: the 29 sums (256 bytes, with their page-locked landing place h_align_sums)
+    DevScratch store_tmp, pub, pub_out, render_keys, render_splats, grid_splats, grid_planes, field, align_planes, align_sums;
     hipEvent_t ev_pub_dst = nullptr; // a device destination is written behind the null stream's work so far (as hipMemcpy would)
-    // dsm_render_compose: grow-only device scratch, none before the first render -- the key plane with the ray tables behind
-    // it (render_px pixels), the splat records and the number -> record table (render_seq surfels)
-    unsigned long long *d_render_keys = nullptr;
-    size_t render_px = 0;
-    void *d_render_splats = nullptr;
-    size_t render_seq = 0;
-    // dsm_grid_compose: grow-only device scratch, none before the first grid -- the surfel records (grid_seq surfels), and the
-    // planes the caller did not pass or passed as host memory with the cell list's scan counts behind them (grid_bytes bytes)
-    void *d_grid_splats = nullptr;
-    size_t grid_seq = 0;
-    void *d_grid_planes = nullptr;
-    size_t grid_bytes = 0;
-    // dsm_grid_distance / dsm_field_compose: grow-only device scratch, none before the first field (field_bytes bytes) -- the
-    // distance table, the byte plane of the x pass, the word plane of the y pass, then (dsm_field_compose) the composed bit set and the
-    // planes that go to host memory; the table as built on the host stays here until the call has synchronised
-    void *d_field = nullptr;
-    size_t field_bytes = 0;
-    std::vector<float> field_table;
+    std::vector<float> field_table; // dsm_field_compose's distance table as built on the host, until the call has synchronised
     // dsm_grid_carve: the frames' matrices and plane offsets as built on the host, until the call has synchronised (the device copy
-    // lies in d_pub)
+    // lies in `pub`)
     std::vector<CarveFrame> carve_frames;
-    // dsm_align_equations / dsm_align_frame: none before the first call -- the 29 sums on the device and their page-locked landing
-    // place, and (dsm_align_frame, grow-only) the rendered model planes: align_px depths, then 3 * align_px normal components
-    unsigned long long *d_align_sums = nullptr;
     int64_t *h_align_sums = nullptr;
-    float *d_align_planes = nullptr;
-    size_t align_px = 0;
     // drop-in calls (dsm_fuse_map / dsm_fuse_initialize_map): page-locked staging owned by the handle
     uint8_t *pin_frame = nullptr; // one frame, image then depth, rows at the frame slots' pitch
     dsm_surfel *pin_map = nullptr; // shadow of the caller's array: what the last drop-in call returned == the device map
@@ -480,15 +472,16 @@ void retire_graphs(dsm_handle *h) {
     h->retired.clear();
 }
 
-// grow-only device scratch of the handle (tail copy of dsm_store_erase, argument blocks of the warps)
-int scratch_reserve(dsm_handle *h, size_t need) {
-    if (need <= h->store_tmp_bytes) return DSM_OK;
+// The one grower of the handle's DevScratch members: room for need_bytes, or -- behind everything the map stream still does with
+// the old block -- a new block of alloc_bytes (>= need_bytes: the call site's headroom).  The contents do not survive.
+int scratch_grow(dsm_handle *h, DevScratch &s, size_t need_bytes, size_t alloc_bytes) {
+    if (need_bytes <= s.bytes) return DSM_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->d_store_tmp) (void)hipFree(h->d_store_tmp);
-    h->d_store_tmp = nullptr;
-    h->store_tmp_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->d_store_tmp, need * 2));
-    h->store_tmp_bytes = need * 2;
+    if (s.p) (void)hipFree(s.p);
+    s.p = nullptr;
+    s.bytes = 0;
+    HIP_TRY(h, hipMalloc(&s.p, alloc_bytes));
+    s.bytes = alloc_bytes;
     return DSM_OK;
 }
 
@@ -1409,17 +1402,10 @@ void dsm_destroy(dsm_handle *h) {
     if (h->d_stage_frames_depth) (void)hipFree(h->d_stage_frames_depth);
     if (h->d_store) (void)hipFree(h->d_store);
     if (h->d_cloud) (void)hipFree(h->d_cloud);
-    if (h->d_store_tmp) (void)hipFree(h->d_store_tmp);
-    if (h->d_pub) (void)hipFree(h->d_pub);
-    if (h->d_pub_out) (void)hipFree(h->d_pub_out);
+    for (DevScratch *s : {&h->store_tmp, &h->pub, &h->pub_out, &h->render_keys, &h->render_splats, &h->grid_splats, &h->grid_planes, &h->field,
+                          &h->align_planes, &h->align_sums})
+        if (s->p) (void)hipFree(s->p);
     if (h->ev_pub_dst) (void)hipEventDestroy(h->ev_pub_dst);
-    if (h->d_render_keys) (void)hipFree(h->d_render_keys);
-    if (h->d_render_splats) (void)hipFree(h->d_render_splats);
-    if (h->d_grid_splats) (void)hipFree(h->d_grid_splats);
-    if (h->d_grid_planes) (void)hipFree(h->d_grid_planes);
-    if (h->d_field) (void)hipFree(h->d_field);
-    if (h->d_align_sums) (void)hipFree(h->d_align_sums);
-    if (h->d_align_planes) (void)hipFree(h->d_align_planes);
     if (h->h_align_sums) (void)hipHostFree(h->h_align_sums);
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->h_scalars) (void)hipHostFree(h->h_scalars);
@@ -1690,8 +1676,8 @@ int dsm_warp_grouped_device(dsm_handle *h, void *surfels_device, int32_t n_group
     if (rc) return rc;
     // argument block (matrices, offsets) in the handle's grow-only scratch, like dsm_store_warp
     const size_t b_m = sizeof(float) * 16 * (size_t)n_groups, b_o = sizeof(int32_t) * ((size_t)n_groups + 1);
-    if ((rc = scratch_reserve(h, b_m + b_o))) return rc;
-    char *d = (char *)h->d_store_tmp;
+    if ((rc = scratch_grow(h, h->store_tmp, b_m + b_o, 2 * (b_m + b_o)))) return rc;
+    char *d = h->store_tmp.as<char>();
     hipError_t e = hipMemcpyAsync(d, mats16, b_m, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + b_m, offsets, b_o, hipMemcpyHostToDevice, h->stream);
     const int n = offsets[n_groups];
@@ -1827,12 +1813,12 @@ int dsm_store_erase(dsm_handle *h, int32_t begin, int32_t n) {
     const int tail = h->store_n - (begin + n);
     if (n && tail) { // the tail moves down through a scratch copy (the ranges overlap)
         const size_t need = sizeof(dsm_surfel) * (size_t)tail;
-        if ((rc = scratch_reserve(h, need))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_store_tmp, h->d_store + begin + n, need, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->d_store + begin, h->d_store_tmp, need, hipMemcpyDeviceToDevice, h->stream));
+        if ((rc = scratch_grow(h, h->store_tmp, need, 2 * need))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->store_tmp.p, h->d_store + begin + n, need, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_store + begin, h->store_tmp.p, need, hipMemcpyDeviceToDevice, h->stream));
         const size_t need_c = sizeof(float4) * (size_t)tail;
-        HIP_TRY(h, hipMemcpyAsync(h->d_store_tmp, h->d_cloud + begin + n, need_c, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->d_cloud + begin, h->d_store_tmp, need_c, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->store_tmp.p, h->d_cloud + begin + n, need_c, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_cloud + begin, h->store_tmp.p, need_c, hipMemcpyDeviceToDevice, h->stream));
     }
     h->store_n -= n;
     return DSM_OK;
@@ -1850,8 +1836,8 @@ int dsm_store_warp(dsm_handle *h, int32_t n_groups, const int32_t *offsets, cons
     if (rc) return rc;
     const size_t b_m = sizeof(float) * 16 * (size_t)n_groups, b_o = sizeof(int32_t) * ((size_t)n_groups + 1);
     const size_t need = b_m + b_o + (size_t)n_groups;
-    if ((rc = scratch_reserve(h, need))) return rc; // the scratch of dsm_store_erase doubles as the argument block
-    char *d = (char *)h->d_store_tmp;
+    if ((rc = scratch_grow(h, h->store_tmp, need, 2 * need))) return rc; // the scratch of dsm_store_erase doubles as the argument block
+    char *d = h->store_tmp.as<char>();
     hipError_t e = hipMemcpyAsync(d, mats16, b_m, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + b_m, offsets, b_o, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + b_m + b_o, changed, (size_t)n_groups, hipMemcpyHostToDevice, h->stream);
@@ -1878,24 +1864,69 @@ int dsm_store_download(dsm_handle *h, int32_t begin, int32_t n, dsm_surfel *surf
 
 namespace {
 
+// the words of the products (`ints` of them) and room for `points` float4 on their way to a host destination
 int pub_reserve(dsm_handle *h, size_t ints, size_t points) {
-    if (ints > h->pub_ints) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_pub) (void)hipFree(h->d_pub);
-        h->d_pub = nullptr;
-        h->pub_ints = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_pub, ints * 2 * sizeof(int32_t)));
-        h->pub_ints = ints * 2;
+    if (int rc = scratch_grow(h, h->pub, ints * sizeof(int32_t), ints * 2 * sizeof(int32_t))) return rc;
+    return scratch_grow(h, h->pub_out, points * sizeof(float4), (points + points / 4) * sizeof(float4));
+}
+
+// The layout of dsm_handle::pub, known here alone ("scratch of the map products"): the map part's count @0, the
+// splat counters @16, the cell list's total @32, then from @64 the tile counts of the map part's compaction with the run table
+// behind them.  dsm_grid_carve keeps a 64-bit count at `total` and its frames at `tiles`.
+struct PubWords {
+    int32_t *total, *counts, *cells_total, *tiles, *seg;
+};
+PubWords pub_words(const dsm_handle *h, size_t tiles) {
+    int32_t *w = h->pub.as<int32_t>();
+    return {w, w + 16, w + 32, w + 64, w + 64 + tiles};
+}
+
+// What a product is asked to show, checked before anything reaches the device: the select, the run list, the resident map, every
+// run against the store, and the length of the sequence (the store's record runs first, then the map part, as SurfelMap::save_mesh
+// has them, SM.cpp:1226-1248).  seg: (begin, count, offset in the sequence) of the runs that are not empty.
+struct MapSequence {
+    std::vector<int32_t> seg;
+    int64_t runs_total = 0, bound = 0;
+    int n_upper = 0;
+    size_t tiles() const { return ((size_t)n_upper + kCloudTile - 1) / kCloudTile; }
+};
+
+int check_sequence(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, int64_t max_len, MapSequence &sq) {
+    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
+    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
+    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
+    for (int32_t s = 0; s < n_segments; s++) {
+        const int32_t b = store_begin[s], cnt = store_count[s];
+        if (b < 0 || cnt < 0 || (int64_t)b + cnt > h->store_n)
+            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, cnt, h->store_n);
+        if (!cnt) continue; // empty runs are dropped
+        sq.seg.push_back(b);
+        sq.seg.push_back(cnt);
+        sq.seg.push_back((int32_t)sq.runs_total);
+        sq.runs_total += cnt;
     }
-    if (points > h->pub_out_cap) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_pub_out) (void)hipFree(h->d_pub_out);
-        h->d_pub_out = nullptr;
-        h->pub_out_cap = 0;
-        const size_t want = points + points / 4;
-        HIP_TRY(h, hipMalloc((void **)&h->d_pub_out, want * sizeof(float4)));
-        h->pub_out_cap = want;
-    }
+    sq.n_upper = select == kCloudNone ? 0 : h->map_upper;
+    sq.bound = (int64_t)sq.n_upper + sq.runs_total;
+    if (sq.bound > max_len) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)sq.bound);
+    return DSM_OK;
+}
+
+// room for `bytes` of planes in dsm_handle::grid_planes or dsm_handle::field, with a quarter to spare
+int plane_scratch_grow(dsm_handle *h, DevScratch &s, size_t bytes) {
+    return scratch_grow(h, s, bytes, bytes + bytes / 4 + 256);
+}
+
+int pose_finite(dsm_handle *h, const float *pose16, const float *pose_inv16) {
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(pose16[k]) || (pose_inv16 && !std::isfinite(pose_inv16[k]))) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
+    return DSM_OK;
+}
+
+// the words of a sequence's product, with its run table on its way up; `points`: as pub_reserve
+int pub_sequence(dsm_handle *h, const MapSequence &sq, size_t points, PubWords &w) {
+    if (int rc = pub_reserve(h, 64 + sq.tiles() + sq.seg.size(), points)) return rc;
+    w = pub_words(h, sq.tiles());
+    if (!sq.seg.empty()) HIP_TRY(h, hipMemcpyAsync(w.seg, sq.seg.data(), sq.seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     return DSM_OK;
 }
 
@@ -1913,95 +1944,59 @@ int pub_order_dst(dsm_handle *h) {
 int dsm_cloud_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, void *dst,
                       int dst_on_device, int32_t cap, int32_t *n) {
     if (!h || !n || cap < 0) return DSM_E_INVALID;
-    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
-    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
     if (cap > 0 && !dst) return fail(h, DSM_E_INVALID, "null output");
-    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
-    // the runs, checked before anything reaches the device; empty ones are dropped
-    std::vector<int32_t> seg;
-    int64_t runs_total = 0;
-    for (int32_t s = 0; s < n_segments; s++) {
-        const int32_t b = store_begin[s], c = store_count[s];
-        if (b < 0 || c < 0 || (int64_t)b + c > h->store_n)
-            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, c, h->store_n);
-        if (!c) continue;
-        seg.push_back(b);
-        seg.push_back(c);
-        seg.push_back((int32_t)runs_total);
-        runs_total += c;
-    }
-    if (runs_total > INT32_MAX) return fail(h, DSM_E_INVALID, "%lld points in the runs", (long long)runs_total);
-    int rc = bind_device(h);
+    MapSequence sq;
+    int rc = check_sequence(h, select, n_segments, store_begin, store_count, INT64_MAX, sq); // (only the runs are bounded here)
     if (rc) return rc;
-    const int n_upper = select == kCloudNone ? 0 : h->map_upper;
-    const size_t tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    const int64_t runs_total = sq.runs_total;
+    if (runs_total > INT32_MAX) return fail(h, DSM_E_INVALID, "%lld points in the runs", (long long)runs_total);
+    if ((rc = bind_device(h))) return rc;
     // where the points go: the caller's device memory, or staging for a host destination (no more than the points there can be)
-    const int64_t bound = (int64_t)n_upper + runs_total;
-    const int32_t dev_cap = (int32_t)(bound < cap ? bound : cap);
-    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), dst_on_device ? 0 : (size_t)dev_cap))) return rc;
+    const int32_t dev_cap = (int32_t)(sq.bound < cap ? sq.bound : cap);
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
-    float4 *out = dst_on_device ? (float4 *)dst : h->d_pub_out;
-    int32_t *d_total = h->d_pub, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
-    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    hipError_t e = launch_cloud_map(h->hc.local, h->hc.n_local, n_upper, select, d_tiles, d_total, out, dev_cap, h->stream);
-    if (e == hipSuccess) e = launch_cloud_gather(h->d_cloud, d_seg, (int)(seg.size() / 3), (int)runs_total, d_total, out, dev_cap, h->stream);
+    PubWords w;
+    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : (size_t)dev_cap, w))) return rc;
+    float4 *out = dst_on_device ? (float4 *)dst : h->pub_out.as<float4>();
+    hipError_t e = launch_cloud_map(h->hc.local, h->hc.n_local, sq.n_upper, select, w.tiles, w.total, out, dev_cap, h->stream);
+    if (e == hipSuccess) e = launch_cloud_gather(h->d_cloud, w.seg, (int)(sq.seg.size() / 3), (int)runs_total, w.total, out, dev_cap, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "cloud launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], w.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const int64_t total = (int64_t)h->h_scalars[5] + runs_total;
     *n = (int32_t)total;
     if (total > cap) return fail(h, DSM_E_CAPACITY, "%lld points exceed the caller's capacity %d", (long long)total, cap);
-    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost));
+    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->pub_out.p, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost));
     return DSM_OK;
 }
 
-// the store's record runs first, then the map part: SurfelMap::save_mesh's order (SM.cpp:1226-1248)
 int dsm_mesh_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, int vertex_layout,
                      void *dst, int dst_on_device, int32_t cap, int32_t *n) {
     if (!h || !n || cap < 0) return DSM_E_INVALID;
-    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
     if (vertex_layout != kMeshRef6 && vertex_layout != kMeshXyzRgba8) return fail(h, DSM_E_INVALID, "mesh vertex layout %d", vertex_layout);
-    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
     if (cap > 0 && !dst) return fail(h, DSM_E_INVALID, "null output");
     if (dst_on_device && ((uintptr_t)dst & 3)) return fail(h, DSM_E_INVALID, "device output not 4-byte aligned");
-    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
-    // the runs, checked before anything reaches the device; empty ones are dropped
-    std::vector<int32_t> seg;
-    int64_t runs_total = 0;
-    for (int32_t s = 0; s < n_segments; s++) {
-        const int32_t b = store_begin[s], c = store_count[s];
-        if (b < 0 || c < 0 || (int64_t)b + c > h->store_n)
-            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, c, h->store_n);
-        if (!c) continue;
-        seg.push_back(b);
-        seg.push_back(c);
-        seg.push_back((int32_t)runs_total);
-        runs_total += c;
-    }
-    const int n_upper = select == kCloudNone ? 0 : h->map_upper;
-    const int64_t bound = (int64_t)n_upper + runs_total;
-    if (bound > INT32_MAX) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)bound);
-    int rc = bind_device(h);
+    MapSequence sq;
+    int rc = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX, sq);
     if (rc) return rc;
-    const size_t tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    const int64_t runs_total = sq.runs_total;
+    if ((rc = bind_device(h))) return rc;
     const size_t rec_bytes = (size_t)mesh_surfel_bytes(vertex_layout);
     // where the vertices go: the caller's device memory, or staging for a host destination (no more than there can be)
-    const int32_t dev_cap = (int32_t)(bound < cap ? bound : cap);
-    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), dst_on_device ? 0 : (size_t)dev_cap * (rec_bytes / sizeof(float4))))) return rc;
+    const int32_t dev_cap = (int32_t)(sq.bound < cap ? sq.bound : cap);
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
-    void *out = dst_on_device ? dst : (void *)h->d_pub_out;
-    int32_t *d_total = h->d_pub, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
-    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    hipError_t e = launch_mesh_gather(h->d_store, d_seg, (int)(seg.size() / 3), (int)runs_total, vertex_layout, out, dev_cap, h->stream);
+    PubWords w;
+    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : (size_t)dev_cap * (rec_bytes / sizeof(float4)), w))) return rc;
+    void *out = dst_on_device ? dst : h->pub_out.p;
+    hipError_t e = launch_mesh_gather(h->d_store, w.seg, (int)(sq.seg.size() / 3), (int)runs_total, vertex_layout, out, dev_cap, h->stream);
     if (e == hipSuccess)
-        e = launch_mesh_map(h->hc.local, h->hc.n_local, n_upper, select, d_tiles, d_total, vertex_layout, out, (int)runs_total, dev_cap, h->stream);
+        e = launch_mesh_map(h->hc.local, h->hc.n_local, sq.n_upper, select, w.tiles, w.total, vertex_layout, out, (int)runs_total, dev_cap, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "mesh launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], w.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const int64_t total = (int64_t)h->h_scalars[5] + runs_total;
     *n = (int32_t)total;
     if (total > cap) return fail(h, DSM_E_CAPACITY, "%lld surfels exceed the caller's capacity %d", (long long)total, cap);
-    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)total * rec_bytes, hipMemcpyDeviceToHost));
+    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->pub_out.p, (size_t)total * rec_bytes, hipMemcpyDeviceToHost));
     return DSM_OK;
 }
 
@@ -2015,78 +2010,15 @@ int dsm_mesh_indices(dsm_handle *h, int32_t n_surfels, void *dst, int dst_on_dev
     if (rc) return rc;
     if (!dst_on_device && (rc = pub_reserve(h, 0, (size_t)n_surfels * 3))) return rc;
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
-    uint32_t *out = dst_on_device ? (uint32_t *)dst : (uint32_t *)h->d_pub_out;
+    uint32_t *out = dst_on_device ? (uint32_t *)dst : h->pub_out.as<uint32_t>();
     const hipError_t e = launch_mesh_indices(out, n_surfels, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "mesh index launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!dst_on_device) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)n_surfels * 48, hipMemcpyDeviceToHost));
+    if (!dst_on_device) HIP_TRY(h, hipMemcpy(dst, h->pub_out.p, (size_t)n_surfels * 48, hipMemcpyDeviceToHost));
     return DSM_OK;
 }
 
 // ------------------------------------------------------------------ the map as an image (dsm_k_render.h)
-
-namespace {
-
-int render_reserve(dsm_handle *h, size_t px, size_t side_sum, size_t seq) {
-    const size_t want_px = px + (side_sum + 1) / 2 + 8; // the ray tables (floats) behind the keys, in units of a key
-    if (want_px > h->render_px) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_render_keys) (void)hipFree(h->d_render_keys);
-        h->d_render_keys = nullptr;
-        h->render_px = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_render_keys, want_px * sizeof(unsigned long long)));
-        h->render_px = want_px;
-    }
-    if (seq > h->render_seq) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_render_splats) (void)hipFree(h->d_render_splats);
-        h->d_render_splats = nullptr;
-        h->render_seq = 0;
-        const size_t want = seq + seq / 4 + 64;
-        HIP_TRY(h, hipMalloc(&h->d_render_splats, want * (sizeof(RenderSplat) + sizeof(int32_t))));
-        h->render_seq = want;
-    }
-    return DSM_OK;
-}
-
-} // namespace
-
-// the sequence is dsm_mesh_compose's: the store's record runs first, then the map part
-namespace {
-
-// What dsm_render_compose is asked to show, checked before anything reaches the device (dsm_align_frame makes the same checks in
-// front of its own device work): the select, the run list, the poses, the resident map, every run against the store, and the
-// length of the sequence.  seg: (begin, count, offset in the sequence) of the runs that are not empty.
-struct RenderSequence {
-    std::vector<int32_t> seg;
-    int64_t runs_total = 0, bound = 0;
-    int n_upper = 0;
-};
-
-int render_check_sequence(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, const float *pose16,
-                          const float *pose_inv16, RenderSequence &sq) {
-    if (select != kCloudNone && select != kCloudMature && select != kCloudNonzero) return fail(h, DSM_E_INVALID, "cloud select %d", select);
-    if (n_segments < 0 || (n_segments > 0 && (!store_begin || !store_count))) return fail(h, DSM_E_INVALID, "null/negative run list");
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(pose16[k]) || (pose_inv16 && !std::isfinite(pose_inv16[k]))) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
-    if (select != kCloudNone && !h->map_valid) return fail(h, DSM_E_STATE, "no resident map");
-    for (int32_t s = 0; s < n_segments; s++) {
-        const int32_t b = store_begin[s], cnt = store_count[s];
-        if (b < 0 || cnt < 0 || (int64_t)b + cnt > h->store_n)
-            return fail(h, DSM_E_INVALID, "store run %d = [%d,+%d) outside [0,%d)", s, b, cnt, h->store_n);
-        if (!cnt) continue; // empty runs are dropped
-        sq.seg.push_back(b);
-        sq.seg.push_back(cnt);
-        sq.seg.push_back((int32_t)sq.runs_total);
-        sq.runs_total += cnt;
-    }
-    sq.n_upper = select == kCloudNone ? 0 : h->map_upper;
-    sq.bound = (int64_t)sq.n_upper + sq.runs_total;
-    if (sq.bound > INT32_MAX - 4096) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)sq.bound);
-    return DSM_OK;
-}
-
-} // namespace
 
 int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count,
                        const dsm_render_camera *camera, const float *pose16, const float *pose_inv16, uint32_t flags, const dsm_render_planes *planes,
@@ -2102,19 +2034,21 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
     if (!(c.near_dist > 0.0f) || !(c.near_dist < c.far_dist) || !std::isfinite(c.far_dist))
         return fail(h, DSM_E_INVALID, "render depth range (%g, %g)", (double)c.near_dist, (double)c.far_dist);
     if (!planes->depth && !planes->index && !planes->normal && !planes->intensity) return fail(h, DSM_E_INVALID, "no output plane");
-    RenderSequence sq;
-    int rc = render_check_sequence(h, select, n_segments, store_begin, store_count, pose16, pose_inv16, sq);
+    int rc = pose_finite(h, pose16, pose_inv16);
     if (rc) return rc;
-    const std::vector<int32_t> &seg = sq.seg;
-    const int64_t runs_total = sq.runs_total, bound = sq.bound;
-    const int n_upper = sq.n_upper;
+    MapSequence sq;
+    if ((rc = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX - 4096, sq))) return rc;
+    const size_t n_seq = (size_t)sq.bound;
     if ((rc = bind_device(h))) return rc;
     const int w = c.width, hh = c.height;
-    const size_t px = (size_t)w * hh, tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    const size_t px = (size_t)w * hh;
     // a host destination's planes are staged behind one another, each from a 16-byte boundary
     const size_t q_depth = (px + 3) / 4, q_normal = (3 * px + 3) / 4, q_int = (px + 15) / 16;
-    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), dst_on_device ? 0 : 2 * q_depth + q_normal + q_int))) return rc;
-    if ((rc = render_reserve(h, px, (size_t)w + hh, (size_t)bound))) return rc;
+    // the key plane with the ray tables (floats) behind it, in units of a key; the splat records with the number -> record table
+    // behind them.  (dsm_align_frame renders into dsm_handle::align_planes: no grower reached from here may touch that buffer.)
+    const size_t key_bytes = (px + ((size_t)w + hh + 1) / 2 + 8) * sizeof(unsigned long long), splat_rec = sizeof(RenderSplat) + sizeof(int32_t);
+    if ((rc = scratch_grow(h, h->render_keys, key_bytes, key_bytes))) return rc;
+    if ((rc = scratch_grow(h, h->render_splats, n_seq * splat_rec, (n_seq + n_seq / 4 + 64) * splat_rec))) return rc;
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
     float pose_inv[16];
     if (pose_inv16) memcpy(pose_inv, pose_inv16, sizeof pose_inv);
@@ -2126,34 +2060,34 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
     std::vector<float> rays((size_t)w + hh);
     for (int x = 0; x < w; x++) rays[(size_t)x] = ray_coeff(x, c.cx, c.fx);
     for (int y = 0; y < hh; y++) rays[(size_t)w + y] = ray_coeff(y, c.cy, c.fy);
-    float *d_rays = (float *)(h->d_render_keys + px);
-    int32_t *d_total = h->d_pub, *d_counts = h->d_pub + 16, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
+    float *d_rays = (float *)(h->render_keys.as<unsigned long long>() + px);
     HIP_TRY(h, hipMemcpyAsync(d_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    PubWords pw;
+    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : 2 * q_depth + q_normal + q_int, pw))) return rc;
     RenderScratch sc;
-    sc.keys = h->d_render_keys;
-    sc.splats = (RenderSplat *)h->d_render_splats;
-    sc.slot_of = (int32_t *)((RenderSplat *)h->d_render_splats + h->render_seq);
-    sc.counts = d_counts;
-    sc.n_seq = (int32_t)bound;
+    sc.keys = h->render_keys.as<unsigned long long>();
+    sc.splats = h->render_splats.as<RenderSplat>();
+    sc.slot_of = (int32_t *)(sc.splats + h->render_splats.bytes / splat_rec);
+    sc.counts = pw.counts;
+    sc.n_seq = (int32_t)n_seq;
     float *o_depth = (float *)planes->depth;
     int32_t *o_index = (int32_t *)planes->index;
     float *o_normal = (float *)planes->normal;
     uint8_t *o_int = (uint8_t *)planes->intensity;
     if (!dst_on_device) {
-        float4 *st = h->d_pub_out;
+        float4 *st = h->pub_out.as<float4>();
         if (o_depth) o_depth = (float *)st;
         if (o_index) o_index = (int32_t *)(st + q_depth);
         if (o_normal) o_normal = (float *)(st + 2 * q_depth);
         if (o_int) o_int = (uint8_t *)(st + 2 * q_depth + q_normal);
     }
-    const hipError_t e = launch_render(h->d_store, d_seg, (int)(seg.size() / 3), (int)runs_total, h->hc.local, h->hc.n_local, n_upper, select, d_tiles,
-                                       d_total, cam, pose_inv, flags, eigen33_products(h), sc, d_rays, d_rays + w, o_depth, o_index, o_normal, o_int,
-                                       h->stream);
+    const hipError_t e = launch_render(h->d_store, pw.seg, (int)(sq.seg.size() / 3), (int)sq.runs_total, h->hc.local, h->hc.n_local, sq.n_upper, select,
+                                       pw.tiles, pw.total, cam, pose_inv, flags, eigen33_products(h), sc, d_rays, d_rays + w, o_depth, o_index, o_normal,
+                                       o_int, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "render launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], pw.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + runs_total);
+    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + sq.runs_total);
     if (!dst_on_device) {
         if (planes->depth) HIP_TRY(h, hipMemcpy(planes->depth, o_depth, px * sizeof(float), hipMemcpyDeviceToHost));
         if (planes->index) HIP_TRY(h, hipMemcpy(planes->index, o_index, px * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -2166,28 +2100,6 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
 // ------------------------------------------------------------------ the map as a voxel grid (dsm_k_grid.h)
 
 namespace {
-
-int grid_reserve(dsm_handle *h, size_t seq, size_t bytes) {
-    if (seq > h->grid_seq) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_grid_splats) (void)hipFree(h->d_grid_splats);
-        h->d_grid_splats = nullptr;
-        h->grid_seq = 0;
-        const size_t want = seq + seq / 4 + 64;
-        HIP_TRY(h, hipMalloc(&h->d_grid_splats, want * sizeof(GridSplat)));
-        h->grid_seq = want;
-    }
-    if (bytes > h->grid_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_grid_planes) (void)hipFree(h->d_grid_planes);
-        h->d_grid_planes = nullptr;
-        h->grid_bytes = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        HIP_TRY(h, hipMalloc(&h->d_grid_planes, want));
-        h->grid_bytes = want;
-    }
-    return DSM_OK;
-}
 
 // a dimension < 1 or more than `limit` voxels: false
 bool grid_dims_ok(int32_t nx, int32_t ny, int32_t nz, int64_t limit = kGridMaxVoxels) {
@@ -2238,22 +2150,15 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     if (planes->cells && planes->cells_cap < 0) return fail(h, DSM_E_INVALID, "cells_cap %d", planes->cells_cap);
     if (dst_on_device && ((((uintptr_t)planes->occupied | (uintptr_t)planes->inflated | (uintptr_t)planes->index | (uintptr_t)planes->cells) & 3)))
         return fail(h, DSM_E_INVALID, "device output not 4-byte aligned");
-    {
-        const void *p[4] = {planes->occupied, planes->inflated, planes->index, planes->cells};
-        for (int a = 0; a < 4; a++)
-            for (int b = a + 1; b < 4; b++)
-                if (p[a] && p[a] == p[b]) return fail(h, DSM_E_INVALID, "two output planes are the same memory");
-    }
-    const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; // (no pose is involved)
-    RenderSequence sq;
-    int rc = render_check_sequence(h, select, n_segments, store_begin, store_count, identity, nullptr, sq);
+    const void *const given[4] = {planes->occupied, planes->inflated, planes->index, planes->cells};
+    if (!planes_distinct(given, 4)) return fail(h, DSM_E_INVALID, "two output planes are the same memory");
+    MapSequence sq;
+    int rc = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX - 4096, sq);
     if (rc) return rc;
-    const std::vector<int32_t> &seg = sq.seg;
-    const int64_t runs_total = sq.runs_total, bound = sq.bound;
-    const int n_upper = sq.n_upper;
+    const size_t n_seq = (size_t)sq.bound;
     if ((rc = bind_device(h))) return rc;
     const int nx = spec->nx, ny = spec->ny, nz = spec->nz, wx = (nx + 31) / 32;
-    const size_t rows = (size_t)ny * nz, n_vox = rows * nx, n_words = rows * wx, tiles = ((size_t)n_upper + kCloudTile - 1) / kCloudTile;
+    const size_t rows = (size_t)ny * nz, n_vox = rows * nx, n_words = rows * wx;
     const bool cells_of_inflated = (flags & DSM_GRID_CELLS_OF_INFLATED) != 0;
     const bool want_inflated = planes->inflated || (planes->cells && cells_of_inflated);
     const size_t cells_cap = planes->cells ? ((size_t)planes->cells_cap < n_vox ? (size_t)planes->cells_cap : n_vox) : 0; // (no more cells than voxels)
@@ -2266,20 +2171,21 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     const size_t at_index = take(planes->index && !dst_on_device, n_vox);
     const size_t at_cells = take(planes->cells && !dst_on_device, cells_cap);
     const size_t at_tiles = take(planes->cells != nullptr, (n_words + 255) / 256);
-    if ((rc = pub_reserve(h, 64 + tiles + seg.size(), 0))) return rc;
-    if ((rc = grid_reserve(h, (size_t)bound, words * sizeof(uint32_t)))) return rc;
+    // (dsm_field_compose composes into dsm_handle::field: no grower reached from here may touch that buffer)
+    if ((rc = scratch_grow(h, h->grid_splats, n_seq * sizeof(GridSplat), (n_seq + n_seq / 4 + 64) * sizeof(GridSplat)))) return rc;
+    if ((rc = plane_scratch_grow(h, h->grid_planes, words * sizeof(uint32_t)))) return rc;
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
-    int32_t *d_total = h->d_pub, *d_counts = h->d_pub + 16, *d_cells_total = h->d_pub + 32, *d_tiles = h->d_pub + 64, *d_seg = h->d_pub + 64 + tiles;
-    if (!seg.empty()) HIP_TRY(h, hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    uint32_t *scratch = (uint32_t *)h->d_grid_planes;
+    PubWords pw;
+    if ((rc = pub_sequence(h, sq, 0, pw))) return rc;
+    uint32_t *scratch = h->grid_planes.as<uint32_t>();
     GridSpec g;
     for (int a = 0; a < 3; a++) g.origin[a] = spec->origin[a];
     g.voxel = spec->voxel;
     g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
     GridScratch sc;
-    sc.splats = (GridSplat *)h->d_grid_splats;
-    sc.counts = d_counts;
-    sc.n_seq = (int32_t)bound;
+    sc.splats = h->grid_splats.as<GridSplat>();
+    sc.counts = pw.counts;
+    sc.n_seq = (int32_t)n_seq;
     sc.cell_tiles = (int32_t *)(scratch + at_tiles);
     GridOut out;
     out.occupied = dst_on_device && planes->occupied ? planes->occupied : scratch + at_occ;
@@ -2287,16 +2193,16 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     out.index = !planes->index ? nullptr : dst_on_device ? planes->index : (int32_t *)(scratch + at_index);
     out.cells = !planes->cells ? nullptr : dst_on_device ? planes->cells : (int32_t *)(scratch + at_cells);
     out.cells_cap = (int32_t)cells_cap;
-    out.cells_total = planes->cells ? d_cells_total : nullptr;
+    out.cells_total = planes->cells ? pw.cells_total : nullptr;
     out.cells_of_inflated = cells_of_inflated;
-    const hipError_t e = launch_grid(h->d_store, d_seg, (int)(seg.size() / 3), (int)runs_total, h->hc.local, h->hc.n_local, n_upper, select, d_tiles, d_total,
-                                     g, spec->inflate, sc, out, h->stream);
+    const hipError_t e = launch_grid(h->d_store, pw.seg, (int)(sq.seg.size() / 3), (int)sq.runs_total, h->hc.local, h->hc.n_local, sq.n_upper, select, pw.tiles,
+                                     pw.total, g, spec->inflate, sc, out, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "grid launch: %s", hipGetErrorString(e));
     h->h_scalars[6] = 0;
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (planes->cells) HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[6], d_cells_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], pw.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (planes->cells) HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[6], pw.cells_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + runs_total);
+    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + sq.runs_total);
     const int32_t cells = h->h_scalars[6];
     *n_cells = cells;
     if (!dst_on_device) {
@@ -2315,11 +2221,8 @@ int dsm_grid_inflate(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t 
     if (!src_device || !dst_device || src_device == dst_device) return fail(h, DSM_E_INVALID, "grid inflate: null source or destination, or the same");
     if ((((uintptr_t)src_device | (uintptr_t)dst_device) & 3)) return fail(h, DSM_E_INVALID, "grid inflate: a bit set not 4-byte aligned");
     if (!grid_dims_ok(nx, ny, nz)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", nx, ny, nz);
-    {
-        const uintptr_t a = (uintptr_t)src_device, b = (uintptr_t)dst_device;
-        const uintptr_t bytes = (uintptr_t)((nx + 31) / 32) * (uintptr_t)ny * (uintptr_t)nz * sizeof(uint32_t); // <= 2^30
-        if ((a < b ? b - a : a - b) < bytes) return fail(h, DSM_E_INVALID, "grid inflate: source and destination overlap");
-    }
+    const size_t set_bytes = (size_t)((nx + 31) / 32) * ny * nz * sizeof(uint32_t); // <= 2^30
+    if (ranges_overlap(src_device, set_bytes, dst_device, set_bytes)) return fail(h, DSM_E_INVALID, "grid inflate: source and destination overlap");
     if (radius < 0 || radius > kGridMaxInflate) return fail(h, DSM_E_INVALID, "grid inflate %d outside 0..%d", radius, kGridMaxInflate);
     int rc = bind_device(h);
     if (rc) return rc;
@@ -2339,10 +2242,8 @@ const char *field_request_error(int32_t max_dist, float voxel, const dsm_field_p
     if (max_dist < 1 || max_dist > kFieldMaxDist) return "max_dist outside 1..64";
     if (!p->dist2 && !p->nearest && !p->distance) return "no output plane";
     if (p->distance && (!std::isfinite(voxel) || !(voxel > 0.0f))) return "voxel not finite or not positive";
-    const void *q[3] = {p->dist2, p->nearest, p->distance};
-    for (int a = 0; a < 3; a++)
-        for (int b = a + 1; b < 3; b++)
-            if (q[a] && q[a] == q[b]) return "two output planes are the same memory";
+    const void *const given[3] = {p->dist2, p->nearest, p->distance};
+    if (!planes_distinct(given, 3)) return "two output planes are the same memory";
     if (on_device && ((((uintptr_t)p->nearest | (uintptr_t)p->distance) & 3) || ((uintptr_t)p->dist2 & 1))) return "a device plane is not aligned to its element";
     return nullptr;
 }
@@ -2366,22 +2267,9 @@ FieldLayout field_layout(size_t n_vox, size_t n_words, bool with_bits, const dsm
     return l;
 }
 
-int field_reserve(dsm_handle *h, size_t bytes) {
-    if (bytes > h->field_bytes) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_field) (void)hipFree(h->d_field);
-        h->d_field = nullptr;
-        h->field_bytes = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        HIP_TRY(h, hipMalloc(&h->d_field, want));
-        h->field_bytes = want;
-    }
-    return DSM_OK;
-}
-
 // the table, the three passes, the copies to host planes; synchronises.  The scratch is reserved for `l`.
 int field_run(dsm_handle *h, const uint32_t *bits, int nx, int ny, int nz, int r, float voxel, const dsm_field_planes *p, bool on_device, const FieldLayout &l) {
-    uint8_t *sc = (uint8_t *)h->d_field;
+    uint8_t *sc = h->field.as<uint8_t>();
     const size_t n_vox = (size_t)nx * ny * nz;
     if (p->distance) {
         h->field_table.resize((size_t)(r * r + 1));
@@ -2413,16 +2301,16 @@ int dsm_grid_distance(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t
     if (const char *bad = field_request_error(max_dist, voxel, planes_device, true)) return fail(h, DSM_E_INVALID, "grid distance: %s", bad);
     const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
     {
-        const uintptr_t a = (uintptr_t)src_device, a_end = a + n_words * sizeof(uint32_t);
-        const uintptr_t q[3] = {(uintptr_t)planes_device->dist2, (uintptr_t)planes_device->nearest, (uintptr_t)planes_device->distance};
+        const void *const q[3] = {planes_device->dist2, planes_device->nearest, planes_device->distance};
         const size_t elem[3] = {sizeof(uint16_t), sizeof(int32_t), sizeof(float)};
         for (int k = 0; k < 3; k++)
-            if (q[k] && q[k] < a_end && a < q[k] + n_vox * elem[k]) return fail(h, DSM_E_INVALID, "grid distance: a plane overlaps the source");
+            if (q[k] && ranges_overlap(q[k], n_vox * elem[k], src_device, n_words * sizeof(uint32_t)))
+                return fail(h, DSM_E_INVALID, "grid distance: a plane overlaps the source");
     }
     int rc = bind_device(h);
     if (rc) return rc;
     const FieldLayout l = field_layout(n_vox, n_words, false, planes_device, true);
-    if ((rc = field_reserve(h, l.bytes))) return rc;
+    if ((rc = plane_scratch_grow(h, h->field, l.bytes))) return rc;
     if ((rc = pub_order_dst(h))) return rc;
     return field_run(h, (const uint32_t *)src_device, nx, ny, nz, max_dist, voxel, planes_device, true, l);
 }
@@ -2437,18 +2325,18 @@ int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32
         return fail(h, DSM_E_INVALID, "field of %d x %d x %d: more than 2^26 voxels", spec->nx, spec->ny, spec->nz);
     if (const char *bad = field_request_error(max_dist, spec->voxel, planes, dst_on_device != 0)) return fail(h, DSM_E_INVALID, "field: %s", bad);
     {
-        const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; // the sequence is checked here, before the scratch grows
-        RenderSequence sq;
-        if (int bad = render_check_sequence(h, select, n_segments, store_begin, store_count, identity, nullptr, sq)) return bad;
+        MapSequence sq; // the sequence is checked here, before the scratch grows
+        if (int bad = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX - 4096, sq)) return bad;
     }
     int rc = bind_device(h);
     if (rc) return rc;
     const int nx = spec->nx, ny = spec->ny, nz = spec->nz;
     const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
     const FieldLayout l = field_layout(n_vox, n_words, true, planes, dst_on_device != 0);
-    if ((rc = field_reserve(h, l.bytes))) return rc;
-    // the occupied set by dsm_grid_compose itself, into the scratch as a device destination
-    uint32_t *bits = (uint32_t *)((uint8_t *)h->d_field + l.bits);
+    if ((rc = plane_scratch_grow(h, h->field, l.bytes))) return rc;
+    // the occupied set by dsm_grid_compose itself, into the scratch as a device destination: no grower reached from there touches
+    // dsm_handle::field
+    uint32_t *bits = (uint32_t *)(h->field.as<uint8_t>() + l.bits);
     const dsm_grid_planes occupied = {bits, nullptr, nullptr, nullptr, 0};
     int32_t n = 0, cells = 0;
     if ((rc = dsm_grid_compose(h, select, n_segments, store_begin, store_count, spec, 0, &occupied, 1, &n, &cells))) return rc;
@@ -2505,8 +2393,9 @@ int dsm_grid_carve(dsm_handle *h, const dsm_grid_spec *spec, const dsm_carve_par
         else inverse4<float>(poses16 + 16 * f, cf.inv);
         cf.depth_off = (int64_t)slots[f] * h->hc.slot_elems;
     }
-    unsigned long long *d_count = (unsigned long long *)h->d_pub;
-    CarveFrame *d_frames = (CarveFrame *)(h->d_pub + 64);
+    const PubWords pw = pub_words(h, 0);
+    unsigned long long *d_count = (unsigned long long *)pw.total;
+    CarveFrame *d_frames = (CarveFrame *)pw.tiles;
     HIP_TRY(h, hipMemcpyAsync(d_frames, h->carve_frames.data(), sizeof(CarveFrame) * (size_t)n_frames, hipMemcpyHostToDevice, h->stream));
     CarveConst c;
     memset(&c, 0, sizeof c);
@@ -2539,17 +2428,13 @@ int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const v
     const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
     const size_t cells_cap = p.cells ? ((size_t)p.cells_cap < n_vox ? (size_t)p.cells_cap : n_vox) : 0; // (no more cells than voxels)
     {
-        const uintptr_t q[4] = {(uintptr_t)p.state, (uintptr_t)p.known_free, (uintptr_t)p.frontier, (uintptr_t)p.cells};
-        const size_t bytes[4] = {n_vox, n_words * sizeof(uint32_t), n_words * sizeof(uint32_t), cells_cap * sizeof(int32_t)};
-        const uintptr_t src[2] = {(uintptr_t)occupied_device, (uintptr_t)free_device};
-        for (int a = 0; a < 4; a++) {
-            if (!q[a]) continue;
-            for (int b = a + 1; b < 4; b++)
-                if (q[a] == q[b]) return fail(h, DSM_E_INVALID, "grid classify: two output planes are the same memory");
-            for (int s = 0; s < 2; s++)
-                if (q[a] < src[s] + n_words * sizeof(uint32_t) && src[s] < q[a] + (bytes[a] ? bytes[a] : 1))
+        const void *const q[4] = {p.state, p.known_free, p.frontier, p.cells};
+        const size_t bytes[4] = {n_vox, n_words * sizeof(uint32_t), n_words * sizeof(uint32_t), cells_cap ? cells_cap * sizeof(int32_t) : 1};
+        if (!planes_distinct(q, 4)) return fail(h, DSM_E_INVALID, "grid classify: two output planes are the same memory");
+        for (int a = 0; a < 4; a++)
+            for (const void *src : {occupied_device, free_device})
+                if (q[a] && ranges_overlap(q[a], bytes[a], src, n_words * sizeof(uint32_t)))
                     return fail(h, DSM_E_INVALID, "grid classify: a plane overlaps a source");
-        }
     }
     int rc = bind_device(h);
     if (rc) return rc;
@@ -2557,10 +2442,10 @@ int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const v
     const size_t tiles = (n_words + 255) / 256;
     const size_t at_tiles = p.frontier ? 0 : (n_words + 3) & ~(size_t)3;
     if ((rc = pub_reserve(h, 64, 0))) return rc;
-    if ((rc = grid_reserve(h, 0, (at_tiles + tiles) * sizeof(uint32_t)))) return rc;
+    if ((rc = plane_scratch_grow(h, h->grid_planes, (at_tiles + tiles) * sizeof(uint32_t)))) return rc;
     if ((rc = pub_order_dst(h))) return rc;
-    uint32_t *scratch = (uint32_t *)h->d_grid_planes;
-    int32_t *d_total = h->d_pub + 32;
+    uint32_t *scratch = h->grid_planes.as<uint32_t>();
+    int32_t *d_total = pub_words(h, 0).cells_total;
     const hipError_t e = launch_space((const uint32_t *)occupied_device, (const uint32_t *)free_device, nx, ny, nz, p.state, p.known_free,
                                       p.frontier ? p.frontier : scratch, p.cells, (int)cells_cap, (int32_t *)(scratch + at_tiles), d_total, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "classify launch: %s", hipGetErrorString(e));
@@ -2599,18 +2484,12 @@ int align_setup(dsm_handle *h, int slot, const dsm_render_camera *model_cam, con
     return DSM_OK;
 }
 
+// the sums on the device and their landing place, at the first call; the model planes of px pixels (none: px == 0)
 int align_reserve(dsm_handle *h, size_t px) {
-    if (!h->d_align_sums) HIP_TRY(h, hipMalloc((void **)&h->d_align_sums, 256));
+    if (int rc = scratch_grow(h, h->align_sums, 256, 256)) return rc;
     if (!h->h_align_sums) HIP_TRY(h, hipHostMalloc((void **)&h->h_align_sums, 256, hipHostMallocDefault));
-    if (px > h->align_px) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_align_planes) (void)hipFree(h->d_align_planes);
-        h->d_align_planes = nullptr;
-        h->align_px = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_align_planes, (px * 4 + 64) * sizeof(float)));
-        h->align_px = px;
-    }
-    return DSM_OK;
+    const size_t bytes = (px * 4 + 64) * sizeof(float);
+    return px ? scratch_grow(h, h->align_planes, bytes, bytes) : DSM_OK;
 }
 
 // the stream behind the uploads that wrote the slot
@@ -2622,9 +2501,9 @@ int align_order_slot(dsm_handle *h, int slot) {
 // one evaluation: clear, launch, bring the 29 words back through page-locked memory, wait
 int align_evaluate(dsm_handle *h, const AlignConst &c, int slot, const float *zm, const float *nm, int64_t *sums) {
     const float *depth = (const float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
-    const hipError_t e = launch_align(c, depth, zm, nm, h->d_align_sums, h->stream);
+    const hipError_t e = launch_align(c, depth, zm, nm, h->align_sums.as<unsigned long long>(), h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "align launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(h->h_align_sums, h->d_align_sums, kAlignSums * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_align_sums, h->align_sums.p, kAlignSums * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     memcpy(sums, h->h_align_sums, kAlignSums * sizeof(int64_t));
     return DSM_OK;
@@ -2683,13 +2562,15 @@ int dsm_align_frame(dsm_handle *h, int slot, int select, int32_t n_segments, con
     int rc = align_setup(h, slot, model_cam, params, c);
     if (rc) return rc;
     // dsm_render_compose's own checks of what it is handed below, made here so that they too come before any device work
-    RenderSequence sq;
-    if ((rc = render_check_sequence(h, select, n_segments, store_begin, store_count, pose16_guess, nullptr, sq))) return rc;
+    if ((rc = pose_finite(h, pose16_guess, nullptr))) return rc;
+    MapSequence sq;
+    if ((rc = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX - 4096, sq))) return rc;
     if ((rc = bind_device(h))) return rc;
     const size_t px = (size_t)model_cam->width * model_cam->height;
     if ((rc = align_reserve(h, px))) return rc;
-    // the model, once: two-sided, the closed-form inverse, into the handle's scratch (the call synchronises)
-    float *zm = h->d_align_planes, *nm = h->d_align_planes + px;
+    // the model, once: two-sided, the closed-form inverse, into the handle's scratch (the call synchronises): no grower reached from
+    // dsm_render_compose touches dsm_handle::align_planes
+    float *zm = h->align_planes.as<float>(), *nm = zm + px;
     dsm_render_planes planes = {zm, nullptr, nm, nullptr};
     int32_t n_surfels = 0;
     if ((rc = dsm_render_compose(h, select, n_segments, store_begin, store_count, model_cam, pose16_guess, nullptr, 0, &planes, 1, &n_surfels))) return rc;
@@ -2761,14 +2642,14 @@ int dsm_frame_cloud(dsm_handle *h, int slot, const double *pose7, void *dst, int
     p.fy = h->cfg.fy;
     p.cx = h->cfg.cx;
     p.cy = h->cfg.cy;
-    float4 *out = dst_on_device ? (float4 *)dst : h->d_pub_out;
+    float4 *out = dst_on_device ? (float4 *)dst : h->pub_out.as<float4>();
     const uint8_t *img = (const uint8_t *)h->hc.img_base + (int64_t)slot * h->hc.slot_elems;
     const float *dep = (const float *)h->hc.depth_base + (int64_t)slot * h->hc.slot_elems;
     hipError_t e = total ? launch_cloud_raw(img, dep, h->hc.pitch, w, hh, p, eigen33_products(h), out, h->stream) : hipSuccess;
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "raw cloud launch: %s", hipGetErrorString(e));
     // the call returns when the points are there: nothing enqueued later (an upload into this slot) can overtake the read
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->d_pub_out, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost));
+    if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->pub_out.p, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost));
     return DSM_OK;
 }
 

@@ -5,7 +5,7 @@ tests/render_scale_cases.py; tests/test_cpu_render_align_scale.py asserts the sa
   1. the pixel loops' second trip (k_render_clear, k_render_resolve): a 2048 x 1100 image
   2. the sequence loops' second trip (k_render_setup_run, k_cloud_scan with k_render_setup_map, k_render_splat,
      k_render_splat_big): 2.25 M records, store runs and map part both above 1 048 576
-  3. one handle through many geometries: render_reserve and align_reserve regrow and reuse
+  3. one handle through many geometries: scratch_grow regrows and reuses the render and align scratch
   4. k_align's second trip: a 640 x 416 frame at stride 1, and dsm_align_frame on it"""
 import time
 
