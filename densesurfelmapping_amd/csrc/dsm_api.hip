@@ -1593,7 +1593,15 @@ int dsm_fuse_map_inv(dsm_handle *h, int reference_frame_index, const uint8_t *im
     // of the map, what the frame changed comes back: the surfels it fused or deleted, the slots it refilled or moved, what it
     // appended (dropin_delta_end)
     int m = 0;
-    if ((rc = dropin_delta_end(h, local, cap, (int)n_back, &m))) return rc;
+    if ((rc = dropin_delta_end(h, local, cap, (int)n_back, &m))) {
+        // the caller's array is too small (not the handle's capacity, reported by check_status before m is known: *n_local stays):
+        // the size it needs; nothing of it was written, the shadow is not trusted again
+        if (rc == DSM_E_CAPACITY && m > cap) {
+            *n_new = h->h_scalars[1];
+            *n_local = m;
+        }
+        return rc;
+    }
     *n_new = h->h_scalars[1];
     *n_local = m;
     h->shadow_n = m;

@@ -149,7 +149,12 @@ int dsm_fuse_initialize_map(dsm_handle *h, int reference_frame_index, const uint
                             int32_t n_local, dsm_surfel *new_out, int32_t new_cap, int32_t *n_new);
 
 /* SurfelMap::fuse_map: the call above followed by the reference's order-exact refill of deleted
- * slots and swap-with-last compaction.  *n_local is updated; cap is the capacity of local[]. */
+ * slots and swap-with-last compaction.  *n_local is updated; cap is the capacity of local[].  More surfels than cap:
+ * DSM_E_CAPACITY, *n_local = the count needed, *n_new = the frame's new surfels, local[] is left as it was handed in (its
+ * records are the caller's first n); the frame has been fused on the device, so the same call again with room starts
+ * from the caller's array once more.  More surfels than the HANDLE holds (dsm_config.surfel_capacity): DSM_E_CAPACITY as
+ * well, but *n_local and *n_new are left as they were handed in and local[] is untouched -- no count is known, a larger
+ * handle is needed (dsm_last_error names which of the two limits was hit). */
 int dsm_fuse_map(dsm_handle *h, int reference_frame_index, const uint8_t *image, size_t img_step,
                  const float *depth, size_t depth_step, const float *pose16, dsm_surfel *local,
                  int32_t *n_local, int32_t cap, int32_t *n_new);

@@ -113,13 +113,14 @@ class FusionFunctions {
                  int *n_new_out = nullptr) {
         static_assert(sizeof(Surfel) == sizeof(dsm_surfel), "SurfelElement must keep the layout of elements.h:22-31");
         int32_t n_local = (int32_t)local_surfels.size(), n_new = 0;
+        const size_t n_in = (size_t)n_local;
         local_surfels.resize((size_t)n_local + (size_t)n_seed_);
         Pose inv_store(pose);
         const float *inv = detail::PoseInverse<Pose>::get(pose, inv_store, 0); // FF.cpp:59, in the caller's arithmetic
         const int rc = dsm_fuse_map_inv(h_, reference_index, (const uint8_t *)image.data, (size_t)image.step, (const float *)depth.data,
                                         (size_t)depth.step, pose.data(), inv, reinterpret_cast<dsm_surfel *>(local_surfels.data()),
                                         &n_local, (int32_t)local_surfels.size(), &n_new);
-        local_surfels.resize((size_t)n_local);
+        local_surfels.resize(rc == DSM_OK ? (size_t)n_local : n_in); // (on an error the vector is the caller's again)
         if (n_new_out) *n_new_out = n_new;
         return check(rc, h_);
     }
