@@ -24,6 +24,7 @@
 #include "dsm_device.h"
 #include "dsm_frame_copy.h"
 #include "dsm_frame_format.h"
+#include "dsm_frame_rings.h"
 #include "dsm_ranges.h"
 
 using namespace dsm;
@@ -42,7 +43,7 @@ hipError_t batch_streams_reserve(int device); // see BatchStreamPool
 hipStream_t batch_stream_at(int device, int i);
 constexpr int kUploadStreams = 2;
 hipStream_t device_upload_stream(int device, int *which, bool high_priority); // asynchronous frame uploads of the handles on the device (dsm_frame_upload_async)
-constexpr uint64_t kBatchBit = 1ull << 62;    // UpEntry::pending: a batch stream has not waited for this upload of the handle yet
+constexpr uint64_t kBatchBit = 1ull << 62;    // up_ring's pending: a batch stream has not waited for this upload of the handle yet
 
 } // namespace
 
@@ -206,7 +207,7 @@ struct dsm_handle {
     // of its throughput): uploads that follow one wait for ev_fence, recorded once behind the batch
     hipEvent_t ev_fence = nullptr;
     bool fence_pending = false;
-    // dsm_frame(s)_upload_async: the last kUpRing asynchronous uploads of this handle, oldest first.  ev = the upload has
+    // dsm_frame(s)_upload_async: the last four asynchronous uploads of this handle, oldest first.  ev = the upload has
     // landed (recorded on the device's upload stream the handle was dealt: ONE stream, so an entry's event covers every
     // entry before it); [lo, hi) = the frame slots it wrote; pending = which consumers have not been ordered behind it
     // yet (bit p: pipeline p, kSerialBit: the map stream, kBatchBit: a batch stream).  A consumer waits for the NEWEST
@@ -214,17 +215,11 @@ struct dsm_handle {
     // (send chunk k+1, then enqueue chunk k) chunk k waits for upload k, and upload k+1 -- ordered behind chunk k-1, whose
     // slots it overwrites -- runs beside chunk k's kernels.  (Until round 5 there was one event, re-recorded by every
     // upload: chunk k waited for upload k+1, which waited for chunk k-1 -- a handle streaming alone had no overlap at all.)
-    struct UpEntry {
-        hipEvent_t ev = nullptr;
-        int lo = 0, hi = 0;
-        uint64_t pending = 0;
-    };
-    static constexpr int kUpRing = 4;
-    UpEntry up_ring[kUpRing];
-    int up_n = 0;
+    using Ring = SlotRing<hipEvent_t, 4>; // (dsm_frame_rings.h)
+    Ring up_ring;
     // the frame slots the frames being submitted read (set by the enqueue calls that know them; everything otherwise)
     int read_lo = 0, read_hi = INT32_MAX;
-    // ... and the other direction: which enqueue calls still READ which slots.  rd_ring = the last kRdRing calls of
+    // ... and the other direction: which enqueue calls still READ which slots.  rd_ring = the last four calls of
     // dsm_replay_enqueue, oldest first: ev = everything the call enqueued has finished (recorded on the map stream behind it:
     // it covers the calls before it), [lo, hi) = the slots its frames read.  An asynchronous upload waits for the newest
     // entry that reads a slot it overwrites -- not for everything enqueued so far: with three groups of slots in turn
@@ -232,13 +227,7 @@ struct dsm_handle {
     // hardware queue the upload stream shares with the handle's pipeline streams.  reads_untracked: frames were enqueued
     // some other way (frame by frame, through a batch, timed / debug / drop-in calls): the next upload waits for the whole
     // map stream once (ev_fence), which covers them -- and, the upload stream being in order, every later upload too.
-    struct RdEntry {
-        hipEvent_t ev = nullptr;
-        int lo = 0, hi = 0;
-    };
-    static constexpr int kRdRing = 4;
-    RdEntry rd_ring[kRdRing];
-    int rd_n = 0;
+    Ring rd_ring; // (pending: every bit, and nobody clears one -- an entry that leaves always folds into the next)
     bool reads_untracked = true;
     int up_which = -1; // which of the device's upload streams this handle's uploads take (dealt out at its first upload)
     // dsm_replay_enqueue_host: an event behind each of the last kHostRing calls (dsm_replay_wait)
@@ -348,30 +337,6 @@ int reserve_params(dsm_handle *h, int n) {
     return DSM_OK;
 }
 
-// inv16: the caller's own world -> cam matrix (pose.inverse() of ITS matrix library, FF.cpp:59), or nullptr: the closed
-// form of dsm_math.h
-int stage_params(dsm_handle *h, int slot, int ref_idx, const float *pose16, const float *inv16 = nullptr) {
-    if (slot < 0 || slot >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slot, h->hc.n_slots);
-    int rc = reserve_params(h, 1);
-    if (rc) return rc;
-    const int ring = (int)(h->frames_submitted % kParamRing);
-    FrameParams &fp = h->h_params[ring];
-    memcpy(fp.pose, pose16, sizeof fp.pose);
-    if (inv16) memcpy(fp.inv, inv16, sizeof fp.inv);
-    else inverse4<float>(fp.pose, fp.inv); // FF.cpp:59
-    fp.ref_idx = ref_idx;
-    fp.slot = slot;
-    fp.pad[0] = fp.pad[1] = 0;
-    if (h->n_pipe == 1) { // everything is on one stream: stream order is enough
-        HIP_TRY(h, hipMemcpyAsync(h->d_params + ring, &fp, sizeof fp, hipMemcpyHostToDevice, h->stream));
-        return DSM_OK;
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_params + ring, &fp, sizeof fp, hipMemcpyHostToDevice, h->copy_stream));
-    HIP_TRY(h, hipEventRecord(h->ev_params, h->copy_stream));
-    h->params_pending = ~0ull;
-    return DSM_OK;
-}
-
 // stage the params of up to n consecutive frames with one host-to-device copy; returns how many
 // were staged (limited by the ring's wrap-around point)
 // defer_copy: the entries are only written to the page-locked ring; whoever submits the frames copies them to the device on the
@@ -379,8 +344,7 @@ int stage_params(dsm_handle *h, int slot, int ref_idx, const float *pose16, cons
 int stage_params_batch(dsm_handle *h, int n, const int32_t *slots, const int32_t *ref_idx, const float *poses16, const float *inv_poses16, int *staged,
                        hipStream_t batch_stream = nullptr, bool defer_copy = false) {
     const int ring = (int)(h->frames_submitted % kParamRing);
-    int m = n < kParamRing - ring ? n : kParamRing - ring;
-    if (m > kParamRing / 2) m = kParamRing / 2;
+    const int m = param_chunk(h->frames_submitted, n, kParamRing);
     int rc = reserve_params(h, m);
     if (rc) return rc;
     for (int i = 0; i < m; i++) {
@@ -405,17 +369,35 @@ int stage_params_batch(dsm_handle *h, int n, const int32_t *slots, const int32_t
     *staged = m;
     return DSM_OK;
 }
+// ... and of one frame.  inv16: the caller's own world -> cam matrix (pose.inverse() of ITS matrix library, FF.cpp:59), or nullptr:
+// the closed form of dsm_math.h
+int stage_params(dsm_handle *h, int slot, int ref_idx, const float *pose16, const float *inv16 = nullptr) {
+    int staged = 0;
+    return stage_params_batch(h, 1, &slot, &ref_idx, pose16, inv16, &staged);
+}
 
 // Order `st` behind the asynchronous frame uploads that wrote a slot in [h->read_lo, h->read_hi), once per consumer
-// (`bits` = the consumer's bits of UpEntry::pending, see dsm_handle): the newest such upload's event covers the older ones.
+// (`bits` = the consumer's bits of the entries' `pending`, see dsm_handle): the newest such upload's event covers the older ones.
 int wait_uploads(dsm_handle *h, hipStream_t st, uint64_t bits) {
-    for (int i = h->up_n - 1; i >= 0; i--) {
-        dsm_handle::UpEntry &e = h->up_ring[i];
-        if (!(e.pending & bits) || e.lo >= h->read_hi || h->read_lo >= e.hi) continue;
-        HIP_TRY(h, hipStreamWaitEvent(st, e.ev, 0));
-        for (int k = 0; k <= i; k++) h->up_ring[k].pending &= ~bits;
-        break;
+    const int i = h->up_ring.newest_overlapping(h->read_lo, h->read_hi, bits);
+    if (i < 0) return DSM_OK;
+    HIP_TRY(h, hipStreamWaitEvent(st, h->up_ring.e[i].ev, 0));
+    h->up_ring.clear_through(i, bits);
+    return DSM_OK;
+}
+// A new newest entry of one of the handle's slot rings for an operation on slots [lo, hi) that `st` has just been given: its event,
+// recorded behind the operation
+int ring_record(dsm_handle *h, dsm_handle::Ring &ring, int lo, int hi, hipStream_t st) {
+    dsm_handle::Ring::Entry &e = ring.push(lo, hi, ~0ull);
+    if (!e.ev) {
+        const hipError_t err = hipEventCreateWithFlags(&e.ev, hipEventDisableTiming);
+        if (err != hipSuccess) {
+            e.ev = nullptr;
+            ring.drop_newest();
+            return fail(h, DSM_E_HIP, "hipEventCreateWithFlags(&ev, hipEventDisableTiming): %s", hipGetErrorString(err));
+        }
     }
+    HIP_TRY(h, hipEventRecord(e.ev, st));
     return DSM_OK;
 }
 // [lo, hi) of n slot indices
@@ -448,7 +430,7 @@ int tail_bound(const dsm_handle *h) { return h->tail_large ? h->hc.cap : 0; }
 // captured graphs that hold the tail are dropped (once per handle) and come back with its extra workgroups.
 int map_grows(dsm_handle *h, int frames) {
     if (h->tail_large) return DSM_OK;
-    if ((int64_t)h->map_upper + (int64_t)(frames - 1) * h->hc.n_seed <= (int64_t)kTailFastWords * 64) return DSM_OK;
+    if (!tail_may_be_large(h->map_upper, frames, h->hc.n_seed, (int64_t)kTailFastWords * 64)) return DSM_OK;
     h->tail_large = true;
     // The graphs may be in flight: they are set aside, not destroyed -- and nothing is waited for (until round 6 the map stream
     // was drained here: 50 ms in the middle of a streamed replay, a quarter of a 3 000-frame run) -- and go at the handle's next
@@ -657,76 +639,91 @@ int upload_host_frames(dsm_handle *h, const HostFrames &f0, int slot_base, int f
     return DSM_OK;
 }
 
+// ---- what the four submit functions below say in common
+
+// Frames are about to be enqueued that the drop-in calls know nothing of: the shadow of the map and the clean dirty flags are gone, and
+// an upload that follows waits for the whole map stream (dsm_replay_enqueue, which lists what it reads, puts that flag back)
+void frames_enqueued(dsm_handle *h) {
+    h->shadow_n = -1;
+    h->dirty_flags_clean = false;
+    h->reads_untracked = true;
+}
+
+// `st` behind the latest params upload, once per consumer (`bits` of params_pending).  At depth 1 the params go up on the stream that
+// reads them and no bit is ever set.
+int wait_params(dsm_handle *h, hipStream_t st, uint64_t bits) {
+    if (!(h->params_pending & bits)) return DSM_OK;
+    HIP_TRY(h, hipStreamWaitEvent(st, h->ev_params, 0));
+    h->params_pending &= ~bits;
+    return DSM_OK;
+}
+
+// Stages lo .. hi of the frame on the pipeline with context `ctx`, on `st`: as the graph *g, captured at its first use (graphs carry
+// fuse_grid_bound / tail_bound: see capture) -- or, where there is none (g == nullptr: the serial replays, whose stage events `ev` a
+// graph would not hold) or under DSM_FLAG_NO_GRAPH, launched as they are with the running bound of the map size.
+int run_stages(dsm_handle *h, const DeviceCtx &ctx, bool with_compaction, int lo, int hi, hipStream_t st, hipGraphExec_t *g, hipEvent_t *ev = nullptr) {
+    if (!g || (h->cfg.flags & DSM_FLAG_NO_GRAPH)) {
+        const hipError_t e = launch_frame(ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, st, ev, lo, hi);
+        if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
+        return DSM_OK;
+    }
+    if (int rc = capture(h, ctx, with_compaction, lo, hi, g)) return rc;
+    HIP_TRY(h, hipGraphLaunch(*g, st));
+    return DSM_OK;
+}
+
+// The map stream has been given fuse + tail of k frames, the last of them on pipeline `last`.  Past depth 1 ONE event behind them
+// says that the buffers of the k pipelines are free again (the map stream is in order, and every record is a marker packet on it, the
+// serial spine of a sequence).  The taps read the state of the latest frame; the ring's cursor moves on (advance: the tail ran) and,
+// where the frames may add surfels (grows), so does the bound of the map size.
+int frames_fused(dsm_handle *h, int last, int k, bool grows, bool advance = true) {
+    dsm_handle::Pipe &lp = h->pipe[last];
+    if (h->n_pipe > 1) {
+        HIP_TRY(h, hipEventRecord(lp.ev_map, h->stream));
+        for (int j = 0; j < k; j++) h->pipe[last - j].ev_free = lp.ev_map;
+    }
+    h->hc = lp.ctx;
+    if (!advance) return DSM_OK;
+    h->frames_submitted += k;
+    if (grows) h->map_upper = map_upper_after(h->map_upper, k, h->hc.n_seed, h->hc.cap);
+    return DSM_OK;
+}
+
+// Frames that come with the enqueue call: `count` of them from host.image / host.depth on go into the frame slots slot_base ... on `st`,
+// the stream that runs their superpixel stages, with their parameters in front of them on the same stream (the ring entries of the
+// frames of a group are adjacent: the ring's length is a multiple of every group size).
+int upload_host_with_params(dsm_handle *h, const HostFrames &host, int slot_base, int count, hipStream_t st) {
+    const int ring = (int)(h->frames_submitted % kParamRing);
+    HIP_TRY(h, hipMemcpyAsync(h->d_params + ring, h->h_params + ring, sizeof(FrameParams) * (size_t)count, hipMemcpyHostToDevice, st));
+    return upload_host_frames(h, host, slot_base, 0, count, st);
+}
+
 // enqueue the kernels of one frame whose params were staged by stage_params: superpixel stages on the
 // frame's pipeline stream, fuse + tail on the map stream.  host: the frame itself, to go up in front of them (slot = pipeline)
 int submit_frame(dsm_handle *h, bool with_compaction, const HostFrames *host = nullptr) {
-    h->shadow_n = -1;
-    h->dirty_flags_clean = false;
-    h->reads_untracked = true; // (dsm_replay_enqueue, which lists what it reads, puts the flag back)
-    if (int rc = map_grows(h, 1)) return rc;
+    frames_enqueued(h);
+    int rc = map_grows(h, 1);
+    if (rc) return rc;
     const int p = (int)(h->frames_submitted % h->n_pipe);
     dsm_handle::Pipe &pp = h->pipe[p];
-    const bool eager = (h->cfg.flags & DSM_FLAG_NO_GRAPH) != 0;
     const int wc = with_compaction ? 1 : 0;
     if (h->n_pipe == 1) { // everything on the map stream, one graph
-        if (int rc = wait_uploads(h, h->stream, kSerialBit)) return rc;
-        if (host) {
-            const int ring = (int)(h->frames_submitted % kParamRing);
-            HIP_TRY(h, hipMemcpyAsync(h->d_params + ring, h->h_params + ring, sizeof(FrameParams), hipMemcpyHostToDevice, h->stream));
-            if (int rc = upload_host_frames(h, *host, 0, 0, 1, h->stream)) return rc;
-        }
-        if (eager) {
-            hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, nullptr);
-            if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
-        } else {
-            int rc = capture(h, pp.ctx, with_compaction, 0, kNumStages - 1, &pp.g_all[wc]);
-            if (rc) return rc;
-            HIP_TRY(h, hipGraphLaunch(pp.g_all[wc], h->stream));
-        }
+        if ((rc = wait_uploads(h, h->stream, kSerialBit))) return rc;
+        if (host && (rc = upload_host_with_params(h, *host, 0, 1, h->stream))) return rc;
+        if ((rc = run_stages(h, pp.ctx, with_compaction, 0, kNumStages - 1, h->stream, &pp.g_all[wc]))) return rc;
     } else {
         // the pipeline's buffers are free once the map stream has finished the frame that used them last,
         // and the frame's params must have landed
         HIP_TRY(h, hipStreamWaitEvent(pp.stream, pp.ev_free ? pp.ev_free : pp.ev_map, 0));
-        if (h->params_pending & (1ull << p)) {
-            HIP_TRY(h, hipStreamWaitEvent(pp.stream, h->ev_params, 0));
-            h->params_pending &= ~(1ull << p);
-        }
-        if (int rc = wait_uploads(h, pp.stream, 1ull << p)) return rc;
-        if (host) { // (behind ev_free: the frame that last read slot p has been fused)
-            const int ring = (int)(h->frames_submitted % kParamRing);
-            HIP_TRY(h, hipMemcpyAsync(h->d_params + ring, h->h_params + ring, sizeof(FrameParams), hipMemcpyHostToDevice, pp.stream));
-            if (int rc = upload_host_frames(h, *host, p, 0, 1, pp.stream)) return rc;
-        }
-        if (eager) {
-            hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, pp.stream, nullptr, 0, kLastSuperpixelStage);
-            if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
-        } else {
-            int rc = capture(h, pp.ctx, with_compaction, 0, kLastSuperpixelStage, &pp.g_sp);
-            if (rc) return rc;
-            HIP_TRY(h, hipGraphLaunch(pp.g_sp, pp.stream));
-        }
+        if ((rc = wait_params(h, pp.stream, 1ull << p))) return rc;
+        if ((rc = wait_uploads(h, pp.stream, 1ull << p))) return rc;
+        if (host && (rc = upload_host_with_params(h, *host, p, 1, pp.stream))) return rc; // (behind ev_free: the frame that last read slot p has been fused)
+        if ((rc = run_stages(h, pp.ctx, with_compaction, 0, kLastSuperpixelStage, pp.stream, &pp.g_sp))) return rc;
         HIP_TRY(h, hipEventRecord(pp.ev_sp, pp.stream));
         HIP_TRY(h, hipStreamWaitEvent(h->stream, pp.ev_sp, 0));
-        if (eager) {
-            hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
-            if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
-        } else {
-            int rc = capture(h, pp.ctx, with_compaction, kLastSuperpixelStage + 1, kNumStages - 1, &pp.g_map[wc]);
-            if (rc) return rc;
-            HIP_TRY(h, hipGraphLaunch(pp.g_map[wc], h->stream));
-        }
+        if ((rc = run_stages(h, pp.ctx, with_compaction, kLastSuperpixelStage + 1, kNumStages - 1, h->stream, &pp.g_map[wc]))) return rc;
     }
-    if (h->n_pipe > 1) {
-        HIP_TRY(h, hipEventRecord(pp.ev_map, h->stream));
-        pp.ev_free = pp.ev_map;
-    }
-    h->hc = pp.ctx; // taps read the state of the latest frame
-    h->frames_submitted++;
-    if (with_compaction) {
-        h->map_upper += h->hc.n_seed;
-        if (h->map_upper > h->hc.cap) h->map_upper = h->hc.cap;
-    }
-    return DSM_OK;
+    return frames_fused(h, p, 1, with_compaction);
 }
 
 // Frame groups.  The superpixel stages of a frame need nothing but the frame, so those of G consecutive frames -- which
@@ -735,16 +732,14 @@ int submit_frame(dsm_handle *h, bool with_compaction, const HostFrames *host = n
 // then follow on the map stream in frame order.  The pipelines form two groups (four from depth 16 on) used in turn,
 // so the batches of the next group(s) run while the map stream works the previous one off.  Same results as frame by
 // frame; the params of the G frames must have been staged, and frames_submitted be a multiple of G.
-int group_size(const dsm_handle *h) { return (h->n_pipe == 12 || h->n_pipe == 24) ? h->n_pipe / 3 : h->n_pipe >= 16 ? h->n_pipe / 4 : h->n_pipe / 2; }
 bool group_path(const dsm_handle *h) {
     return h->n_pipe >= 4 && h->d_pipe_ctxs && !(h->cfg.flags & DSM_FLAG_NO_GRAPH);
 }
 int submit_group(dsm_handle *h, const HostFrames *host = nullptr) {
-    h->shadow_n = -1;
-    h->dirty_flags_clean = false;
-    h->reads_untracked = true;
-    const int G = group_size(h);
-    if (int rc = map_grows(h, G)) return rc;
+    frames_enqueued(h);
+    const int G = group_size(h->n_pipe);
+    int rc = map_grows(h, G);
+    if (rc) return rc;
     const int p0 = (int)(h->frames_submitted % h->n_pipe); // a multiple of G
     const int half = p0 / G;
     // group k runs on the stream of pipeline k: HIP spreads streams over its four hardware queues in creation order, and
@@ -761,22 +756,12 @@ int submit_group(dsm_handle *h, const HostFrames *host = nullptr) {
     // and the map stream waits for lead.ev_sp below.  A later submit_frame on one of these pipelines (ragged end of a
     // replay) stages its own params first, which sets its bit again (stage_params: params_pending = ~0u) -- so a cleared
     // bit never stands for an upload its stream has not been ordered behind.
-    const uint64_t mask = ((1ull << G) - 1ull) << p0;
-    if (h->params_pending & mask) {
-        HIP_TRY(h, hipStreamWaitEvent(lead.stream, h->ev_params, 0));
-        h->params_pending &= ~mask;
-    }
+    if ((rc = wait_params(h, lead.stream, ((1ull << G) - 1ull) << p0))) return rc;
     // (only `lead` reads these frames' slots before the map stream does -- which waits for lead.ev_sp below -- and only the
     // lead stream's bit is cleared: a later frame-by-frame submit on another of these pipelines waits for itself)
-    if (int rc = wait_uploads(h, lead.stream, 1ull << half)) return rc;
+    if ((rc = wait_uploads(h, lead.stream, 1ull << half))) return rc;
     // the G frames themselves, if they came with the call: slots p0 .. p0 + G - 1, behind the wait for the frames that read them last
-    if (host) {
-        // ... and their parameters in front of them, on the same stream (the ring entries of G consecutive frames are adjacent: the
-        // ring's length is a multiple of every group size)
-        const int ring = (int)(h->frames_submitted % kParamRing);
-        HIP_TRY(h, hipMemcpyAsync(h->d_params + ring, h->h_params + ring, sizeof(FrameParams) * (size_t)G, hipMemcpyHostToDevice, lead.stream));
-        if (int rc = upload_host_frames(h, *host, p0, 0, G, lead.stream)) return rc;
-    }
+    if (host && (rc = upload_host_with_params(h, *host, p0, G, lead.stream))) return rc;
     if (!h->g_group[half]) {
         const std::string err = capture_graph([&](hipStream_t st) {
             return launch_frame(lead.ctx, eigen33_products(h), fuse_grid_bound(h), tail_bound(h), true, st, nullptr, 0, kLastSuperpixelStage, h->d_pipe_ctxs + p0, G, 4);
@@ -789,99 +774,103 @@ int submit_group(dsm_handle *h, const HostFrames *host = nullptr) {
     // fuse + tail of the G frames, in frame order, as one graph on the map stream (a graph launch per frame costs the
     // map stream more than the two kernels do)
     if (!h->g_group_map[half]) {
-        const std::string err = capture_graph([&](hipStream_t st) {
-            hipError_t le = hipSuccess;
-            for (int j = 0; j < G && le == hipSuccess; j++)
-                le = launch_frame(h->pipe[p0 + j].ctx, eigen33_products(h), fuse_grid_bound(h), tail_bound(h), true, st, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
-            return le;
-        }, &h->g_group_map[half]);
-        if (!err.empty()) return fail(h, DSM_E_HIP, "%s", err.c_str());
-        if (!h->tail_large && h->hc.cap > kTailFastWords * 64 && !h->g_group_map_large[half]) { // the large-map form, for later
-            const std::string err2 = capture_graph([&](hipStream_t st) {
+        const auto capture_map = [&](int tail, hipGraphExec_t *out) {
+            return capture_graph([&](hipStream_t st) {
                 hipError_t le = hipSuccess;
                 for (int j = 0; j < G && le == hipSuccess; j++)
-                    le = launch_frame(h->pipe[p0 + j].ctx, eigen33_products(h), fuse_grid_bound(h), h->hc.cap, true, st, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
+                    le = launch_frame(h->pipe[p0 + j].ctx, eigen33_products(h), fuse_grid_bound(h), tail, true, st, nullptr, kLastSuperpixelStage + 1, kNumStages - 1);
                 return le;
-            }, &h->g_group_map_large[half]);
-            if (!err2.empty()) return fail(h, DSM_E_HIP, "%s", err2.c_str());
-        }
+            }, out);
+        };
+        std::string err = capture_map(tail_bound(h), &h->g_group_map[half]);
+        if (err.empty() && !h->tail_large && h->hc.cap > kTailFastWords * 64 && !h->g_group_map_large[half])
+            err = capture_map(h->hc.cap, &h->g_group_map_large[half]); // the large-map form, for later
+        if (!err.empty()) return fail(h, DSM_E_HIP, "%s", err.c_str());
     }
     HIP_TRY(h, hipGraphLaunch(h->g_group_map[half], h->stream));
-    // ONE event for the group (every record is a marker packet on the map stream, the serial spine of a sequence)
-    HIP_TRY(h, hipEventRecord(h->pipe[p0 + G - 1].ev_map, h->stream));
-    for (int j = 0; j < G; j++) h->pipe[p0 + j].ev_free = h->pipe[p0 + G - 1].ev_map;
-    h->hc = h->pipe[p0 + G - 1].ctx; // taps read the state of the latest frame
-    h->frames_submitted += G;
-    const int64_t up = (int64_t)h->map_upper + (int64_t)G * h->hc.n_seed;
-    h->map_upper = up > h->hc.cap ? h->hc.cap : (int)up;
-    return DSM_OK;
+    return frames_fused(h, p0 + G - 1, G, true);
 }
 
 // run some or all stages of the next frame serially on the map stream (timed replays, state-level taps)
 int submit_serial(dsm_handle *h, bool with_compaction, hipEvent_t *ev, int lo, int hi) {
-    h->shadow_n = -1;
-    h->dirty_flags_clean = false;
-    h->reads_untracked = true;
+    frames_enqueued(h);
     const int p = (int)(h->frames_submitted % h->n_pipe);
-    dsm_handle::Pipe &pp = h->pipe[p];
-    if (h->n_pipe > 1 && (h->params_pending & kSerialBit)) {
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_params, 0));
-        h->params_pending &= ~kSerialBit;
-    }
-    if (int rc = wait_uploads(h, h->stream, kSerialBit)) return rc;
-    hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, ev, lo, hi);
-    if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
-    if (h->n_pipe > 1) {
-        HIP_TRY(h, hipEventRecord(pp.ev_map, h->stream));
-        pp.ev_free = pp.ev_map;
-    }
-    h->hc = pp.ctx;
+    int rc = wait_params(h, h->stream, kSerialBit);
+    if (rc || (rc = wait_uploads(h, h->stream, kSerialBit))) return rc;
+    if ((rc = run_stages(h, h->pipe[p].ctx, with_compaction, lo, hi, h->stream, nullptr, ev))) return rc;
+    if ((rc = frames_fused(h, p, 1, with_compaction, hi == kNumStages - 1))) return rc; // (the tail advances the pipeline's cursor)
     h->fence_pending = true; // (timed / debug replays: uploads wait for the whole stream)
-    if (hi == kNumStages - 1) { // the tail advanced the pipeline's cursor
-        h->frames_submitted++;
-        if (with_compaction) {
-            h->map_upper += h->hc.n_seed;
-            if (h->map_upper > h->hc.cap) h->map_upper = h->hc.cap;
-        }
-    }
     return DSM_OK;
 }
 
 // ---- drop-in calls: everything on the map stream, in two parts, so that the host can look at the caller's surfel
 // array while the superpixel stages (which need the frame only) already run
 int submit_part(dsm_handle *h, bool with_compaction, bool map_part) {
-    h->reads_untracked = true;
-    if (int rc = map_grows(h, 1)) return rc;
+    h->reads_untracked = true; // (not frames_enqueued: the drop-in calls keep the shadow and the dirty flags themselves)
+    int rc = map_grows(h, 1);
+    if (rc) return rc;
     const int p = (int)(h->frames_submitted % h->n_pipe);
     dsm_handle::Pipe &pp = h->pipe[p];
-    if (h->n_pipe > 1 && (h->params_pending & kSerialBit)) {
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_params, 0));
-        h->params_pending &= ~kSerialBit;
-    }
-    if (int rc = wait_uploads(h, h->stream, kSerialBit)) return rc;
+    if ((rc = wait_params(h, h->stream, kSerialBit)) || (rc = wait_uploads(h, h->stream, kSerialBit))) return rc;
     const int lo = map_part ? kLastSuperpixelStage + 1 : 0, hi = map_part ? kNumStages - 1 : kLastSuperpixelStage;
-    if (h->cfg.flags & DSM_FLAG_NO_GRAPH) {
-        hipError_t e = launch_frame(pp.ctx, eigen33_products(h), h->map_upper, h->map_upper, with_compaction, h->stream, nullptr, lo, hi);
-        if (e != hipSuccess) return fail(h, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
-    } else {
-        hipGraphExec_t *g = map_part ? &pp.g_map[with_compaction ? 1 : 0] : &pp.g_sp_main;
-        int rc = capture(h, pp.ctx, with_compaction, lo, hi, g);
+    if ((rc = run_stages(h, pp.ctx, with_compaction, lo, hi, h->stream, map_part ? &pp.g_map[with_compaction ? 1 : 0] : &pp.g_sp_main))) return rc;
+    return map_part ? frames_fused(h, p, 1, with_compaction) : DSM_OK;
+}
+
+// ---- the replay calls
+
+// what every call that fuses resident frames checks first: `missing` = one of the arrays its n frames need is null
+int check_replay_args(dsm_handle *h, int n, bool missing, const char *what = "null/negative argument") {
+    if (n < 0 || (n > 0 && missing)) return fail(h, DSM_E_INVALID, "%s", what);
+    if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
+    return DSM_OK;
+}
+
+// Stage and submit n frames: chunk by chunk of the parameter ring, as whole frame groups where the handle runs them and the cursor
+// stands at a group's start, frame by frame otherwise (and at the ragged end).  hf: the frames come with the call (frame i at
+// hf->image + i * hf->img_frame_step ...), and each submit sends its frames' parameters along with them instead of staging them here.
+int enqueue_frames(dsm_handle *h, int n, const int32_t *slots, const int32_t *ref_idx, const float *poses16, const float *inv_poses16, const HostFrames *hf) {
+    HostFrames at = hf ? *hf : HostFrames();
+    for (int i = 0; i < n;) {
+        int m = 0;
+        int rc = stage_params_batch(h, n - i, slots + i, ref_idx + i, poses16 + 16 * (size_t)i, inv_poses16 ? inv_poses16 + 16 * (size_t)i : nullptr, &m,
+                                    nullptr, hf != nullptr);
         if (rc) return rc;
-        HIP_TRY(h, hipGraphLaunch(*g, h->stream));
-    }
-    if (map_part) {
-        if (h->n_pipe > 1) {
-            HIP_TRY(h, hipEventRecord(pp.ev_map, h->stream));
-            pp.ev_free = pp.ev_map;
+        for (int j = 0; j < m;) {
+            const int G = group_size(h->n_pipe);
+            if (hf) {
+                at.image = hf->image + (size_t)(i + j) * hf->img_frame_step;
+                at.depth = (const char *)hf->depth + (size_t)(i + j) * hf->depth_frame_step;
+            }
+            const bool group = group_path(h) && m - j >= G && h->frames_submitted % G == 0;
+            if ((rc = group ? submit_group(h, hf ? &at : nullptr) : submit_frame(h, true, hf ? &at : nullptr))) return rc;
+            j += group ? G : 1;
         }
-        h->hc = pp.ctx;
-        h->frames_submitted++;
-        if (with_compaction) {
-            h->map_upper += h->hc.n_seed;
-            if (h->map_upper > h->hc.cap) h->map_upper = h->hc.cap;
-        }
+        i += m;
     }
     return DSM_OK;
+}
+
+// A timed frame of the n handles hs has run with the stage events ev[0 .. kNumStages + 1] and has been waited for: its times and
+// counts into *out (per handle-frame, like `frames`)
+hipError_t add_stage_times(dsm_stage_times *out, hipEvent_t *ev, dsm_handle *const *hs, int n) {
+    for (int s = 0; s < kNumStages; s++) {
+        float ms = 0.0f;
+        const hipError_t e = hipEventElapsedTime(&ms, ev[s], ev[s + 1]);
+        if (e != hipSuccess) return e;
+        out->ms[s] += (double)ms;
+        out->launches[s] += 1;
+    }
+    float cal = 0.0f;
+    const hipError_t e = hipEventElapsedTime(&cal, ev[kNumStages], ev[kNumStages + 1]);
+    if (e != hipSuccess) return e;
+    out->event_overhead_ms += (double)cal * n;
+    out->frames += n;
+    for (int j = 0; j < n; j++) {
+        out->sum_new += hs[j]->h_scalars[1];
+        out->sum_local += hs[j]->h_scalars[0];
+    }
+    return hipSuccess;
 }
 
 constexpr size_t kParChunk = 1 << 20; // bytes per task of the parallel copies
@@ -1386,12 +1375,10 @@ void dsm_destroy(dsm_handle *h) {
     for (hipEvent_t e : h->ev_slot)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
-    for (int i = h->up_n - 1; i >= 0; i--) {
-        if (i == h->up_n - 1) (void)hipEventSynchronize(h->up_ring[i].ev);
-        (void)hipEventDestroy(h->up_ring[i].ev);
-    }
-    for (int i = 0; i < dsm_handle::kRdRing; i++)
-        if (h->rd_ring[i].ev) (void)hipEventDestroy(h->rd_ring[i].ev);
+    if (h->up_ring.n) (void)hipEventSynchronize(h->up_ring.e[h->up_ring.n - 1].ev);
+    for (dsm_handle::Ring *ring : {&h->up_ring, &h->rd_ring})
+        for (dsm_handle::Ring::Entry &e : ring->e)
+            if (e.ev) (void)hipEventDestroy(e.ev);
     for (int i = 0; i < dsm_handle::kHostRing; i++)
         if (h->host_ring[i]) (void)hipEventDestroy(h->host_ring[i]);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
@@ -2765,20 +2752,16 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
         if (h->reads_untracked) {
             HIP_TRY(h, hipStreamWaitEvent(up, h->batch_order_ev, 0));
             h->reads_untracked = false;
-            h->rd_n = 0;
+            h->rd_ring.reset();
         }
     } else if (h->reads_untracked) {
         HIP_TRY(h, hipEventRecord(h->ev_fence, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(up, h->ev_fence, 0));
         h->reads_untracked = false;
-        h->rd_n = 0; // (covered by the fence; the events stay in their places for reuse)
+        h->rd_ring.reset(); // (covered by the fence)
     } else {
-        for (int i = h->rd_n - 1; i >= 0; i--) {
-            const dsm_handle::RdEntry &e = h->rd_ring[i];
-            if (e.lo >= slot0 + n || slot0 >= e.hi) continue;
-            HIP_TRY(h, hipStreamWaitEvent(up, e.ev, 0));
-            break;
-        }
+        const int i = h->rd_ring.newest_overlapping(slot0, slot0 + n, ~0ull);
+        if (i >= 0) HIP_TRY(h, hipStreamWaitEvent(up, h->rd_ring.e[i].ev, 0));
     }
     uint8_t *di = (uint8_t *)h->hc.img_base + (int64_t)slot0 * h->hc.slot_elems;
     float *dd = (float *)h->hc.depth_base + (int64_t)slot0 * h->hc.slot_elems;
@@ -2818,29 +2801,8 @@ static int frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *i
     if (u16) rc = upload_depth_u16(h, slot0, n, depth, depth_step, depth_frame_step, hipMemcpyHostToDevice, *u16, up);
     else if (!dep_tight) rc = copy_planes(h, dd, depth, pd, hipMemcpyHostToDevice, up);
     if (rc) return rc;
-    // a ring entry for this upload; when the ring is full the oldest entry is folded into the one after it (whose event
-    // is later on the same stream: waiting for it instead is safe) and its event is reused
-    hipEvent_t ev = nullptr;
-    if (h->up_n == dsm_handle::kUpRing) {
-        dsm_handle::UpEntry old = h->up_ring[0];
-        for (int i = 1; i < h->up_n; i++) h->up_ring[i - 1] = h->up_ring[i];
-        h->up_n--;
-        dsm_handle::UpEntry &nx = h->up_ring[0];
-        if (old.pending) {
-            nx.lo = old.lo < nx.lo ? old.lo : nx.lo;
-            nx.hi = old.hi > nx.hi ? old.hi : nx.hi;
-            nx.pending |= old.pending;
-        }
-        ev = old.ev;
-    }
-    if (!ev) HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    dsm_handle::UpEntry &e = h->up_ring[h->up_n++];
-    e.ev = ev;
-    e.lo = slot0;
-    e.hi = slot0 + n;
-    e.pending = ~0ull;
-    HIP_TRY(h, hipEventRecord(e.ev, up)); // (behind the u16 / colour conversions: the upload has landed when the slot's planes are there)
-    return DSM_OK;
+    // a ring entry for this upload, its event behind the u16 / colour conversions: the upload has landed when the slot's planes are there
+    return ring_record(h, h->up_ring, slot0, slot0 + n, up);
 }
 
 int dsm_frames_upload_async(dsm_handle *h, int slot0, int n, const uint8_t *image, size_t img_step, size_t img_frame_step,
@@ -2875,10 +2837,10 @@ int dsm_frames_upload_async_fmt(dsm_handle *h, int slot0, int n, const void *ima
 
 int dsm_frame_uploads_wait(dsm_handle *h) {
     if (!h) return DSM_E_INVALID;
-    if (!h->up_n) return DSM_OK;
+    if (!h->up_ring.n) return DSM_OK;
     int rc = bind_device(h);
     if (rc) return rc;
-    HIP_TRY(h, hipEventSynchronize(h->up_ring[h->up_n - 1].ev));
+    HIP_TRY(h, hipEventSynchronize(h->up_ring.e[h->up_ring.n - 1].ev));
     return DSM_OK;
 }
 
@@ -2888,10 +2850,8 @@ int dsm_fuse_frame_resident(dsm_handle *h, int slot, int reference_frame_index, 
 
 int dsm_fuse_frame_resident_inv(dsm_handle *h, int slot, int reference_frame_index, const float *pose16, const float *inv_pose16) {
     if (!h) return DSM_E_INVALID;
-    if (!pose16) return fail(h, DSM_E_INVALID, "null pose");
-    if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
-    int rc = bind_device(h);
-    if (rc) return rc;
+    int rc = check_replay_args(h, 1, !pose16, "null pose");
+    if (rc || (rc = bind_device(h))) return rc;
     const ReadSlots reads(h, slot, slot + 1);
     if ((rc = stage_params(h, slot, reference_frame_index, pose16, inv_pose16))) return rc;
     if ((rc = submit_frame(h, true))) return rc;
@@ -2912,34 +2872,16 @@ static int replay_enqueue_host(dsm_handle *h, int32_t n, const uint8_t *image, s
                                size_t depth_step, size_t depth_frame_step, const int32_t *ref_idx, const float *poses16, const float *inv_poses16,
                                const DepthU16 *u16, const ImageGray *gray = nullptr) {
     if (!h) return DSM_E_INVALID;
-    if (n < 0 || (n > 0 && (!image || !depth || !ref_idx || !poses16))) return fail(h, DSM_E_INVALID, "null/negative argument");
-    if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
+    int rc = check_replay_args(h, n, !image || !depth || !ref_idx || !poses16);
+    if (rc) return rc;
     if (h->hc.n_slots < h->n_pipe) return fail(h, DSM_E_INVALID, "dsm_replay_enqueue_host keeps a frame in the slot of its pipeline: %d frame slots for pipeline_depth %d", h->hc.n_slots, h->n_pipe);
     HostFrames hf = {image, depth, img_step, img_frame_step, depth_step, depth_frame_step, u16, gray};
-    int rc = check_frames(h, kNoSlots, 0, n, hf);
-    if (rc || (rc = bind_device(h))) return rc;
+    if ((rc = check_frames(h, kNoSlots, 0, n, hf)) || (rc = bind_device(h))) return rc;
     // the frames read -- and overwrite -- the slots of the pipelines they run on: uploads of the asynchronous kind that
     // follow wait for the whole stream
     std::vector<int32_t> slots((size_t)(n > 0 ? n : 0));
     for (int i = 0; i < n; i++) slots[(size_t)i] = (int32_t)((h->frames_submitted + i) % h->n_pipe);
-    for (int i = 0; i < n;) {
-        int m = 0;
-        if ((rc = stage_params_batch(h, n - i, slots.data() + i, ref_idx + i, poses16 + 16 * (size_t)i,
-                                     inv_poses16 ? inv_poses16 + 16 * (size_t)i : nullptr, &m, nullptr, true))) return rc;
-        for (int j = 0; j < m;) {
-            const int G = group_size(h);
-            hf.image = image + (size_t)(i + j) * img_frame_step;
-            hf.depth = (const char *)depth + (size_t)(i + j) * depth_frame_step;
-            if (group_path(h) && m - j >= G && h->frames_submitted % G == 0) {
-                if ((rc = submit_group(h, &hf))) return rc;
-                j += G;
-            } else {
-                if ((rc = submit_frame(h, true, &hf))) return rc;
-                j++;
-            }
-        }
-        i += m;
-    }
+    if ((rc = enqueue_frames(h, n, slots.data(), ref_idx, poses16, inv_poses16, &hf))) return rc;
     if (n) {
         h->fence_pending = true;
         h->reads_untracked = true;
@@ -2987,50 +2929,17 @@ int dsm_replay_wait(dsm_handle *h, int32_t calls_back) {
 int dsm_replay_enqueue_inv(dsm_handle *h, int32_t n, const int32_t *slots, const int32_t *ref_idx, const float *poses16,
                            const float *inv_poses16) {
     if (!h) return DSM_E_INVALID;
-    if (n < 0 || (n > 0 && (!slots || !ref_idx || !poses16))) return fail(h, DSM_E_INVALID, "null/negative argument");
-    if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
-    int rc = bind_device(h);
-    if (rc) return rc;
+    int rc = check_replay_args(h, n, !slots || !ref_idx || !poses16);
+    if (rc || (rc = bind_device(h))) return rc;
     int r_lo, r_hi;
     slot_range(slots, n, &r_lo, &r_hi);
     const ReadSlots reads(h, r_lo, r_hi);
     const bool untracked_before = h->reads_untracked;
-    for (int i = 0; i < n;) {
-        int m = 0;
-        if ((rc = stage_params_batch(h, n - i, slots + i, ref_idx + i, poses16 + 16 * (size_t)i,
-                                     inv_poses16 ? inv_poses16 + 16 * (size_t)i : nullptr, &m))) return rc;
-        for (int j = 0; j < m;) {
-            const int G = group_size(h);
-            if (group_path(h) && m - j >= G && h->frames_submitted % G == 0) {
-                if ((rc = submit_group(h))) return rc;
-                j += G;
-            } else {
-                if ((rc = submit_frame(h, true))) return rc;
-                j++;
-            }
-        }
-        i += m;
-    }
+    if ((rc = enqueue_frames(h, n, slots, ref_idx, poses16, inv_poses16, nullptr))) return rc;
     if (n) {
         h->fence_pending = true;
-        // what this call reads, for the uploads that follow (dsm_handle::rd_ring); the oldest entry folds into the one after it
-        hipEvent_t ev = nullptr;
-        if (h->rd_n == dsm_handle::kRdRing) {
-            const dsm_handle::RdEntry old = h->rd_ring[0];
-            for (int i = 1; i < h->rd_n; i++) h->rd_ring[i - 1] = h->rd_ring[i];
-            h->rd_n--;
-            dsm_handle::RdEntry &nx = h->rd_ring[0];
-            nx.lo = old.lo < nx.lo ? old.lo : nx.lo;
-            nx.hi = old.hi > nx.hi ? old.hi : nx.hi;
-            ev = old.ev;
-        }
-        if (!ev) ev = h->rd_ring[h->rd_n].ev; // (left behind by an earlier reset)
-        if (!ev) HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        dsm_handle::RdEntry &e = h->rd_ring[h->rd_n++];
-        e.ev = ev;
-        e.lo = r_lo;
-        e.hi = r_hi;
-        HIP_TRY(h, hipEventRecord(e.ev, h->stream));
+        // what this call reads, for the uploads that follow (dsm_handle::rd_ring)
+        if ((rc = ring_record(h, h->rd_ring, r_lo, r_hi, h->stream))) return rc;
         h->reads_untracked = untracked_before;
     }
     return DSM_OK;
@@ -3406,7 +3315,7 @@ int batch_stage(dsm_batch *b, int n_frames, int i0, int m, const int32_t *slots,
                                           b->stream);
         if (rc) return bfail(b, rc, "handle %zu: %s", j, h->err.c_str());
         if (staged != m) return bfail(b, DSM_E_STATE, "handle %zu: parameter rings of the batch are out of step", j);
-        if (h->up_n) { // frames this handle was sent with dsm_frame(s)_upload_async: the uploads that wrote the slots these frames read
+        if (h->up_ring.n) { // frames this handle was sent with dsm_frame(s)_upload_async: the uploads that wrote the slots these frames read
             int r_lo, r_hi;
             slot_range(slots + o, m, &r_lo, &r_hi);
             const ReadSlots reads(h, r_lo, r_hi);
@@ -3415,12 +3324,11 @@ int batch_stage(dsm_batch *b, int n_frames, int i0, int m, const int32_t *slots,
     }
     return DSM_OK;
 }
-// the handles' bookkeeping after m frames were enqueued on the batch stream; their streams wait for the batch
 // map_grows for a batch: its one graph holds the tails of all its handles
 int batch_map_grows(dsm_batch *b, int m) {
     if (b->tail_large) return DSM_OK;
     bool large = false;
-    for (const dsm_handle *h : b->hs) large = large || (int64_t)h->map_upper + (int64_t)(m - 1) * h->hc.n_seed > (int64_t)kTailFastWords * 64;
+    for (const dsm_handle *h : b->hs) large = large || tail_may_be_large(h->map_upper, m, h->hc.n_seed, (int64_t)kTailFastWords * 64);
     if (!large) return DSM_OK;
     b->tail_large = true;
     if (b->graph) { // (possibly in flight: set aside without a wait, destroyed at the batch's next synchronisation point)
@@ -3429,16 +3337,14 @@ int batch_map_grows(dsm_batch *b, int m) {
     }
     return DSM_OK;
 }
+// the handles' bookkeeping after m frames were enqueued on the batch stream; their streams wait for the batch
 int batch_advance(dsm_batch *b, int m) {
     BHIP_TRY(b, hipEventRecord(b->ev_out, b->stream));
     for (dsm_handle *h : b->hs) {
         h->batch_order_ev = b->ev_out; // (waited for when the handle's stream is next used)
-        h->shadow_n = -1;
-        h->dirty_flags_clean = false;
-        h->reads_untracked = true;
+        frames_enqueued(h);
         h->frames_submitted += m;
-        const int64_t up = (int64_t)h->map_upper + (int64_t)m * h->hc.n_seed;
-        h->map_upper = up > h->hc.cap ? h->hc.cap : (int)up;
+        h->map_upper = map_upper_after(h->map_upper, m, h->hc.n_seed, h->hc.cap);
         h->fence_pending = true;
     }
     return DSM_OK;
@@ -3540,10 +3446,7 @@ int dsm_batch_replay_enqueue_inv(dsm_batch *b, int32_t n_frames, const int32_t *
     if (int rc = batch_rings_in_step(b)) return rc;
     dsm_handle *h0 = b->hs[0];
     for (int i = 0; i < n_frames;) {
-        int m = n_frames - i;
-        const int ring = (int)(h0->frames_submitted % kParamRing);
-        if (m > kParamRing - ring) m = kParamRing - ring;
-        if (m > kParamRing / 2) m = kParamRing / 2;
+        const int m = param_chunk(h0->frames_submitted, n_frames - i, kParamRing);
         int rc = batch_stage(b, n_frames, i, m, slots, ref_idx, poses16, inv_poses16);
         if (rc) return rc;
         if ((rc = batch_map_grows(b, m))) return rc;
@@ -3592,20 +3495,7 @@ int dsm_batch_replay_timed(dsm_batch *b, int32_t n_frames, const int32_t *slots,
         if (e != hipSuccess) return bfail(b, DSM_E_HIP, "kernel launch: %s", hipGetErrorString(e));
         if ((rc = batch_advance(b, 1))) return rc;
         if ((rc = dsm_batch_synchronize(b))) return rc;
-        for (int s = 0; s < kNumStages; s++) {
-            float ms = 0.0f;
-            BHIP_TRY(b, hipEventElapsedTime(&ms, b->ev[s], b->ev[s + 1]));
-            out->ms[s] += (double)ms;
-            out->launches[s] += 1;
-        }
-        float cal = 0.0f;
-        BHIP_TRY(b, hipEventElapsedTime(&cal, b->ev[kNumStages], b->ev[kNumStages + 1]));
-        out->event_overhead_ms += (double)cal * n; // (per handle-frame, like `frames`)
-        out->frames += n;
-        for (dsm_handle *h : b->hs) {
-            out->sum_new += h->h_scalars[1];
-            out->sum_local += h->h_scalars[0];
-        }
+        BHIP_TRY(b, add_stage_times(out, b->ev, b->hs.data(), n));
     }
     return DSM_OK;
 }
@@ -3618,10 +3508,8 @@ extern "C" {
 int dsm_replay_timed(dsm_handle *h, int32_t n, const int32_t *slots, const int32_t *ref_idx, const float *poses16,
                      dsm_stage_times *out) {
     if (!h || !out) return DSM_E_INVALID;
-    if (n < 0 || (n > 0 && (!slots || !ref_idx || !poses16))) return fail(h, DSM_E_INVALID, "null/negative argument");
-    if (!h->map_valid) return fail(h, DSM_E_STATE, "no resident map: call dsm_map_upload first (n may be 0)");
-    int rc = bind_device(h);
-    if (rc) return rc;
+    int rc = check_replay_args(h, n, !slots || !ref_idx || !poses16);
+    if (rc || (rc = bind_device(h))) return rc;
     out->n_stages = kNumStages;
     for (int s = 0; s < kNumStages; s++) {
         out->name[s] = kStageNames[s];
@@ -3630,18 +3518,7 @@ int dsm_replay_timed(dsm_handle *h, int32_t n, const int32_t *slots, const int32
         if ((rc = stage_params(h, slots[i], ref_idx[i], poses16 + 16 * (size_t)i))) return rc;
         if ((rc = submit_serial(h, true, h->ev, 0, kNumStages - 1))) return rc;
         if ((rc = sync_and_fetch_counts(h))) return rc;
-        for (int s = 0; s < kNumStages; s++) {
-            float ms = 0.0f;
-            HIP_TRY(h, hipEventElapsedTime(&ms, h->ev[s], h->ev[s + 1]));
-            out->ms[s] += (double)ms;
-            out->launches[s] += 1;
-        }
-        float cal = 0.0f;
-        HIP_TRY(h, hipEventElapsedTime(&cal, h->ev[kNumStages], h->ev[kNumStages + 1]));
-        out->event_overhead_ms += (double)cal;
-        out->frames += 1;
-        out->sum_new += h->h_scalars[1];
-        out->sum_local += h->h_scalars[0];
+        HIP_TRY(h, add_stage_times(out, h->ev, &h, 1));
     }
     return DSM_OK;
 }

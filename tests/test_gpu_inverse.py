@@ -2,9 +2,9 @@
 
 The C++ facade (include/dsm_fusion_functions.hpp) calls dsm_fuse_initialize_map_inv / dsm_fuse_map_inv whenever the pose type
 has an inverse(), so this is the path an integrator runs.  Every form stages the inverses with index arithmetic of its own --
-stage_params (drop-in, one frame), stage_params_batch (resident replays, in chunks of kParamRing / 2 over a ring of kParamRing),
-the host-frame loop of dsm_replay_enqueue_host, batch_stage (handle-major: handle j's frames start at j * n_frames) -- and the
-frame groups read them G at a time.  Each case here feeds the inverses of tests/inverse_cases.py (near-exact, wrong on purpose,
+stage_params_batch (one frame for the drop-in calls, through stage_params; resident replays in chunks of kParamRing / 2 over a
+ring of kParamRing), enqueue_frames (the loop of dsm_replay_enqueue and dsm_replay_enqueue_host, the latter's frames advancing
+with it), batch_stage (handle-major: handle j's frames start at j * n_frames) -- and the frame groups read them G at a time.  Each case here feeds the inverses of tests/inverse_cases.py (near-exact, wrong on purpose,
 hostile) and compares the engine with PortOracle fed THE SAME inverses (dsmo_fuse_map_inv, pinned to the reference's own TU by
 tests/test_cpu.py::test_port_takes_the_callers_inverse): label image, seed table, surfel array and new-surfel count, every
 byte equal, NaN == NaN, after every frame where the form allows it, otherwise after every call.  Every case also checks that
