@@ -78,6 +78,8 @@ ABI_SYMBOLS = (
     "dsm_grid_distance", "dsm_field_compose",
     # free space carved by depth frames, the three-state map and its frontier
     "dsm_carve_params_init", "dsm_grid_carve", "dsm_grid_classify",
+    # connected components of a bit set of the grid: frontier clusters, obstacles as objects
+    "dsm_grid_components",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -232,6 +234,17 @@ class _CarveParams(C.Structure):
 
 class _SpacePlanes(C.Structure):
     _fields_ = [("state", C.c_void_p), ("known_free", C.c_void_p), ("frontier", C.c_void_p), ("cells", C.c_void_p), ("cells_cap", C.c_int32)]
+
+
+class _ComponentPlanes(C.Structure):
+    _fields_ = [("label", C.c_void_p), ("table", C.c_void_p), ("table_cap", C.c_int32)]
+
+
+# dsm_component (include/dsm.h): 64 bytes
+COMPONENT_DTYPE = np.dtype([("root", np.int32), ("count", np.int32), ("sum", np.int64, (3,)), ("lo", np.int32, (3,)), ("hi", np.int32, (3,)),
+                            ("tag", np.int32), ("reserved", np.int32)])
+assert COMPONENT_DTYPE.itemsize == 64
+CONNECT_FACES, CONNECT_ALL = 6, 26
 
 
 class _AlignParams(C.Structure):
@@ -504,6 +517,7 @@ def load_library():
     lib.dsm_carve_params_init.restype = None
     lib.dsm_grid_carve.argtypes = [_vp, C.POINTER(_GridSpec), C.POINTER(_CarveParams), C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]
     lib.dsm_grid_classify.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_SpacePlanes), _vp]
+    lib.dsm_grid_components.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_ComponentPlanes), _vp, _vp]
     lib.dsm_align_params_init.argtypes = [C.POINTER(_AlignParams)]
     lib.dsm_align_params_init.restype = None
     lib.dsm_align_equations.argtypes = [_vp, C.c_int, C.POINTER(_RenderCamera), _vp, _vp, _vp, C.POINTER(_AlignParams), _vp, _vp]
@@ -934,6 +948,47 @@ class FusionFunctions:
             raise e
         self._check(rc)
         return n.value
+
+    # ---- connected components of a bit set ------------------------------------------------------------
+    def grid_components(self, dims, src_ptr, connectivity=26, min_count=1, tag_ptr=None, label_ptr=None, table_ptr=None, table_cap=0):
+        """dsm_grid_components: the connected components (connectivity 6 or 26) of the bit set [nz, ny, wx] at the device pointer
+        src_ptr; dims = (nx, ny, nz).  label_ptr: a device plane int32 [nz, ny, nx] (the lowest linear index of the voxel's component,
+        -1 outside the set), table_ptr: COMPONENT_DTYPE [table_cap] in device memory for the components of at least min_count voxels,
+        ascending by root; either may be None.  tag_ptr: an int32 [nz, ny, nx] device plane whose value at a component's root becomes
+        its `tag`.  Returns (n_components, n_all).  More than table_cap: DsmError with code DSM_E_CAPACITY and .n_components = the count
+        needed, .n_all."""
+        st = _ComponentPlanes(_vp(label_ptr) if label_ptr else None, _vp(table_ptr) if table_ptr else None, int(table_cap))
+        n, n_all = C.c_int32(0), C.c_int32(0)
+        rc = self._lib.dsm_grid_components(self._h, int(dims[0]), int(dims[1]), int(dims[2]), int(connectivity), int(min_count), _vp(src_ptr),
+                                           _vp(tag_ptr) if tag_ptr else None, C.byref(st), C.byref(n), C.byref(n_all))
+        if rc == DSM_E_CAPACITY:
+            e = DsmError(rc, self._lib.dsm_last_error(self._h).decode())
+            e.n_components, e.n_all = n.value, n_all.value
+            raise e
+        self._check(rc)
+        return n.value, n_all.value
+
+    def grid_components_host(self, bits, nx, connectivity=26, min_count=1, tags=None, labels=True):
+        """The convenience for host data: the bit set `bits` (uint32 [nz, ny, wx]) and the optional int32 tag plane go to the device
+        through torch, the table is sized by a first call.  Returns (table as a COMPONENT_DTYPE array, n_all, labels int32 [nz, ny, nx]
+        or None)."""
+        import torch
+        b = np.ascontiguousarray(bits, np.uint32)
+        nz, ny, wx = b.shape
+        if wx != (nx + 31) // 32:
+            raise ValueError("bits is not [nz, ny, (nx + 31) // 32]")
+        dims = (nx, ny, nz)
+        d_src = torch.from_numpy(b.view(np.int32)).cuda()
+        d_tag = None if tags is None else torch.from_numpy(np.ascontiguousarray(tags, np.int32).reshape(nz, ny, nx)).cuda()
+        d_label = torch.empty((nz, ny, nx), dtype=torch.int32, device="cuda")
+        tag_ptr = None if d_tag is None else d_tag.data_ptr()
+        n, n_all = self.grid_components(dims, d_src.data_ptr(), connectivity, min_count, tag_ptr, label_ptr=d_label.data_ptr())
+        table = np.zeros(n, COMPONENT_DTYPE)
+        if n:
+            d_table = torch.empty((n * 8,), dtype=torch.int64, device="cuda")
+            self.grid_components(dims, d_src.data_ptr(), connectivity, min_count, tag_ptr, table_ptr=d_table.data_ptr(), table_cap=n)
+            table = d_table.cpu().numpy().view(COMPONENT_DTYPE).copy()
+        return table, n_all, (d_label.cpu().numpy() if labels else None)
 
     # ---- a depth frame against the rendered map -----------------------------------------------------
     def align_equations(self, slot, model_cam, model_depth_ptr, model_normal_ptr, T, params=None):

@@ -21,6 +21,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "dsm_components.h"
 #include "dsm_device.h"
 #include "dsm_frame_copy.h"
 #include "dsm_frame_format.h"
@@ -178,7 +179,7 @@ struct dsm_handle {
     std::vector<void *> allocs; // every hipMalloc of this handle
     std::vector<hipGraphExec_t> retired; // graphs replaced while possibly in flight (map_grows): destroyed at the next synchronisation point
     FrameParams *h_params = nullptr; // pinned staging ring
-    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size, [6] grid cells, [7] frontier cells, [8..9] carved voxels (64 bits); [64..127] the device's scalar block as it came
+    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size, [6] grid cells, [7] frontier cells, [8..9] carved voxels (64 bits), [10] components kept, [11] components; [64..127] the device's scalar block as it came
     int32_t *d_scalars = nullptr;    // the device's scalar block (64 ints: n_local @8, n_local_next @16, n_new @24, n_holes @32, status @48, delta count @56)
     FrameParams *d_params = nullptr;
     uint8_t *d_stage_img = nullptr; // one tightly packed frame on its way into a pitched slot
@@ -263,7 +264,9 @@ struct dsm_handle {
     //                  y pass, then (dsm_field_compose) the composed bit set and the planes that go to host memory
     //   align_planes   dsm_align_frame: the rendered model, px depths and then 3 * px normal components
     //   align_sums     dsm_align_equations / dsm_align_frame: the 29 sums (256 bytes, with their page-locked landing place h_align_sums)
-    DevScratch store_tmp, pub, pub_out, render_keys, render_splats, grid_splats, grid_planes, field, align_planes, align_sums;
+    //   components     dsm_grid_components: the label plane where the caller takes none, the work plane, the root and keep bit planes,
+    //                  the tile counts of both
+    DevScratch store_tmp, pub, pub_out, render_keys, render_splats, grid_splats, grid_planes, field, align_planes, align_sums, components;
     hipEvent_t ev_pub_dst = nullptr; // a device destination is written behind the null stream's work so far (as hipMemcpy would)
     std::vector<float> field_table; // dsm_field_compose's distance table as built on the host, until the call has synchronised
     // dsm_grid_carve: the frames' matrices and plane offsets as built on the host, until the call has synchronised (the device copy
@@ -1390,7 +1393,7 @@ void dsm_destroy(dsm_handle *h) {
     if (h->d_store) (void)hipFree(h->d_store);
     if (h->d_cloud) (void)hipFree(h->d_cloud);
     for (DevScratch *s : {&h->store_tmp, &h->pub, &h->pub_out, &h->render_keys, &h->render_splats, &h->grid_splats, &h->grid_planes, &h->field,
-                          &h->align_planes, &h->align_sums})
+                          &h->align_planes, &h->align_sums, &h->components})
         if (s->p) (void)hipFree(s->p);
     if (h->ev_pub_dst) (void)hipEventDestroy(h->ev_pub_dst);
     if (h->h_align_sums) (void)hipHostFree(h->h_align_sums);
@@ -2449,6 +2452,63 @@ int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const v
     const int32_t cells = h->h_scalars[7];
     *n_frontier = cells;
     if (p.cells && cells > p.cells_cap) return fail(h, DSM_E_CAPACITY, "%d frontier cells, room for %d", cells, p.cells_cap);
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ connected components of a bit set (dsm_k_components.h)
+
+int dsm_grid_components(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_count, const void *src_device,
+                        const int32_t *tag_src_device, const dsm_component_planes *planes_device, int32_t *n_components, int32_t *n_all) {
+    if (!h || !n_components) return DSM_E_INVALID;
+    if (!src_device || !planes_device) return fail(h, DSM_E_INVALID, "grid components: null source or planes");
+    if ((((uintptr_t)src_device | (uintptr_t)tag_src_device) & 3)) return fail(h, DSM_E_INVALID, "grid components: the bit set or the tag plane is not 4-byte aligned");
+    if (!grid_dims_ok(nx, ny, nz, kFieldMaxVoxels)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^26 voxels", nx, ny, nz);
+    if (connectivity != kConnectFaces && connectivity != kConnectAll) return fail(h, DSM_E_INVALID, "grid components: connectivity %d, neither 6 nor 26", connectivity);
+    if (min_count < 1) return fail(h, DSM_E_INVALID, "grid components: min_count %d", min_count);
+    const dsm_component_planes &p = *planes_device;
+    if (!p.label && !p.table) return fail(h, DSM_E_INVALID, "grid components: no output plane");
+    if (p.table && p.table_cap < 0) return fail(h, DSM_E_INVALID, "table_cap %d", p.table_cap);
+    if (((uintptr_t)p.label & 3) || ((uintptr_t)p.table & 7)) return fail(h, DSM_E_INVALID, "grid components: a device plane is not aligned to its element");
+    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
+    const size_t cap = p.table ? ((size_t)p.table_cap < n_vox ? (size_t)p.table_cap : n_vox) : 0; // (no more components than voxels)
+    {
+        const void *const q[2] = {p.label, p.table};
+        const size_t bytes[2] = {n_vox * sizeof(int32_t), cap ? cap * sizeof(dsm_component) : 1};
+        if (!planes_distinct(q, 2) || (p.label && p.table && ranges_overlap(p.label, bytes[0], p.table, bytes[1])))
+            return fail(h, DSM_E_INVALID, "grid components: two output planes are the same memory");
+        for (int a = 0; a < 2; a++) {
+            if (q[a] && ranges_overlap(q[a], bytes[a], src_device, n_words * sizeof(uint32_t)))
+                return fail(h, DSM_E_INVALID, "grid components: a plane overlaps the source");
+            if (q[a] && tag_src_device && ranges_overlap(q[a], bytes[a], tag_src_device, n_vox * sizeof(int32_t)))
+                return fail(h, DSM_E_INVALID, "grid components: a plane overlaps the tag plane");
+        }
+    }
+    int rc = bind_device(h);
+    if (rc) return rc;
+    // scratch, every part from a 256-byte boundary: the label plane where the caller takes none, the work plane, the two bit planes,
+    // the tile counts of both
+    const size_t tiles = (n_words + 255) / 256;
+    size_t at = 0;
+    const auto take = [&](bool here, size_t bytes) { const size_t was = at; if (here) at += (bytes + 255) & ~(size_t)255; return was; };
+    const size_t at_label = take(!p.label, n_vox * sizeof(int32_t)), at_work = take(true, n_vox * sizeof(int32_t));
+    const size_t at_roots = take(true, n_words * sizeof(uint32_t)), at_keep = take(true, n_words * sizeof(uint32_t));
+    const size_t at_root_tiles = take(true, tiles * sizeof(int32_t)), at_keep_tiles = take(true, tiles * sizeof(int32_t));
+    if ((rc = pub_reserve(h, 64, 0))) return rc;
+    if ((rc = plane_scratch_grow(h, h->components, at))) return rc;
+    if ((rc = pub_order_dst(h))) return rc;
+    uint8_t *sc = h->components.as<uint8_t>();
+    int32_t *d_kept = pub_words(h, 0).cells_total, *d_all = d_kept + 1;
+    const hipError_t e = launch_components((const uint32_t *)src_device, tag_src_device, nx, ny, nz, connectivity, min_count,
+                                           p.label ? p.label : (int32_t *)(sc + at_label), (int32_t *)(sc + at_work), (uint32_t *)(sc + at_roots),
+                                           (uint32_t *)(sc + at_keep), (int32_t *)(sc + at_root_tiles), (int32_t *)(sc + at_keep_tiles), p.table, (int)cap,
+                                           d_all, d_kept, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "components launch: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[10], d_kept, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const int32_t kept = h->h_scalars[10];
+    *n_components = kept;
+    if (n_all) *n_all = h->h_scalars[11];
+    if (p.table && kept > p.table_cap) return fail(h, DSM_E_CAPACITY, "%d components, room for %d", kept, p.table_cap);
     return DSM_OK;
 }
 

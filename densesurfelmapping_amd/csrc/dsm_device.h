@@ -288,6 +288,14 @@ hipError_t launch_carve(const float *depth_base, const CarveFrame *frames, int n
 hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, int nx, int ny, int nz, uint8_t *state, uint32_t *known_free, uint32_t *frontier,
                         int32_t *cells, int cells_cap, int32_t *cell_tiles, int32_t *cells_total, hipStream_t st);
 
+// ---- connected components of a bit set (dsm_k_components.h; the definition is in dsm_components.h)
+// src: [nz][ny][wx] words, pad bits ignored; at most kFieldMaxVoxels voxels.  label: [voxels], always written (the caller's plane or
+// scratch); work: [voxels] of scratch; root_bits / keep_bits: [words]; root_tiles / keep_tiles: (words + 255) / 256 ints each.  table
+// may be null: no statistics; no entry is written at or beyond cap.  *n_all = the components, *n_kept = those with count >= min_count.
+hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, int nx, int ny, int nz, int connectivity, int min_count, int32_t *label,
+                             int32_t *work, uint32_t *root_bits, uint32_t *keep_bits, int32_t *root_tiles, int32_t *keep_tiles, dsm_component *table,
+                             int cap, int32_t *n_all, int32_t *n_kept, hipStream_t st);
+
 // ---- a depth frame against the rendered map (dsm_k_align.h; the definition is align_pixel of dsm_align.h)
 // One evaluation: clears sums[29] on `st`, then adds the fixed-point terms of every sampled pixel of the frame plane `depth`
 // ([h][pitch]) that passes align_pixel against the model planes zm [mh][mw] and nm [mh][mw][3].  c from align_prepare, with T set.

@@ -5,6 +5,7 @@
 // installs them.  The per-fuse carve is the SYNCHRONISING dsm_grid_carve: it is enqueued behind the fuse on the engine's stream and
 // has returned before the slot's next upload is issued.  The set is cleared and copied on the null stream; dsm_grid_carve orders
 // itself behind that stream (a caller's device memory), so a clear cannot overtake or be overtaken by a carve.
+#include "dsm_components.h"
 #include "dsm_surfel_map_node.h"
 
 #include <hip/hip_runtime_api.h>
@@ -117,23 +118,42 @@ Space *ready(dsm_surfel_map *m, int *rc) {
     return (Space *)m->space;
 }
 
+// the occupied set of `kind` in the accumulator's spec into s->d_occ (allocated at the first call): what dsm_surfel_map_space and
+// dsm_surfel_map_frontier_clusters classify against the accumulated free set
+int compose_occupied(dsm_surfel_map *m, Space *s, int kind, const char *what, int32_t *n_surfels) {
+    int select = DSM_CLOUD_SELECT_NONE;
+    std::vector<int32_t> begin, count;
+    if (!render_runs(m, kind, select, begin, count)) return space_fail(m, DSM_E_INVALID, "%s kind %d", what, kind);
+    SPACE_HIP(m, hipSetDevice(m->cfg.device));
+    if (!s->d_occ) SPACE_HIP(m, hipMalloc((void **)&s->d_occ, s->n_words * sizeof(uint32_t)));
+    const dsm_grid_planes occupied = {s->d_occ, nullptr, nullptr, nullptr, 0};
+    int32_t n = 0, cells = 0;
+    const int rc = dsm_grid_compose(m->engine, select, (int32_t)begin.size(), begin.data(), count.data(), &s->spec, 0, &occupied, 1, &n, &cells);
+    if (rc) return space_fail(m, rc, "dsm_grid_compose: %s", dsm_last_error(m->engine));
+    if (n_surfels) *n_surfels = n;
+    return DSM_OK;
+}
+
+// room for `bytes` of device staging in s->d_tmp (grow-only; growth drops the contents)
+int tmp_reserve(dsm_surfel_map *m, Space *s, size_t bytes) {
+    if (bytes <= s->tmp_bytes) return DSM_OK;
+    if (s->d_tmp) (void)hipFree(s->d_tmp);
+    s->d_tmp = nullptr;
+    s->tmp_bytes = 0;
+    SPACE_HIP(m, hipMalloc((void **)&s->d_tmp, bytes));
+    s->tmp_bytes = bytes;
+    return DSM_OK;
+}
+
 int space(dsm_surfel_map *m, int kind, const dsm_space_planes *planes, int on_device, int32_t *n_surfels, int32_t *n_frontier) {
     if (!m || !planes) return DSM_E_INVALID;
     int rc = DSM_OK;
     Space *s = ready(m, &rc);
     if (!s) return rc;
-    int select = DSM_CLOUD_SELECT_NONE;
-    std::vector<int32_t> begin, count;
-    if (!render_runs(m, kind, select, begin, count)) return space_fail(m, DSM_E_INVALID, "space kind %d", kind);
     if (!planes->state && !planes->known_free && !planes->frontier && !planes->cells) return space_fail(m, DSM_E_INVALID, "no output plane");
     if (planes->cells && planes->cells_cap < 0) return space_fail(m, DSM_E_INVALID, "cells_cap %d", planes->cells_cap);
-    SPACE_HIP(m, hipSetDevice(m->cfg.device));
-    if (!s->d_occ) SPACE_HIP(m, hipMalloc((void **)&s->d_occ, s->n_words * sizeof(uint32_t)));
-    const dsm_grid_planes occupied = {s->d_occ, nullptr, nullptr, nullptr, 0};
-    int32_t n = 0, cells = 0, nf = 0;
-    rc = dsm_grid_compose(m->engine, select, (int32_t)begin.size(), begin.data(), count.data(), &s->spec, 0, &occupied, 1, &n, &cells);
-    if (rc) return space_fail(m, rc, "dsm_grid_compose: %s", dsm_last_error(m->engine));
-    if (n_surfels) *n_surfels = n;
+    if ((rc = compose_occupied(m, s, kind, "space", n_surfels))) return rc;
+    int32_t nf = 0;
     const int nx = s->spec.nx, ny = s->spec.ny, nz = s->spec.nz;
     if (on_device) {
         rc = dsm_grid_classify(m->engine, nx, ny, nz, s->d_occ, s->d_free, planes, &nf);
@@ -148,13 +168,7 @@ int space(dsm_surfel_map *m, int kind, const dsm_space_planes *planes, int on_de
     const size_t at_kf = take(planes->known_free != nullptr, s->n_words * sizeof(uint32_t));
     const size_t at_fr = take(planes->frontier != nullptr, s->n_words * sizeof(uint32_t));
     const size_t at_cells = take(planes->cells != nullptr, (cap ? cap : 1) * sizeof(int32_t));
-    if (at > s->tmp_bytes) {
-        if (s->d_tmp) (void)hipFree(s->d_tmp);
-        s->d_tmp = nullptr;
-        s->tmp_bytes = 0;
-        SPACE_HIP(m, hipMalloc((void **)&s->d_tmp, at));
-        s->tmp_bytes = at;
-    }
+    if ((rc = tmp_reserve(m, s, at))) return rc;
     dsm_space_planes dev = {nullptr, nullptr, nullptr, nullptr, 0};
     if (planes->state) dev.state = s->d_tmp + at_state;
     if (planes->known_free) dev.known_free = (uint32_t *)(s->d_tmp + at_kf);
@@ -169,6 +183,71 @@ int space(dsm_surfel_map *m, int kind, const dsm_space_planes *planes, int on_de
     const size_t n_out = (size_t)nf < cap ? (size_t)nf : cap;
     if (planes->cells && n_out) SPACE_HIP(m, hipMemcpy(planes->cells, dev.cells, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (planes->cells && nf > planes->cells_cap) return space_fail(m, DSM_E_CAPACITY, "%d frontier cells, room for %d", nf, planes->cells_cap);
+    return DSM_OK;
+}
+
+// dsm_surfel_map_frontier_clusters: classify as space() does, then label the frontier (and, for reachability, the known-free set)
+int frontier_clusters(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, dsm_component *table, int32_t table_cap, int32_t *label, int on_device,
+                      int32_t *n_clusters, int32_t *n_all, int32_t *from_root) {
+    if (!m || !q || !n_clusters) return DSM_E_INVALID;
+    int rc = DSM_OK;
+    Space *s = ready(m, &rc);
+    if (!s) return rc;
+    if (q->struct_size != sizeof(dsm_frontier_query)) return space_fail(m, DSM_E_INVALID, "dsm_frontier_query struct_size %u, not %zu", q->struct_size, sizeof(dsm_frontier_query));
+    if (q->connectivity != DSM_CONNECT_FACES && q->connectivity != DSM_CONNECT_ALL) return space_fail(m, DSM_E_INVALID, "frontier clusters: connectivity %d", q->connectivity);
+    if (q->min_count < 1) return space_fail(m, DSM_E_INVALID, "frontier clusters: min_count %d", q->min_count);
+    if (!table && !label) return space_fail(m, DSM_E_INVALID, "frontier clusters: no output");
+    if (table && table_cap < 0) return space_fail(m, DSM_E_INVALID, "table_cap %d", table_cap);
+    if (s->n_vox > ((size_t)1 << 26)) return space_fail(m, DSM_E_INVALID, "frontier clusters: more than 2^26 voxels");
+    if ((rc = compose_occupied(m, s, kind, "frontier clusters", nullptr))) return rc;
+    const int nx = s->spec.nx, ny = s->spec.ny, nz = s->spec.nz;
+    const bool from = q->has_from != 0;
+    const size_t cap = table ? ((size_t)table_cap < s->n_vox ? (size_t)table_cap : s->n_vox) : 0;
+    // device staging, each part from a 256-byte boundary: the frontier, then for reachability the known-free set and its labels, then
+    // what goes to host memory
+    size_t at = 0;
+    const auto take = [&](bool here, size_t bytes) { const size_t was = at; if (here) at += (bytes + 255) & ~(size_t)255; return was; };
+    const size_t at_fr = take(true, s->n_words * sizeof(uint32_t));
+    const size_t at_kf = take(from, s->n_words * sizeof(uint32_t));
+    const size_t at_region = take(from, s->n_vox * sizeof(int32_t));
+    const size_t at_table = take(table && !on_device, (cap ? cap : 1) * sizeof(dsm_component));
+    const size_t at_label = take(label && !on_device, s->n_vox * sizeof(int32_t));
+    if ((rc = tmp_reserve(m, s, at))) return rc;
+    uint32_t *frontier = (uint32_t *)(s->d_tmp + at_fr), *known_free = from ? (uint32_t *)(s->d_tmp + at_kf) : nullptr;
+    int32_t *region = from ? (int32_t *)(s->d_tmp + at_region) : nullptr;
+    const dsm_space_planes sp = {nullptr, known_free, frontier, nullptr, 0};
+    int32_t nf = 0;
+    rc = dsm_grid_classify(m->engine, nx, ny, nz, s->d_occ, s->d_free, &sp, &nf);
+    if (rc) return space_fail(m, rc, "dsm_grid_classify: %s", dsm_last_error(m->engine));
+    int32_t root = -1;
+    if (from) {
+        const dsm_component_planes rp = {region, nullptr, 0};
+        int32_t n_regions = 0;
+        rc = dsm_grid_components(m->engine, nx, ny, nz, DSM_CONNECT_FACES, 1, known_free, nullptr, &rp, &n_regions, nullptr);
+        if (rc) return space_fail(m, rc, "dsm_grid_components: %s", dsm_last_error(m->engine));
+        const int32_t i[3] = {dsm::comp_from_voxel(q->from[0], s->spec.origin[0], s->spec.voxel), dsm::comp_from_voxel(q->from[1], s->spec.origin[1], s->spec.voxel),
+                              dsm::comp_from_voxel(q->from[2], s->spec.origin[2], s->spec.voxel)};
+        if (i[0] >= 0 && i[0] < nx && i[1] >= 0 && i[1] < ny && i[2] >= 0 && i[2] < nz)
+            SPACE_HIP(m, hipMemcpy(&root, region + ((size_t)i[2] * ny + i[1]) * nx + i[0], sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    dsm_component_planes cp = {label, table, table_cap};
+    if (!on_device) {
+        cp.label = label ? (int32_t *)(s->d_tmp + at_label) : nullptr;
+        cp.table = table ? (dsm_component *)(s->d_tmp + at_table) : nullptr;
+        cp.table_cap = (int32_t)cap;
+    }
+    int32_t n = 0, all = 0;
+    rc = dsm_grid_components(m->engine, nx, ny, nz, q->connectivity, q->min_count, frontier, region, &cp, &n, &all);
+    *n_clusters = n;
+    if (n_all) *n_all = all;
+    if (from_root) *from_root = root;
+    if (rc && rc != DSM_E_CAPACITY) return space_fail(m, rc, "dsm_grid_components: %s", dsm_last_error(m->engine));
+    if (!on_device) {
+        const size_t n_out = (size_t)n < cap ? (size_t)n : cap;
+        if (table && n_out) SPACE_HIP(m, hipMemcpy(table, cp.table, n_out * sizeof(dsm_component), hipMemcpyDeviceToHost));
+        if (label) SPACE_HIP(m, hipMemcpy(label, cp.label, s->n_vox * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (table && n > table_cap) return space_fail(m, DSM_E_CAPACITY, "%d frontier clusters, room for %d", n, table_cap);
     return DSM_OK;
 }
 
@@ -230,6 +309,24 @@ int dsm_surfel_map_space(dsm_surfel_map *m, int kind, const dsm_space_planes *pl
 
 int dsm_surfel_map_space_device(dsm_surfel_map *m, int kind, const dsm_space_planes *planes_device, int32_t *n_surfels, int32_t *n_frontier) {
     return space(m, kind, planes_device, 1, n_surfels, n_frontier);
+}
+
+void dsm_frontier_query_init(dsm_frontier_query *q) {
+    if (!q) return;
+    memset(q, 0, sizeof *q);
+    q->struct_size = (uint32_t)sizeof(dsm_frontier_query);
+    q->connectivity = DSM_CONNECT_ALL;
+    q->min_count = 1;
+}
+
+int dsm_surfel_map_frontier_clusters(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, dsm_component *table, int32_t table_cap, int32_t *label,
+                                     int32_t *n_clusters, int32_t *n_all, int32_t *from_root) {
+    return frontier_clusters(m, kind, q, table, table_cap, label, 0, n_clusters, n_all, from_root);
+}
+
+int dsm_surfel_map_frontier_clusters_device(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, dsm_component *table_device, int32_t table_cap,
+                                            int32_t *label_device, int32_t *n_clusters, int32_t *n_all, int32_t *from_root) {
+    return frontier_clusters(m, kind, q, table_device, table_cap, label_device, 1, n_clusters, n_all, from_root);
 }
 
 int dsm_surfel_map_carve_last(dsm_surfel_map *m, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags, void *free_device) {

@@ -26,6 +26,10 @@ metres around the FIRST pose of the log (--carve-near N, --carve-far F, --carve-
 origin, voxel, dims, near, far, margin, state [nz][ny][nx] (0 unknown, 1 free, 2 occupied), frontier_cells, free, n_free and resets
 (how often a loop closure cleared the set: after one it holds only the frames fused since).
 
+--save-frontier-clusters PATH.npz uses the same accumulator (the same --grid-* and --carve-* options) and writes the frontier as
+connected clusters (--cluster-connect 6|26, --cluster-min N voxels): origin, voxel, dims, the table (root, count, sum, lo, hi, tag),
+n_all and from_root, with `from` at the pose of the last fuse: a cluster with tag == from_root can be reached through known-free space.
+
 --eigen-products 3.3 fuses with the 3x3 products in the order of a reference built against Eigen >= 3.3
 (DSM_FLAG_EIGEN33_PRODUCTS); the default, 3.2, is the order of Eigen 3.2, as without the flag.
 """
@@ -100,19 +104,21 @@ EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-pro
 
 def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None, align=None,
            save_grid=None, grid_voxel=0.1, grid_dims=(64, 64, 32), grid_inflate=0, save_field=None, field_max_dist=16,
-           save_space=None, carve_near=None, carve_far=None, carve_margin=None):
+           save_space=None, carve_near=None, carve_far=None, carve_margin=None, save_frontier_clusters=None, cluster_min=1, cluster_connect=26):
     """Feed a log to a SurfelMap on the GPU; returns a summary dict.  align = a cloud kind: after every fused frame that frame is
     aligned against the surfels of that kind at the pose it was fused with (SurfelMap.align_last, the library's defaults) and a
     JSON line says how it went; the poses fed to the map are not changed.  save_grid: the whole map as an occupancy grid of grid_dims voxels
     of grid_voxel metres around the final fuse pose (SurfelMap.grid), as an .npz.  save_field: the distance field of that grid's occupied
     set out to field_max_dist voxels (SurfelMap.field), as an .npz.  save_space: the free-space accumulator is switched on before the
     replay, in a grid of grid_dims voxels around the first pose of the log, and the three-state map and its frontier are written as an
-    .npz (SurfelMap.set_free_space / space)."""
+    .npz (SurfelMap.set_free_space / space).  save_frontier_clusters: with the same accumulator, the frontier as clusters of
+    cluster_connect-connectivity with at least cluster_min voxels, and whether each can be reached through known-free space from the
+    pose of the last fuse (SurfelMap.frontier_clusters), as an .npz."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
     node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity,
                                 engine_flags=EIGEN_PRODUCTS[eigen_products])
-    if save_space:  # (the node turns the SLAM frame so that the first camera sits at the world's origin: the grid lies around it)
+    if save_space or save_frontier_clusters:  # (the node turns the SLAM frame so that the first camera sits at the world's origin: the grid lies around it)
         carve = {k: v for k, v in (("near_dist", carve_near), ("far_dist", carve_far), ("margin", carve_margin)) if v is not None}
         node.set_free_space(api.grid_spec_around((0.0, 0.0, 0.0), grid_voxel, tuple(grid_dims)), carve)
     n = 0
@@ -158,6 +164,15 @@ def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, e
                  near=np.float32(p.near_dist), far=np.float32(p.far_dist), margin=np.float32(p.margin), state=sp["state"], frontier_cells=sp["cells"],
                  free=free, n_free=np.int64(n_free), resets=np.int64(node.free_space_resets))
         out["free_voxels"], out["frontier_cells"], out["free_space_resets"] = int(n_free), int(sp["n_frontier"]), node.free_space_resets
+    if save_frontier_clusters:  # the frontier as clusters, reachability from the pose of the last fuse
+        origin = node.last_pose()[:3, 3]
+        fc = node.frontier_clusters("all", connectivity=cluster_connect, min_count=cluster_min, origin=origin)
+        g = fc["spec"]
+        np.savez(save_frontier_clusters, origin=np.array(g.origin[:], np.float32), voxel=np.float32(g.voxel), dims=np.array([g.nx, g.ny, g.nz], np.int32),
+                 connectivity=np.int32(cluster_connect), min_count=np.int32(cluster_min), table=fc["table"], from_root=np.int32(fc["from_root"]),
+                 n_all=np.int32(fc["n_all"]), origin_point=np.asarray(origin, np.float32))
+        out["frontier_clusters"], out["frontier_clusters_all"] = int(len(fc["table"])), int(fc["n_all"])
+        out["frontier_clusters_reachable"] = int((fc["table"]["tag"] == fc["from_root"]).sum()) if fc["from_root"] >= 0 else 0
     node.close()
     return out
 
@@ -185,6 +200,10 @@ def main():
     ap.add_argument("--carve-far", type=float, default=None, metavar="F", help="farthest depth carved, metres (default: the library's, 10)")
     ap.add_argument("--carve-margin", type=float, default=None, metavar="M", help="clearance kept in front of the measured surface, metres "
                     "(default: the library's, one voxel diagonal of a 0.1 m grid)")
+    ap.add_argument("--save-frontier-clusters", metavar="PATH.npz", help="with the accumulator of --save-space (the same --grid-* and --carve-* options): the "
+                    "frontier as connected clusters: origin, voxel, dims, table (root, count, sum, lo, hi, tag), from_root, n_all; from = the pose of the last fuse")
+    ap.add_argument("--cluster-min", type=int, default=1, metavar="N", help="clusters of fewer voxels are left out (default 1)")
+    ap.add_argument("--cluster-connect", type=int, default=26, choices=(6, 26), help="connectivity of the clusters (default 26)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
                     help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
@@ -197,7 +216,8 @@ def main():
                             save_mesh_binary=args.save_mesh_binary, render=args.render, align=args.align,
                             save_grid=args.save_grid, grid_voxel=args.grid_voxel, grid_dims=args.grid_dims, grid_inflate=args.grid_inflate,
                             save_field=args.save_field, field_max_dist=args.field_max_dist,
-                            save_space=args.save_space, carve_near=args.carve_near, carve_far=args.carve_far, carve_margin=args.carve_margin)))
+                            save_space=args.save_space, carve_near=args.carve_near, carve_far=args.carve_far, carve_margin=args.carve_margin,
+                            save_frontier_clusters=args.save_frontier_clusters, cluster_min=args.cluster_min, cluster_connect=args.cluster_connect)))
 
 
 if __name__ == "__main__":

@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_field", "dsm_surfel_map_field_device",
     "dsm_surfel_map_set_free_space", "dsm_surfel_map_free_space_resets", "dsm_surfel_map_free_space", "dsm_surfel_map_free_space_device",
     "dsm_surfel_map_space", "dsm_surfel_map_space_device", "dsm_surfel_map_carve_last",
+    "dsm_frontier_query_init", "dsm_surfel_map_frontier_clusters", "dsm_surfel_map_frontier_clusters_device",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -36,6 +37,10 @@ CLOUD_ACTIVE, CLOUD_INACTIVE, CLOUD_ALL, CLOUD_NEIGHBOR, CLOUD_RAW = range(5)
 CLOUD_KINDS = ("active", "inactive", "all", "neighbor", "raw")
 
 _vp = C.c_void_p
+
+
+class _FrontierQuery(C.Structure):  # dsm_frontier_query
+    _fields_ = [("struct_size", C.c_uint32), ("connectivity", C.c_int32), ("min_count", C.c_int32), ("has_from", C.c_int32), ("from_", C.c_float * 3)]
 
 
 class _Stamp(C.Structure):
@@ -121,6 +126,11 @@ def _bind(lib):
             for name in ("dsm_surfel_map_space", "dsm_surfel_map_space_device"):
                 getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._SpacePlanes), _vp, _vp]
             lib.dsm_surfel_map_carve_last.argtypes = [_vp, C.POINTER(api._GridSpec), C.POINTER(api._CarveParams), C.c_uint32, _vp]
+        if hasattr(lib, "dsm_surfel_map_frontier_clusters"):  # (nor frontier clusters)
+            lib.dsm_frontier_query_init.argtypes = [C.POINTER(_FrontierQuery)]
+            lib.dsm_frontier_query_init.restype = None
+            for name in ("dsm_surfel_map_frontier_clusters", "dsm_surfel_map_frontier_clusters_device"):
+                getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(_FrontierQuery), _vp, C.c_int32, _vp, _vp, _vp, _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -369,6 +379,57 @@ class SurfelMap:
         if "cells" in out:
             out["cells"] = out["cells"][: nf.value]
         out["n_surfels"], out["n_frontier"], out["spec"] = n.value, nf.value, spec
+        return out
+
+    def frontier_clusters(self, kind="all", connectivity=26, min_count=1, origin=None, labels=False, dst_ptrs=None, table_cap=None):
+        """The frontier of space(kind) as connected clusters (connectivity 6 or 26) of at least min_count voxels.  origin: a world
+        point (x, y, z), e.g. the translation of the last pose; with it every cluster's "tag" is the root of the known-free region
+        (6-connected) that holds the cluster's root voxel, and "from_root" that of the region holding `origin` (-1: outside the grid or
+        not known free): a cluster is reachable through known-free space iff tag == from_root.  Returns a dict: "table"
+        (api.COMPONENT_DTYPE, ascending by root), "n_all" (the clusters before the filter), "from_root", "spec", and "labels" (int32
+        [nz, ny, nx]: the root of each frontier voxel's cluster, -1 elsewhere) when asked for.  table_cap None: the table is sized by a
+        second call.  With dst_ptrs = {"table": device pointer, "label": device pointer} (either may be missing) and table_cap:
+        (n_clusters, n_all, from_root).  More clusters than table_cap: DsmError with code DSM_E_CAPACITY and .n_clusters."""
+        k = self._kind(kind)
+        spec = getattr(self, "_space_spec", None)
+        q = _FrontierQuery()
+        self._lib.dsm_frontier_query_init(C.byref(q))
+        q.connectivity, q.min_count = int(connectivity), int(min_count)
+        if origin is not None:
+            q.has_from = 1
+            q.from_[:] = [float(v) for v in np.asarray(origin, np.float32).reshape(3)]
+        n, n_all, root = C.c_int32(0), C.c_int32(0), C.c_int32(-1)
+        if dst_ptrs is not None:
+            t, l = dst_ptrs.get("table"), dst_ptrs.get("label")
+            rc = self._lib.dsm_surfel_map_frontier_clusters_device(self._h, k, C.byref(q), _vp(t) if t else None, int(table_cap or 0), _vp(l) if l else None,
+                                                                   C.byref(n), C.byref(n_all), C.byref(root))
+            if rc == api.DSM_E_CAPACITY:
+                e = api.DsmError(rc, self._lib.dsm_surfel_map_last_error(self._h).decode())
+                e.n_clusters, e.n_all, e.from_root = n.value, n_all.value, root.value
+                raise e
+            self._check(rc)
+            return n.value, n_all.value, root.value
+        auto = table_cap is None
+        lab = np.zeros(api.grid_shapes(spec)[2], np.int32) if labels and spec is not None else None
+        table = np.zeros(max(1, 1024 if auto else int(table_cap)), api.COMPONENT_DTYPE)
+        cap = 1024 if auto else int(table_cap)
+
+        def call():
+            return self._lib.dsm_surfel_map_frontier_clusters(self._h, k, C.byref(q), _ptr(table), cap, None if lab is None else _ptr(lab), C.byref(n),
+                                                              C.byref(n_all), C.byref(root))
+        rc = call()
+        if rc == api.DSM_E_CAPACITY and auto:
+            cap = n.value
+            table = np.zeros(cap, api.COMPONENT_DTYPE)
+            rc = call()
+        if rc == api.DSM_E_CAPACITY:
+            e = api.DsmError(rc, self._lib.dsm_surfel_map_last_error(self._h).decode())
+            e.n_clusters, e.n_all, e.from_root, e.table = n.value, n_all.value, root.value, table[:cap]
+            raise e
+        self._check(rc)
+        out = {"table": table[: n.value].copy(), "n_all": n_all.value, "from_root": root.value, "spec": spec}
+        if labels:
+            out["labels"] = lab
         return out
 
     def carve_last(self, spec, free_ptr, params=None, flags=0):

@@ -466,6 +466,42 @@ typedef struct dsm_space_planes {
 int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const void *occupied_device, const void *free_device,
                       const dsm_space_planes *planes_device, int32_t *n_frontier);
 
+/* ---- connected components of a bit set: frontier clusters, obstacles as objects, the pocket of free space a robot sits in ----
+ * Input: a bit set S in the grid layout ([nz][ny][wx] words, pad bits ignored) and a connectivity.  Two set voxels are ADJACENT
+ * when both lie inside the grid and their offset (dx, dy, dz) is not zero with |dx| + |dy| + |dz| == 1 (DSM_CONNECT_FACES) or
+ * max(|dx|, |dy|, |dz|) == 1 (DSM_CONNECT_ALL).  A component is a class of the transitive closure of adjacency; nothing outside the
+ * grid connects anything.  A component is NAMED by the lowest linear index lin = (z ny + y) nx + x of its voxels, its root.  Every
+ * output is an integer minimum, maximum, sum or count over a set: the result does not depend on how the GPU arranges the work and
+ * is reproducible bit for bit.
+ * Not provided: clusters tracked from one call to the next, viewpoints or goal poses, 18-connectivity, a component's voxel list. */
+#define DSM_CONNECT_FACES 6
+#define DSM_CONNECT_ALL 26
+typedef struct dsm_component { /* 64 bytes */
+    int32_t root;         /* the lowest linear index of the component */
+    int32_t count;        /* its voxels */
+    int64_t sum[3];       /* the sums of the x, y, z voxel indices: centroid_a = origin_a + (sum_a / count + 0.5) voxel, the caller's division */
+    int32_t lo[3], hi[3]; /* the inclusive bounding box in voxel indices */
+    int32_t tag;          /* tag_src[root] when a tag plane is given, else 0 */
+    int32_t reserved;     /* 0 */
+} dsm_component;
+/* device memory; either may be NULL (not written), not both; label 4-byte and table 8-byte aligned */
+typedef struct dsm_component_planes {
+    int32_t *label;       /* [nz][ny][nx]  the root of the voxel's component; -1 for a voxel not in S.  Never filtered. */
+    dsm_component *table; /* [table_cap]   the components with count >= min_count, ascending by root */
+    int32_t table_cap;    /* >= 0 when table is not NULL */
+} dsm_component_planes;
+/* The components of a bit set in DEVICE memory.  tag_src_device: an int32 [nz][ny][nx] plane in device memory or NULL.
+ * *n_components = the components with count >= min_count, *n_all (may be NULL) = all of them, whichever planes are asked for.
+ * More than table_cap pass the filter: DSM_E_CAPACITY with *n_components = the count needed; `label` is complete, the first
+ * table_cap entries are complete, and nothing is written past the cap.  The intermediates cost up to 8 bytes a voxel of grow-only
+ * handle scratch, hence the limit of 2^26 voxels.  DSM_E_INVALID before any device work, nothing written: a NULL handle, source,
+ * planes or n_components; a dimension < 1; more than 2^26 voxels; a connectivity other than 6 or 26; min_count < 1; both outputs
+ * NULL; table with table_cap < 0; the two outputs the same pointer; an output overlapping the source or the tag plane; the
+ * source, the tag plane or `label` not 4-byte aligned, `table` not 8-byte aligned.  Ordered and synchronised like dsm_grid_inflate.
+ * Synchronises. */
+int dsm_grid_components(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t connectivity, int32_t min_count, const void *src_device,
+                        const int32_t *tag_src_device, const dsm_component_planes *planes_device, int32_t *n_components, int32_t *n_all);
+
 /* ---- a depth frame against the map: projective association and point-to-plane alignment (no counterpart in the reference) ----
  * What dsm_render_compose predicts for a camera (the MODEL camera: depth plane Zm, camera-frame normal plane Nm) is compared with
  * the depth plane of a frame slot, whichever upload wrote it.  T is a rigid transform from the frame camera to the model camera,

@@ -222,6 +222,37 @@ int dsm_surfel_map_space_device(dsm_surfel_map *m, int kind, const dsm_space_pla
  * fused with, into the caller's set in device memory.  params NULL: the defaults.  DSM_E_STATE before the first fuse. */
 int dsm_surfel_map_carve_last(dsm_surfel_map *m, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags, void *free_device);
 
+/* ---- frontier clusters: the frontier of dsm_surfel_map_space as connected components (dsm_grid_components of dsm.h) ----
+ * The occupied set of `kind` in the accumulator's grid is classified against the accumulated free set exactly as
+ * dsm_surfel_map_space does it, and the frontier is labelled with q->connectivity; clusters of fewer than q->min_count voxels are
+ * left out of the table (never out of `label`).  With q->has_from the known-free set is labelled as well, with DSM_CONNECT_FACES,
+ * and a cluster's `tag` is the root of the known-free region that holds the cluster's ROOT voxel (never -1: a frontier voxel is
+ * known free).  With 6-connected clusters the whole cluster lies in that region; with 26 it is the region of the root voxel only.
+ * *from_root = the known-free root at the voxel of q->from, i_a = (int)floor(((double)from_a - (double)origin_a) / (double)voxel),
+ * or -1 when that voxel is outside the grid or not known free.  A cluster can be reached from `from` through known-free space iff
+ * tag == *from_root.  Without has_from: tag 0, *from_root -1.
+ * table: [table_cap] entries, label: [nz][ny][nx] (may be NULL), in host memory; *n_clusters = the clusters that pass min_count
+ * (more than table_cap: DSM_E_CAPACITY with the count needed, the first table_cap entries and `label` complete), *n_all (may be
+ * NULL) = all of them.  DSM_E_STATE before dsm_surfel_map_set_free_space or before the first fuse; DSM_E_INVALID for a wrong
+ * struct_size, a kind dsm_surfel_map_space refuses, and what dsm_grid_components refuses (more than 2^26 voxels among it).  The map
+ * and the accumulator are not changed.  Synchronises.
+ * Not provided: clusters tracked across calls, viewpoints or goal poses, and labelling across a loop-closure reset (the
+ * accumulator starts again there, and so do the clusters). */
+typedef struct dsm_frontier_query {
+    uint32_t struct_size; /* sizeof(dsm_frontier_query) */
+    int32_t connectivity; /* of the frontier clusters: DSM_CONNECT_FACES or DSM_CONNECT_ALL */
+    int32_t min_count;    /* >= 1 */
+    int32_t has_from;     /* 0: no reachability */
+    float from[3];        /* a world point, e.g. the translation of dsm_surfel_map_last_pose16 */
+} dsm_frontier_query;
+/* DSM_CONNECT_ALL, min_count 1, no from */
+void dsm_frontier_query_init(dsm_frontier_query *q);
+int dsm_surfel_map_frontier_clusters(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, dsm_component *table, int32_t table_cap, int32_t *label,
+                                     int32_t *n_clusters, int32_t *n_all, int32_t *from_root);
+/* the same with table (8-byte aligned) and label (4-byte aligned) in device memory of the node's GPU */
+int dsm_surfel_map_frontier_clusters_device(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, dsm_component *table_device, int32_t table_cap,
+                                            int32_t *label_device, int32_t *n_clusters, int32_t *n_all, int32_t *from_root);
+
 /* ---- the latest frame against the map (dsm_align_frame of dsm.h, where the alignment is defined) ----
  * Aligns the depth frame of the latest fuse, still in its engine slot, against the surfel set of `kind` with the rules and runs of
  * dsm_surfel_map_render (ACTIVE: refine or judge a pose; INACTIVE: verify a loop closure against the inactive map), seen by the

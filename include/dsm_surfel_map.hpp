@@ -310,6 +310,15 @@ class SurfelMap {
     int space_device(dsm_cloud_kind kind, const dsm_space_planes &planes_device, int32_t *n_surfels = nullptr, int32_t *n_frontier = nullptr) {
         return check(dsm_surfel_map_space_device(m_, kind, &planes_device, n_surfels, n_frontier));
     }
+    // the frontier of space(kind) as connected clusters (dsm_frontier_query_init gives the query's defaults); table and label in host memory
+    int frontier_clusters(dsm_cloud_kind kind, const dsm_frontier_query &query, dsm_component *table, int32_t table_cap, int32_t *label,
+                          int32_t *n_clusters, int32_t *n_all = nullptr, int32_t *from_root = nullptr) {
+        return check(dsm_surfel_map_frontier_clusters(m_, kind, &query, table, table_cap, label, n_clusters, n_all, from_root));
+    }
+    int frontier_clusters_device(dsm_cloud_kind kind, const dsm_frontier_query &query, dsm_component *table_device, int32_t table_cap, int32_t *label_device,
+                                 int32_t *n_clusters, int32_t *n_all = nullptr, int32_t *from_root = nullptr) {
+        return check(dsm_surfel_map_frontier_clusters_device(m_, kind, &query, table_device, table_cap, label_device, n_clusters, n_all, from_root));
+    }
     // one carve of the latest fused frame into a caller's set in device memory: the stateless counterpart
     int carve_last(const dsm_grid_spec &spec, const dsm_carve_params *params, uint32_t flags, void *free_device) {
         return check(dsm_surfel_map_carve_last(m_, &spec, params, flags, free_device));
