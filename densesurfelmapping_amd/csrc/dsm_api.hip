@@ -1885,7 +1885,7 @@ PubWords pub_words(const dsm_handle *h, size_t tiles) {
 struct MapSequence {
     std::vector<int32_t> seg;
     int64_t runs_total = 0, bound = 0;
-    int n_upper = 0;
+    int n_upper = 0, select = kCloudNone;
     size_t tiles() const { return ((size_t)n_upper + kCloudTile - 1) / kCloudTile; }
 };
 
@@ -1903,6 +1903,7 @@ int check_sequence(dsm_handle *h, int select, int32_t n_segments, const int32_t 
         sq.seg.push_back((int32_t)sq.runs_total);
         sq.runs_total += cnt;
     }
+    sq.select = select;
     sq.n_upper = select == kCloudNone ? 0 : h->map_upper;
     sq.bound = (int64_t)sq.n_upper + sq.runs_total;
     if (sq.bound > max_len) return fail(h, DSM_E_INVALID, "%lld surfels in the runs and the map", (long long)sq.bound);
@@ -1920,11 +1921,27 @@ int pose_finite(dsm_handle *h, const float *pose16, const float *pose_inv16) {
     return DSM_OK;
 }
 
-// the words of a sequence's product, with its run table on its way up; `points`: as pub_reserve
-int pub_sequence(dsm_handle *h, const MapSequence &sq, size_t points, PubWords &w) {
+// the words of a sequence's product and the sequence as the launches take it (dsm_device.h), with its run table on its way up;
+// `points`: as pub_reserve
+struct PubSequence {
+    PubWords w;
+    RunTable rt;
+    MapPart mp;
+};
+int pub_sequence(dsm_handle *h, const MapSequence &sq, size_t points, PubSequence &ps) {
     if (int rc = pub_reserve(h, 64 + sq.tiles() + sq.seg.size(), points)) return rc;
-    w = pub_words(h, sq.tiles());
-    if (!sq.seg.empty()) HIP_TRY(h, hipMemcpyAsync(w.seg, sq.seg.data(), sq.seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    ps.w = pub_words(h, sq.tiles());
+    ps.rt = {ps.w.seg, (int)(sq.seg.size() / 3), (int)sq.runs_total};
+    ps.mp = {h->hc.local, h->hc.n_local, sq.n_upper, sq.select, ps.w.tiles, ps.w.total};
+    if (!sq.seg.empty()) HIP_TRY(h, hipMemcpyAsync(ps.w.seg, sq.seg.data(), sq.seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    return DSM_OK;
+}
+
+// the length of the sequence behind a product's launches: the map part's count comes down, the stream is through
+int pub_sequence_length(dsm_handle *h, const PubSequence &ps, int64_t &total) {
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], ps.mp.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    total = (int64_t)h->h_scalars[5] + ps.rt.total;
     return DSM_OK;
 }
 
@@ -1946,21 +1963,19 @@ int dsm_cloud_compose(dsm_handle *h, int select, int32_t n_segments, const int32
     MapSequence sq;
     int rc = check_sequence(h, select, n_segments, store_begin, store_count, INT64_MAX, sq); // (only the runs are bounded here)
     if (rc) return rc;
-    const int64_t runs_total = sq.runs_total;
-    if (runs_total > INT32_MAX) return fail(h, DSM_E_INVALID, "%lld points in the runs", (long long)runs_total);
+    if (sq.runs_total > INT32_MAX) return fail(h, DSM_E_INVALID, "%lld points in the runs", (long long)sq.runs_total);
     if ((rc = bind_device(h))) return rc;
     // where the points go: the caller's device memory, or staging for a host destination (no more than the points there can be)
     const int32_t dev_cap = (int32_t)(sq.bound < cap ? sq.bound : cap);
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
-    PubWords w;
-    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : (size_t)dev_cap, w))) return rc;
+    PubSequence ps;
+    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : (size_t)dev_cap, ps))) return rc;
     float4 *out = dst_on_device ? (float4 *)dst : h->pub_out.as<float4>();
-    hipError_t e = launch_cloud_map(h->hc.local, h->hc.n_local, sq.n_upper, select, w.tiles, w.total, out, dev_cap, h->stream);
-    if (e == hipSuccess) e = launch_cloud_gather(h->d_cloud, w.seg, (int)(sq.seg.size() / 3), (int)runs_total, w.total, out, dev_cap, h->stream);
+    hipError_t e = launch_cloud_map(ps.mp, out, dev_cap, h->stream);
+    if (e == hipSuccess) e = launch_cloud_gather(h->d_cloud, ps.rt, ps.mp.total, out, dev_cap, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "cloud launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], w.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const int64_t total = (int64_t)h->h_scalars[5] + runs_total;
+    int64_t total;
+    if ((rc = pub_sequence_length(h, ps, total))) return rc;
     *n = (int32_t)total;
     if (total > cap) return fail(h, DSM_E_CAPACITY, "%lld points exceed the caller's capacity %d", (long long)total, cap);
     if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->pub_out.p, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1976,22 +1991,19 @@ int dsm_mesh_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     MapSequence sq;
     int rc = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX, sq);
     if (rc) return rc;
-    const int64_t runs_total = sq.runs_total;
     if ((rc = bind_device(h))) return rc;
     const size_t rec_bytes = (size_t)mesh_surfel_bytes(vertex_layout);
     // where the vertices go: the caller's device memory, or staging for a host destination (no more than there can be)
     const int32_t dev_cap = (int32_t)(sq.bound < cap ? sq.bound : cap);
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
-    PubWords w;
-    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : (size_t)dev_cap * (rec_bytes / sizeof(float4)), w))) return rc;
+    PubSequence ps;
+    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : (size_t)dev_cap * (rec_bytes / sizeof(float4)), ps))) return rc;
     void *out = dst_on_device ? dst : h->pub_out.p;
-    hipError_t e = launch_mesh_gather(h->d_store, w.seg, (int)(sq.seg.size() / 3), (int)runs_total, vertex_layout, out, dev_cap, h->stream);
-    if (e == hipSuccess)
-        e = launch_mesh_map(h->hc.local, h->hc.n_local, sq.n_upper, select, w.tiles, w.total, vertex_layout, out, (int)runs_total, dev_cap, h->stream);
+    hipError_t e = launch_mesh_gather(h->d_store, ps.rt, vertex_layout, out, dev_cap, h->stream);
+    if (e == hipSuccess) e = launch_mesh_map(ps.mp, vertex_layout, out, ps.rt.total, dev_cap, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "mesh launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], w.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const int64_t total = (int64_t)h->h_scalars[5] + runs_total;
+    int64_t total;
+    if ((rc = pub_sequence_length(h, ps, total))) return rc;
     *n = (int32_t)total;
     if (total > cap) return fail(h, DSM_E_CAPACITY, "%lld surfels exceed the caller's capacity %d", (long long)total, cap);
     if (!dst_on_device && total) HIP_TRY(h, hipMemcpy(dst, h->pub_out.p, (size_t)total * rec_bytes, hipMemcpyDeviceToHost));
@@ -2060,13 +2072,13 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
     for (int y = 0; y < hh; y++) rays[(size_t)w + y] = ray_coeff(y, c.cy, c.fy);
     float *d_rays = (float *)(h->render_keys.as<unsigned long long>() + px);
     HIP_TRY(h, hipMemcpyAsync(d_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    PubWords pw;
-    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : 2 * q_depth + q_normal + q_int, pw))) return rc;
+    PubSequence ps;
+    if ((rc = pub_sequence(h, sq, dst_on_device ? 0 : 2 * q_depth + q_normal + q_int, ps))) return rc;
     RenderScratch sc;
     sc.keys = h->render_keys.as<unsigned long long>();
     sc.splats = h->render_splats.as<RenderSplat>();
     sc.slot_of = (int32_t *)(sc.splats + h->render_splats.bytes / splat_rec);
-    sc.counts = pw.counts;
+    sc.counts = ps.w.counts;
     sc.n_seq = (int32_t)n_seq;
     float *o_depth = (float *)planes->depth;
     int32_t *o_index = (int32_t *)planes->index;
@@ -2079,13 +2091,12 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
         if (o_normal) o_normal = (float *)(st + 2 * q_depth);
         if (o_int) o_int = (uint8_t *)(st + 2 * q_depth + q_normal);
     }
-    const hipError_t e = launch_render(h->d_store, pw.seg, (int)(sq.seg.size() / 3), (int)sq.runs_total, h->hc.local, h->hc.n_local, sq.n_upper, select,
-                                       pw.tiles, pw.total, cam, pose_inv, flags, eigen33_products(h), sc, d_rays, d_rays + w, o_depth, o_index, o_normal,
-                                       o_int, h->stream);
+    const hipError_t e = launch_render(h->d_store, ps.rt, ps.mp, cam, pose_inv, flags, eigen33_products(h), sc, d_rays, d_rays + w, o_depth, o_index,
+                                       o_normal, o_int, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "render launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], pw.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + sq.runs_total);
+    int64_t total;
+    if ((rc = pub_sequence_length(h, ps, total))) return rc;
+    *n_surfels = (int32_t)total;
     if (!dst_on_device) {
         if (planes->depth) HIP_TRY(h, hipMemcpy(planes->depth, o_depth, px * sizeof(float), hipMemcpyDeviceToHost));
         if (planes->index) HIP_TRY(h, hipMemcpy(planes->index, o_index, px * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -2173,8 +2184,8 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     if ((rc = scratch_grow(h, h->grid_splats, n_seq * sizeof(GridSplat), (n_seq + n_seq / 4 + 64) * sizeof(GridSplat)))) return rc;
     if ((rc = plane_scratch_grow(h, h->grid_planes, words * sizeof(uint32_t)))) return rc;
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
-    PubWords pw;
-    if ((rc = pub_sequence(h, sq, 0, pw))) return rc;
+    PubSequence ps;
+    if ((rc = pub_sequence(h, sq, 0, ps))) return rc;
     uint32_t *scratch = h->grid_planes.as<uint32_t>();
     GridSpec g;
     for (int a = 0; a < 3; a++) g.origin[a] = spec->origin[a];
@@ -2182,7 +2193,7 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
     GridScratch sc;
     sc.splats = h->grid_splats.as<GridSplat>();
-    sc.counts = pw.counts;
+    sc.counts = ps.w.counts;
     sc.n_seq = (int32_t)n_seq;
     sc.cell_tiles = (int32_t *)(scratch + at_tiles);
     GridOut out;
@@ -2191,16 +2202,15 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     out.index = !planes->index ? nullptr : dst_on_device ? planes->index : (int32_t *)(scratch + at_index);
     out.cells = !planes->cells ? nullptr : dst_on_device ? planes->cells : (int32_t *)(scratch + at_cells);
     out.cells_cap = (int32_t)cells_cap;
-    out.cells_total = planes->cells ? pw.cells_total : nullptr;
+    out.cells_total = planes->cells ? ps.w.cells_total : nullptr;
     out.cells_of_inflated = cells_of_inflated;
-    const hipError_t e = launch_grid(h->d_store, pw.seg, (int)(sq.seg.size() / 3), (int)sq.runs_total, h->hc.local, h->hc.n_local, sq.n_upper, select, pw.tiles,
-                                     pw.total, g, spec->inflate, sc, out, h->stream);
+    const hipError_t e = launch_grid(h->d_store, ps.rt, ps.mp, g, spec->inflate, sc, out, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "grid launch: %s", hipGetErrorString(e));
     h->h_scalars[6] = 0;
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], pw.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (planes->cells) HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[6], pw.cells_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *n_surfels = (int32_t)((int64_t)h->h_scalars[5] + sq.runs_total);
+    if (planes->cells) HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[6], ps.w.cells_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    int64_t total;
+    if ((rc = pub_sequence_length(h, ps, total))) return rc;
+    *n_surfels = (int32_t)total;
     const int32_t cells = h->h_scalars[6];
     *n_cells = cells;
     if (!dst_on_device) {

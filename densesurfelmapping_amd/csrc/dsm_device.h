@@ -200,13 +200,23 @@ struct RawCloudParams {
     float t[3];
     float fx, fy, cx, cy;
 };
-// XYZI of the records [0, min(*n_ptr, n_upper)) that pass `select` (kCloudMature / kCloudNonzero), in map order, into
-// out[0, cap); total[0] = how many passed (also those beyond cap).  tile_cnt: ceil(n_upper / 1024) ints of scratch
-hipError_t launch_cloud_map(const dsm_surfel *rec, const int32_t *n_ptr, int n_upper, int select, int32_t *tile_cnt, int32_t *total,
-                            float4 *out, int cap, hipStream_t st);
-// runs of src (seg: n_seg triples begin, count, exclusive output offset; `total` points in all) to out[*base_ptr + ...], below cap
-hipError_t launch_cloud_gather(const float4 *src, const int32_t *seg, int n_seg, int total, const int32_t *base_ptr, float4 *out, int cap,
-                               hipStream_t st);
+// The surfel sequence that the cloud, the mesh, the render and the grid read (dsm_k_sequence.h walks it): first the runs of the
+// inactive store, then the records of the resident map that pass `select`, in map order.
+struct RunTable {       // the runs: output j of them is store record seg[3 s] + (j - seg[3 s + 2]) of the last run s with seg[3 s + 2] <= j
+    const int32_t *seg; // device memory: n_seg triples (begin in the store, count > 0, exclusive offset in the sequence)
+    int n_seg, total;   // total = the sum of the counts
+};
+struct MapPart {           // the map part: the records [0, min(*n_ptr, n_upper)) of rec that pass select (kCloudMature / kCloudNonzero)
+    const dsm_surfel *rec;
+    const int32_t *n_ptr;  // device memory: the map's size; n_upper = the handle's running bound of it, which sizes the grids
+    int n_upper, select;
+    int32_t *tile_cnt;     // ceil(n_upper / kCloudTile) ints of scratch: the tile counts, then their exclusive prefix
+    int32_t *total;        // total[0] = how many records passed (also those a product's cap keeps out)
+};
+// XYZI of the map part, into out[0, cap)
+hipError_t launch_cloud_map(const MapPart &mp, float4 *out, int cap, hipStream_t st);
+// XYZI of the runs, read from the store's shadow src, to out[*base_ptr + ...] below cap: here the map part comes FIRST
+hipError_t launch_cloud_gather(const float4 *src, const RunTable &rt, const int32_t *base_ptr, float4 *out, int cap, hipStream_t st);
 // w * h world points of a pitched frame, column-major (index i * h + j for column i, row j)
 // (eigen33: rotation_R * cam_point in Eigen >= 3.3's product order, DSM_FLAG_EIGEN33_PRODUCTS)
 hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, int w, int h, const RawCloudParams &p, bool eigen33, float4 *out,
@@ -215,13 +225,11 @@ hipError_t launch_cloud_raw(const uint8_t *img, const float *depth, int pitch, i
 // ---- the hexagon mesh (dsm_k_mesh.h)
 constexpr int kMeshRef6 = 0, kMeshXyzRgba8 = 1; // dsm_mesh_vertex_layout of include/dsm.h
 constexpr int mesh_surfel_bytes(int layout) { return layout == kMeshRef6 ? 144 : 96; }
-// the six vertices of every record [0, min(*n_ptr, n_upper)) that passes `select`, in map order, as records base, base + 1, ...
-// of `out` (4-byte aligned; faster when 16-byte aligned), none at or beyond record cap; total[0] = how many passed.
-// tile_cnt: ceil(n_upper / 1024) ints of scratch
-hipError_t launch_mesh_map(const dsm_surfel *rec, const int32_t *n_ptr, int n_upper, int select, int32_t *tile_cnt, int32_t *total, int layout,
-                           void *out, int base, int cap, hipStream_t st);
-// runs of the records src (seg: launch_cloud_gather's table; `total` records in all) as records 0, 1, ... of `out`, below cap
-hipError_t launch_mesh_gather(const dsm_surfel *src, const int32_t *seg, int n_seg, int total, int layout, void *out, int cap, hipStream_t st);
+// the six vertices of every record of the map part as records base, base + 1, ... of `out` (4-byte aligned; faster when 16-byte
+// aligned), none at or beyond record cap
+hipError_t launch_mesh_map(const MapPart &mp, int layout, void *out, int base, int cap, hipStream_t st);
+// the runs of the store's records src as records 0, 1, ... of `out`, below cap
+hipError_t launch_mesh_gather(const dsm_surfel *src, const RunTable &rt, int layout, void *out, int cap, hipStream_t st);
 // 12 indices per surfel: 6 i + {0,1,2, 1,3,2, 2,3,4, 4,3,5}
 hipError_t launch_mesh_indices(uint32_t *out, int n, hipStream_t st);
 
@@ -234,12 +242,10 @@ struct RenderScratch {
     int32_t *counts;          // [2]: splats in the small list, in the large one
     int32_t n_seq;            // an upper bound of the sequence's length (the runs + the map's running bound)
 };
-// The surfel sequence = the runs of `store` (seg: launch_cloud_gather's table, runs_total records), then the records [0,
-// min(*n_ptr, n_upper)) of `rec` that pass `select`; total[0] = how many of those passed.  inv16: world -> cam.  ray_x [w] /
-// ray_y [h]: ray_coeff of every column / row, in device memory.  Any plane may be null.  tile_cnt as for launch_cloud_map.
-hipError_t launch_render(const dsm_surfel *store, const int32_t *seg, int n_seg, int runs_total, const dsm_surfel *rec, const int32_t *n_ptr, int n_upper,
-                         int select, int32_t *tile_cnt, int32_t *total, const RenderCam &cam, const float *inv16, uint32_t flags, bool eigen33,
-                         const RenderScratch &sc, const float *ray_x, const float *ray_y, float *depth, int32_t *index, float *normal,
+// The surfel sequence (above): the runs of `store`, then the map part.  inv16: world -> cam.  ray_x [w] / ray_y [h]: ray_coeff
+// of every column / row, in device memory.  Any plane may be null.
+hipError_t launch_render(const dsm_surfel *store, const RunTable &rt, const MapPart &mp, const RenderCam &cam, const float *inv16, uint32_t flags,
+                         bool eigen33, const RenderScratch &sc, const float *ray_x, const float *ray_y, float *depth, int32_t *index, float *normal,
                          uint8_t *intensity, hipStream_t st);
 
 // ---- the map as a voxel grid (dsm_k_grid.h; the definition is grid_setup / grid_covers / grid_centre of dsm_math.h)
@@ -259,10 +265,9 @@ struct GridOut {          // device memory; row-major [nz][ny][..]
     int32_t *cells_total; // the number of set cells, or null: no cell list
     bool cells_of_inflated;
 };
-// The surfel sequence as for launch_render.  inflate: the radius in voxels, 0 .. kGridMaxInflate.  tile_cnt as for launch_cloud_map.
-hipError_t launch_grid(const dsm_surfel *store, const int32_t *seg, int n_seg, int runs_total, const dsm_surfel *rec, const int32_t *n_ptr, int n_upper,
-                       int select, int32_t *tile_cnt, int32_t *total, const GridSpec &g, int inflate, const GridScratch &sc, const GridOut &out,
-                       hipStream_t st);
+// The surfel sequence (above): the runs of `store`, then the map part.  inflate: the radius in voxels, 0 .. kGridMaxInflate.
+hipError_t launch_grid(const dsm_surfel *store, const RunTable &rt, const MapPart &mp, const GridSpec &g, int inflate, const GridScratch &sc,
+                       const GridOut &out, hipStream_t st);
 // dst = src dilated by the voxels within radius r; pad bits of src ignored, of dst 0.  src != dst.
 hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int ny, int nz, int r, hipStream_t st);
 

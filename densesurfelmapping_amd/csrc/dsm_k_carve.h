@@ -131,13 +131,7 @@ hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, int nx, int ny
         const int blocks = (int)((n_vox + 255) / 256 < 16384 ? (n_vox + 255) / 256 : 16384);
         hipLaunchKernelGGL(k_space_state, dim3(blocks), dim3(256), 0, st, occ, fre, state, a);
     }
-    const int64_t cell_tiles_n = (n_words + 255) / 256; // <= 2^20
-    const int blocks = (int)(cell_tiles_n < 8192 ? cell_tiles_n : 8192);
-    hipLaunchKernelGGL(k_grid_cell_count, dim3(blocks), dim3(256), 0, st, (const uint32_t *)frontier, n_words, cell_tiles);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, cell_tiles, (int)cell_tiles_n, cells_total);
-    if (cells && cells_cap > 0)
-        hipLaunchKernelGGL(k_grid_cell_scatter, dim3(blocks), dim3(256), 0, st, (const uint32_t *)frontier, n_words, nx, a.wx, (const int32_t *)cell_tiles, cells,
-                           cells_cap);
+    launch_cell_list(frontier, n_words, nx, a.wx, cell_tiles, cells_total, cells, cells_cap, st);
     return hipGetLastError();
 }
 

@@ -1,50 +1,20 @@
 // dsm_k_cloud.h -- the node's point-cloud publications (SM.cpp = surfel_fusion/src/surfel_map.cpp of the reference):
-//   k_cloud_count / k_cloud_scan / k_cloud_scatter   order-preserving filtered compaction of the resident map into XYZI
-//                    (publish_active_pointcloud SM.cpp:1398-1417: update_times >= 5; publish_neighbor_pointcloud
+//   k_cloud_scan / k_cloud_scatter   behind k_cloud_count: order-preserving filtered compaction of the resident map into
+//                    XYZI (publish_active_pointcloud SM.cpp:1398-1417: update_times >= 5; publish_neighbor_pointcloud
 //                    SM.cpp:1292-1303: update_times != 0)
 //   k_cloud_gather   runs of the inactive store's XYZI shadow behind it (publish_inactive / all / neighbor_pointcloud,
 //                    SM.cpp:1305-1319, 1385-1454)
 //   k_cloud_raw      the fused frame back-projected to world points, column-major (publish_raw_pointcloud SM.cpp:1115-1151)
 // Included by dsm_kernels.hip.
 //
-// The compaction has no inter-workgroup waiting: a count pass (one tile of kCloudTile records per workgroup, wave ballots),
-// a one-workgroup exclusive scan of the tile counts, and a scatter pass that recomputes the ballots and places every
-// passing record at its tile offset + wave prefix + mbcnt rank.  update_times is read twice (once per pass); a look-back
-// scan would read it once but spins on other workgroups.
+// The compaction is the walk of dsm_k_sequence.h: k_cloud_count, k_cloud_scan, and a scatter pass that places every passing
+// record at its sequence number.
 #pragma once
-#include "dsm_k_common.h"
+#include "dsm_k_sequence.h"
 
 namespace dsm {
 
 constexpr int kRawTileW = 64, kRawTileH = 32;            // pixels of a k_cloud_raw tile (columns x rows)
-
-__device__ __forceinline__ bool cloud_pass(int select, int32_t update_times) {
-    return select == kCloudMature ? update_times >= 5 : update_times != 0;
-}
-
-// records below min(*n_ptr, n_upper) are the map: the grid covers n_upper, the running bound of the handle
-__device__ __forceinline__ int cloud_map_size(const int32_t *__restrict__ n_ptr, int n_upper) {
-    const int n = n_ptr[0];
-    return n < n_upper ? n : n_upper;
-}
-
-__global__ __launch_bounds__(256) void k_cloud_count(const dsm_surfel *__restrict__ rec, const int32_t *__restrict__ n_ptr, int n_upper,
-                                                     int select, int32_t *__restrict__ tile_cnt) {
-    __shared__ int s_cnt[4];
-    const int n = cloud_map_size(n_ptr, n_upper);
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int first = blockIdx.x * kCloudTile + wv * 64 * kCloudChunks;
-    int cnt = 0;
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const int i = first + c * 64 + lane;
-        const bool pass = i < n && cloud_pass(select, rec[i].update_times);
-        cnt += __popcll(__ballot(pass));
-    }
-    if (lane == 0) s_cnt[wv] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-}
 
 // in place: tile_cnt[0 .. n_tiles) -> exclusive prefix; total[0] = the sum.  One workgroup of 1024 threads.
 __global__ __launch_bounds__(1024) void k_cloud_scan(int32_t *__restrict__ tile_cnt, int n_tiles, int32_t *__restrict__ total) {
@@ -84,51 +54,23 @@ __global__ __launch_bounds__(1024) void k_cloud_scan(int32_t *__restrict__ tile_
     if (threadIdx.x == 0) total[0] = s_carry;
 }
 
-__global__ __launch_bounds__(256) void k_cloud_scatter(const dsm_surfel *__restrict__ rec, const int32_t *__restrict__ n_ptr, int n_upper,
-                                                       int select, const int32_t *__restrict__ tile_off, float4 *__restrict__ out, int cap) {
-    __shared__ int s_cnt[4];
-    const int n = cloud_map_size(n_ptr, n_upper);
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int first = blockIdx.x * kCloudTile + wv * 64 * kCloudChunks;
-    unsigned long long mask[kCloudChunks];
-    int cnt = 0;
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const int i = first + c * 64 + lane;
-        mask[c] = __ballot(i < n && cloud_pass(select, rec[i].update_times));
-        cnt += __popcll(mask[c]);
-    }
-    if (lane == 0) s_cnt[wv] = cnt;
-    __syncthreads();
-    int at = tile_off[blockIdx.x];
-    for (int k = 0; k < wv; k++) at += s_cnt[k];
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const unsigned long long m = mask[c];
-        if ((m >> lane) & 1ull) {
-            const int idx = at + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            if (idx < cap) {
-                const dsm_surfel *r = rec + first + c * 64 + lane;
-                out[idx] = make_float4(r->px, r->py, r->pz, r->color); // SM.cpp:1404-1409
-            }
+__global__ __launch_bounds__(256) void k_cloud_scatter(const MapPart mp, float4 *__restrict__ out, int cap) {
+    map_tile_walk(mp, 0, [&](unsigned long long m, int at, int i) {
+        const int idx = at + rank_below(m);
+        if (((m >> lane_id()) & 1ull) && idx < cap) {
+            const dsm_surfel *r = mp.rec + i;
+            out[idx] = make_float4(r->px, r->py, r->pz, r->color); // SM.cpp:1404-1409
         }
-        at += __popcll(m);
-    }
+    });
 }
 
-// seg[3 s + 0 .. 2] = (begin in the store, count, exclusive output offset) of the non-empty runs; output j of the runs goes to
-// out[base + j], base = *base_ptr (the map part's count, on the device)
-__global__ __launch_bounds__(256) void k_cloud_gather(const float4 *__restrict__ src, const int32_t *__restrict__ seg, int n_seg, int total,
-                                                      const int32_t *__restrict__ base_ptr, float4 *__restrict__ out, int cap) {
+// output j of the runs goes to out[base + j], base = *base_ptr (the map part's count, on the device)
+__global__ __launch_bounds__(256) void k_cloud_gather(const float4 *__restrict__ src, const RunTable rt, const int32_t *__restrict__ base_ptr,
+                                                      float4 *__restrict__ out, int cap) {
     const int base = base_ptr[0];
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < total; j += gridDim.x * 256) {
-        int lo = 0, hi = n_seg; // last run whose offset is <= j
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (seg[3 * mid + 2] <= j) lo = mid; else hi = mid;
-        }
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < rt.total; j += gridDim.x * 256) {
         const int dst = base + j;
-        if (dst < cap) out[dst] = src[seg[3 * lo] + (j - seg[3 * lo + 2])];
+        if (dst < cap) out[dst] = src[run_source(rt, j)];
     }
 }
 
@@ -162,22 +104,16 @@ template <bool E33 = false> __global__ __launch_bounds__(256) void k_cloud_raw(c
     }
 }
 
-hipError_t launch_cloud_map(const dsm_surfel *rec, const int32_t *n_ptr, int n_upper, int select, int32_t *tile_cnt, int32_t *total,
-                            float4 *out, int cap, hipStream_t st) {
-    const int tiles = (n_upper + kCloudTile - 1) / kCloudTile;
-    if (tiles == 0) return hipMemsetAsync(total, 0, sizeof(int32_t), st);
-    hipLaunchKernelGGL(k_cloud_count, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, tile_cnt);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, tile_cnt, tiles, total);
-    hipLaunchKernelGGL(k_cloud_scatter, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, (const int32_t *)tile_cnt, out, cap);
+hipError_t launch_cloud_map(const MapPart &mp, float4 *out, int cap, hipStream_t st) {
+    const hipError_t e = launch_map_offsets(mp, st);
+    if (e != hipSuccess || map_tiles(mp) == 0) return e;
+    hipLaunchKernelGGL(k_cloud_scatter, dim3(map_tiles(mp)), dim3(256), 0, st, mp, out, cap);
     return hipGetLastError();
 }
 
-hipError_t launch_cloud_gather(const float4 *src, const int32_t *seg, int n_seg, int total, const int32_t *base_ptr, float4 *out, int cap,
-                               hipStream_t st) {
-    if (n_seg == 0 || total == 0) return hipSuccess;
-    int blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_cloud_gather, dim3(blocks), dim3(256), 0, st, src, seg, n_seg, total, base_ptr, out, cap);
+hipError_t launch_cloud_gather(const float4 *src, const RunTable &rt, const int32_t *base_ptr, float4 *out, int cap, hipStream_t st) {
+    if (rt.n_seg == 0 || rt.total == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_cloud_gather, dim3(run_blocks(rt.total)), dim3(256), 0, st, src, rt, base_ptr, out, cap);
     return hipGetLastError();
 }
 

@@ -24,7 +24,7 @@
 // per-voxel passes run along x; the word passes read the label of the first voxel of a run, along x as well.
 #pragma once
 #include "dsm_components.h"
-#include "dsm_k_common.h"
+#include "dsm_k_grid.h"
 
 namespace dsm {
 
@@ -361,7 +361,6 @@ hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, int nx
     const int64_t n_words = (int64_t)a.wx * ny * nz, n_vox = (int64_t)nx * ny * nz; // <= 2^26 each
     const int vox_blocks = (int)((n_vox + 255) / 256 < 16384 ? (n_vox + 255) / 256 : 16384);
     const int word_blocks = (int)((n_words + 255) / 256 < 8192 ? (n_words + 255) / 256 : 8192);
-    const int64_t tiles = (n_words + kCompBlockWords - 1) / kCompBlockWords; // <= 2^18
     const hipError_t e0 = hipMemsetAsync(work, 0, (size_t)n_vox * sizeof(int32_t), st);
     if (e0 != hipSuccess) return e0;
     hipLaunchKernelGGL(k_comp_init, dim3(vox_blocks), dim3(256), 0, st, src, label, a);
@@ -370,10 +369,9 @@ hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, int nx
     hipLaunchKernelGGL(k_comp_flatten, dim3(vox_blocks), dim3(256), 0, st, label, n_vox);
     hipLaunchKernelGGL(k_comp_count, dim3(word_blocks), dim3(256), 0, st, src, (const int32_t *)label, work, root_bits, a);
     hipLaunchKernelGGL(k_comp_keep, dim3(word_blocks), dim3(256), 0, st, (const uint32_t *)root_bits, (const int32_t *)work, keep_bits, min_count, a);
-    hipLaunchKernelGGL(k_grid_cell_count, dim3(word_blocks), dim3(256), 0, st, (const uint32_t *)root_bits, n_words, root_tiles);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, root_tiles, (int)tiles, n_all);
-    hipLaunchKernelGGL(k_grid_cell_count, dim3(word_blocks), dim3(256), 0, st, (const uint32_t *)keep_bits, n_words, keep_tiles);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, keep_tiles, (int)tiles, n_kept);
+    // the counts alone, no list: the tiles of the cell list are k_comp_rank's (kCompBlockWords)
+    launch_cell_list(root_bits, n_words, nx, a.wx, root_tiles, n_all, nullptr, 0, st);
+    launch_cell_list(keep_bits, n_words, nx, a.wx, keep_tiles, n_kept, nullptr, 0, st);
     if (table && cap > 0) {
         hipLaunchKernelGGL(k_comp_rank, dim3(word_blocks), dim3(256), 0, st, (const uint32_t *)root_bits, (const uint32_t *)keep_bits,
                            (const int32_t *)keep_tiles, work, tag_src, table, cap, a);

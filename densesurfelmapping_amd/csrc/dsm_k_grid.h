@@ -3,9 +3,9 @@
 // definition (grid_setup / grid_covers / grid_centre) is in dsm_math.h and shared with the host checker tests/grid_host.cpp; this
 // file is how it is evaluated:
 //   k_grid_clear       the index plane to -1 or the bit set to 0 (whichever is splatted into), and the two list counts
-//   k_grid_setup_map   as k_render_setup_map / _run: the map records that pass `select` and the runs of the store's records,
-//   k_grid_setup_run   a lane per surfel does grid_setup; survivors are appended as GridSplat records to ONE array, small boxes
-//                      from the front, large ones from the back, by a wave ballot and one atomic add per wave and list
+//   k_grid_setup_map   the map part and the runs of the surfel sequence (dsm_k_sequence.h: map_tile_walk, run_source): a lane per
+//   k_grid_setup_run   surfel does grid_setup; survivors are appended as GridSplat records to ONE array, small boxes from the
+//                      front, large ones from the back (two_ended_slot)
 //   k_grid_splat       the small list: 16 lanes per surfel, four surfels per wave.  The 16 lanes take 16 voxels along x from a
 //                      multiple of 16, so they share one word of the bit set: the wave's ballot gives each group its 16 bits
 //                      and one lane ORs them in -- or every lane does its atomicMin on 16 contiguous ints of the index plane
@@ -15,6 +15,7 @@
 //   k_grid_inflate     bit-parallel dilation on 32-voxel words, a tile of row words with its y/z halo and one word of x halo
 //                      each side in LDS; for each (dy, dz) inside the radius the source row dilated along x by the table's width
 //   k_grid_cell_count / k_cloud_scan / k_grid_cell_scatter   popcount per word, scan, ordered scatter of the linear indices
+//                      (launch_cell_list: also the frontier's list and the component counts)
 // A voxel does a plain load first and skips the atomic when nothing would change: bits only get set and indices only decrease,
 // so a stale value can cost an atomic, never a wrong skip.  The atomics are atomicOr / atomicMin / atomicAdd on 32-bit integers,
 // plain C++.  What has been measured on this chip (MI355X_MICROARCH.md, global float atomics) is the no-return fp32 add; the
@@ -44,67 +45,26 @@ __device__ __forceinline__ void grid_emit(const GridSetupArgs &a, bool valid, co
     if (valid) keep = grid_setup(a.g, *r, number, s);
     const int64_t rows = (int64_t)(s.hi[1] - s.lo[1]) * (s.hi[2] - s.lo[2]);
     const bool small = keep && s.hi[0] - s.lo[0] <= kGridSmallW && rows <= kGridSmallRows;
-    const bool big = keep && !small;
-    const unsigned long long m_small = __ballot(small), m_big = __ballot(big);
-    const int lane = lane_id();
-    int base_small = 0, base_big = 0;
-    if (lane == 0) {
-        if (m_small) base_small = atomicAdd(&counts[0], __popcll(m_small));
-        if (m_big) base_big = atomicAdd(&counts[1], __popcll(m_big));
-    }
-    base_small = __shfl(base_small, 0, 64);
-    base_big = __shfl(base_big, 0, 64);
-    if (keep) {
-        const int slot = small ? base_small + rank_below(m_small) : a.n_seq - 1 - (base_big + rank_below(m_big));
-        if (slot >= 0 && slot < a.n_seq) splats[slot] = s; // (always: survivors <= sequence <= n_seq)
-    }
+    const int slot = two_ended_slot(small, keep && !small, counts, a.n_seq);
+    if (keep && slot >= 0 && slot < a.n_seq) splats[slot] = s; // (always: survivors <= sequence <= n_seq)
 }
 
-__global__ __launch_bounds__(256) void k_grid_setup_map(const dsm_surfel *__restrict__ rec, const int32_t *__restrict__ n_ptr, int n_upper, int select,
-                                                        const int32_t *__restrict__ tile_off, int base, const GridSetupArgs a,
-                                                        GridSplat *__restrict__ splats, int32_t *__restrict__ counts) {
-    __shared__ int s_cnt[4];
-    const int n = cloud_map_size(n_ptr, n_upper);
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int first = blockIdx.x * kCloudTile + wv * 64 * kCloudChunks;
-    unsigned long long mask[kCloudChunks];
-    int cnt = 0;
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const int i = first + c * 64 + lane;
-        mask[c] = __ballot(i < n && cloud_pass(select, rec[i].update_times));
-        cnt += __popcll(mask[c]);
-    }
-    if (lane == 0) s_cnt[wv] = cnt;
-    __syncthreads();
-    int at = base + tile_off[blockIdx.x];
-    for (int k = 0; k < wv; k++) at += s_cnt[k];
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const unsigned long long m = mask[c];
+__global__ __launch_bounds__(256) void k_grid_setup_map(const MapPart mp, int base, const GridSetupArgs a, GridSplat *__restrict__ splats,
+                                                        int32_t *__restrict__ counts) {
+    map_tile_walk(mp, base, [&](unsigned long long m, int at, int i) {
         if (m) // (wave-uniform)
-            grid_emit(a, (m >> lane) & 1ull, rec + first + c * 64 + lane, at + rank_below(m), splats, counts);
-        at += __popcll(m);
-    }
+            grid_emit(a, (m >> lane_id()) & 1ull, mp.rec + i, at + rank_below(m), splats, counts);
+    });
 }
 
-// seg: k_cloud_gather's table; output j of the runs is surfel j of the sequence.  A wave takes 64 consecutive outputs at a time.
-__global__ __launch_bounds__(256) void k_grid_setup_run(const dsm_surfel *__restrict__ src, const int32_t *__restrict__ seg, int n_seg, int total,
-                                                        const GridSetupArgs a, GridSplat *__restrict__ splats, int32_t *__restrict__ counts) {
+// output j of the runs is surfel j of the sequence.  A wave takes 64 consecutive outputs at a time.
+__global__ __launch_bounds__(256) void k_grid_setup_run(const dsm_surfel *__restrict__ src, const RunTable rt, const GridSetupArgs a,
+                                                        GridSplat *__restrict__ splats, int32_t *__restrict__ counts) {
     const int lane = lane_id(), wv = threadIdx.x >> 6;
-    for (int64_t j0 = ((int64_t)blockIdx.x * 4 + wv) * 64; j0 < total; j0 += (int64_t)gridDim.x * 256) {
+    for (int64_t j0 = ((int64_t)blockIdx.x * 4 + wv) * 64; j0 < rt.total; j0 += (int64_t)gridDim.x * 256) {
         const int j = (int)j0 + lane;
-        const bool valid = j < total;
-        const dsm_surfel *r = src;
-        if (valid) {
-            int lo = 0, hi = n_seg; // last run whose offset is <= j
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (seg[3 * mid + 2] <= j) lo = mid; else hi = mid;
-            }
-            r = src + ((int64_t)seg[3 * lo] + (j - seg[3 * lo + 2]));
-        }
-        grid_emit(a, valid, r, j, splats, counts);
+        const bool valid = j < rt.total;
+        grid_emit(a, valid, valid ? src + run_source(rt, j) : src, j, splats, counts);
     }
 }
 
@@ -322,6 +282,18 @@ __global__ __launch_bounds__(256) void k_grid_cell_scatter(const uint32_t *__res
     }
 }
 
+// *cells_total = the set bits of bits[0, n_words) (rows of wx words, nx voxels); with `cells`, their linear indices ascending, none
+// at or beyond cells_cap.  cell_tiles: (n_words + 255) / 256 ints of scratch (<= 2^20: at most 2^28 words)
+inline void launch_cell_list(const uint32_t *bits, int64_t n_words, int nx, int wx, int32_t *cell_tiles, int32_t *cells_total, int32_t *cells,
+                             int cells_cap, hipStream_t st) {
+    const int64_t tiles = (n_words + 255) / 256;
+    const int blocks = (int)(tiles < 8192 ? tiles : 8192);
+    hipLaunchKernelGGL(k_grid_cell_count, dim3(blocks), dim3(256), 0, st, bits, n_words, cell_tiles);
+    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, cell_tiles, (int)tiles, cells_total);
+    if (cells && cells_cap > 0)
+        hipLaunchKernelGGL(k_grid_cell_scatter, dim3(blocks), dim3(256), 0, st, bits, n_words, nx, wx, (const int32_t *)cell_tiles, cells, cells_cap);
+}
+
 hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int ny, int nz, int r, hipStream_t st) {
     GridInflateArgs a;
     a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32; a.r = r;
@@ -334,9 +306,8 @@ hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int n
 }
 
 // the clear, then the lists, then the planes derived from them: launched in this order on one stream
-hipError_t launch_grid(const dsm_surfel *store, const int32_t *seg, int n_seg, int runs_total, const dsm_surfel *rec, const int32_t *n_ptr, int n_upper,
-                       int select, int32_t *tile_cnt, int32_t *total, const GridSpec &g, int inflate, const GridScratch &sc, const GridOut &out,
-                       hipStream_t st) {
+hipError_t launch_grid(const dsm_surfel *store, const RunTable &rt, const MapPart &mp, const GridSpec &g, int inflate, const GridScratch &sc,
+                       const GridOut &out, hipStream_t st) {
     const int wx = (g.n[0] + 31) / 32;
     const int64_t rows = (int64_t)g.n[1] * g.n[2], n_vox = rows * g.n[0], n_words = rows * wx; // <= 2^28 each
     {
@@ -348,21 +319,10 @@ hipError_t launch_grid(const dsm_surfel *store, const int32_t *seg, int n_seg, i
     GridSetupArgs a;
     a.g = g;
     a.n_seq = sc.n_seq;
-    if (n_seg > 0 && runs_total > 0) {
-        int blocks = (runs_total + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(k_grid_setup_run, dim3(blocks), dim3(256), 0, st, store, seg, n_seg, runs_total, a, sc.splats, sc.counts);
-    }
-    const int tiles = (n_upper + kCloudTile - 1) / kCloudTile;
-    if (tiles == 0) {
-        const hipError_t e = hipMemsetAsync(total, 0, sizeof(int32_t), st);
-        if (e != hipSuccess) return e;
-    } else {
-        hipLaunchKernelGGL(k_cloud_count, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, tile_cnt);
-        hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, tile_cnt, tiles, total);
-        hipLaunchKernelGGL(k_grid_setup_map, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, (const int32_t *)tile_cnt, runs_total, a, sc.splats,
-                           sc.counts);
-    }
+    if (rt.n_seg > 0 && rt.total > 0) hipLaunchKernelGGL(k_grid_setup_run, dim3(run_blocks(rt.total)), dim3(256), 0, st, store, rt, a, sc.splats, sc.counts);
+    const hipError_t e = launch_map_offsets(mp, st);
+    if (e != hipSuccess) return e;
+    if (map_tiles(mp) > 0) hipLaunchKernelGGL(k_grid_setup_map, dim3(map_tiles(mp)), dim3(256), 0, st, mp, rt.total, a, sc.splats, sc.counts);
     GridTarget t;
     t.g = g;
     t.wx = wx;
@@ -383,16 +343,8 @@ hipError_t launch_grid(const dsm_surfel *store, const int32_t *seg, int n_seg, i
         const hipError_t e = launch_grid_inflate(out.occupied, out.inflated, g.n[0], g.n[1], g.n[2], inflate, st);
         if (e != hipSuccess) return e;
     }
-    if (out.cells_total) {
-        const uint32_t *of = out.cells_of_inflated ? out.inflated : out.occupied;
-        const int64_t cell_tiles = (n_words + 255) / 256; // <= 2^20
-        const int blocks = (int)(cell_tiles < 8192 ? cell_tiles : 8192);
-        hipLaunchKernelGGL(k_grid_cell_count, dim3(blocks), dim3(256), 0, st, of, n_words, sc.cell_tiles);
-        hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, sc.cell_tiles, (int)cell_tiles, out.cells_total);
-        if (out.cells && out.cells_cap > 0)
-            hipLaunchKernelGGL(k_grid_cell_scatter, dim3(blocks), dim3(256), 0, st, of, n_words, g.n[0], wx, (const int32_t *)sc.cell_tiles, out.cells,
-                               out.cells_cap);
-    }
+    if (out.cells_total)
+        launch_cell_list(out.cells_of_inflated ? out.inflated : out.occupied, n_words, g.n[0], wx, sc.cell_tiles, out.cells_total, out.cells, out.cells_cap, st);
     return hipGetLastError();
 }
 

@@ -1,9 +1,7 @@
 // dsm_k_mesh.h -- the hexagon mesh of SurfelMap::save_mesh (SM.cpp = surfel_fusion/src/surfel_map.cpp of the reference,
 // :1176-1280) as vertex and index buffers:
-//   k_mesh_scatter   the resident records that pass `select`, in map order: k_cloud_count / k_cloud_scan of dsm_k_cloud.h
-//                    give the tile offsets, this pass recomputes the ballots as k_cloud_scatter does
-//   k_mesh_gather    runs of the inactive store's surfel RECORDS (not the XYZI shadow) through k_cloud_gather's
-//                    (begin, count, offset) table
+//   k_mesh_scatter   the map part of the surfel sequence (dsm_k_sequence.h: map_tile_walk)
+//   k_mesh_gather    its runs, of the inactive store's surfel RECORDS (not the XYZI shadow; run_source)
 //   k_mesh_indices   12 indices per surfel, the four faces of :1274-1277
 // Included by dsm_kernels.hip.
 //
@@ -84,67 +82,37 @@ template <int LAYOUT> __device__ __forceinline__ void mesh_flush(const mesh_f4 *
 // out: the destination's first byte; the map part starts at record `base` (the runs of the store come first); records at
 // or beyond `cap` are not written
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_mesh_scatter(const dsm_surfel *__restrict__ rec, const int32_t *__restrict__ n_ptr, int n_upper, int select,
-                                                      const int32_t *__restrict__ tile_off, float *__restrict__ out, int base, int cap) {
+__global__ __launch_bounds__(256) void k_mesh_scatter(const MapPart mp, float *__restrict__ out, int base, int cap) {
     constexpr int kSlots = MeshLayout<LAYOUT>::kSlots;
     __shared__ mesh_f4 s_img[4][64 * kSlots];
-    __shared__ int s_cnt[4];
-    const int n = cloud_map_size(n_ptr, n_upper);
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int first = blockIdx.x * kCloudTile + wv * 64 * kCloudChunks;
-    unsigned long long mask[kCloudChunks];
-    int cnt = 0;
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const int i = first + c * 64 + lane;
-        mask[c] = __ballot(i < n && cloud_pass(select, rec[i].update_times));
-        cnt += __popcll(mask[c]);
-    }
-    if (lane == 0) s_cnt[wv] = cnt;
-    __syncthreads();
-    int64_t at = (int64_t)base + tile_off[blockIdx.x];
-    for (int k = 0; k < wv; k++) at += s_cnt[k];
-    mesh_f4 *img = s_img[wv];
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const unsigned long long m = mask[c];
-        const int passed = __popcll(m);
-        const int64_t room = (int64_t)cap - at; // records of this run that fit below cap
-        const int n_rec = room <= 0 ? 0 : room < passed ? (int)room : passed;
+    const int lane = lane_id();
+    mesh_f4 *img = s_img[threadIdx.x >> 6];
+    map_tile_walk(mp, base, [&](unsigned long long m, int at, int i) {
+        const int passed = __popcll(m), room = cap - at; // records of this run that fit below cap
+        const int n_rec = room <= 0 ? 0 : room < passed ? room : passed;
         if (n_rec > 0) { // (wave-uniform)
             if ((m >> lane) & 1ull) {
                 const int rank = rank_below(m);
-                if (rank < n_rec) mesh_stage<LAYOUT>(img, rank, rec[first + c * 64 + lane]);
+                if (rank < n_rec) mesh_stage<LAYOUT>(img, rank, mp.rec[i]);
             }
             wave_lds_sync();
-            mesh_flush<LAYOUT>(img, n_rec, out + at * (int64_t)(kSlots * 4), lane);
+            mesh_flush<LAYOUT>(img, n_rec, out + (int64_t)at * (kSlots * 4), lane);
             wave_lds_sync(); // the next chunk overwrites the image
         }
-        at += passed;
-    }
+    });
 }
 
-// seg[3 s + 0 .. 2] = (begin in the store, count, exclusive output offset) of the non-empty runs (k_cloud_gather's table);
 // output j of the runs is record j of the destination.  A wave takes 64 consecutive outputs at a time.
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_mesh_gather(const dsm_surfel *__restrict__ src, const int32_t *__restrict__ seg, int n_seg, int total,
-                                                     float *__restrict__ out, int cap) {
+__global__ __launch_bounds__(256) void k_mesh_gather(const dsm_surfel *__restrict__ src, const RunTable rt, float *__restrict__ out, int cap) {
     constexpr int kSlots = MeshLayout<LAYOUT>::kSlots;
     __shared__ mesh_f4 s_img[4][64 * kSlots];
     const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int lim = total < cap ? total : cap;
+    const int lim = rt.total < cap ? rt.total : cap;
     mesh_f4 *img = s_img[wv];
     for (int64_t j0 = ((int64_t)blockIdx.x * 4 + wv) * 64; j0 < lim; j0 += (int64_t)gridDim.x * 256) {
         const int n_rec = lim - j0 < 64 ? (int)(lim - j0) : 64;
-        if (lane < n_rec) {
-            const int j = (int)j0 + lane;
-            int lo = 0, hi = n_seg; // last run whose offset is <= j
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (seg[3 * mid + 2] <= j) lo = mid; else hi = mid;
-            }
-            mesh_stage<LAYOUT>(img, lane, src[(int64_t)seg[3 * lo] + (j - seg[3 * lo + 2])]);
-        }
+        if (lane < n_rec) mesh_stage<LAYOUT>(img, lane, src[run_source(rt, (int)j0 + lane)]);
         wave_lds_sync();
         mesh_flush<LAYOUT>(img, n_rec, out + j0 * (int64_t)(kSlots * 4), lane);
         wave_lds_sync();
@@ -171,30 +139,19 @@ template <bool WIDE> __global__ __launch_bounds__(256) void k_mesh_indices(uint3
     }
 }
 
-template <int LAYOUT>
-static hipError_t launch_mesh_map_as(const dsm_surfel *rec, const int32_t *n_ptr, int n_upper, int select, int32_t *tile_cnt, int32_t *total,
-                                     float *out, int base, int cap, hipStream_t st) {
-    const int tiles = (n_upper + kCloudTile - 1) / kCloudTile;
-    if (tiles == 0) return hipMemsetAsync(total, 0, sizeof(int32_t), st);
-    hipLaunchKernelGGL(k_cloud_count, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, tile_cnt);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, tile_cnt, tiles, total);
-    hipLaunchKernelGGL(k_mesh_scatter<LAYOUT>, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, (const int32_t *)tile_cnt, out, base, cap);
+hipError_t launch_mesh_map(const MapPart &mp, int layout, void *out, int base, int cap, hipStream_t st) {
+    const hipError_t e = launch_map_offsets(mp, st);
+    if (e != hipSuccess || map_tiles(mp) == 0) return e;
+    if (layout == kMeshRef6) hipLaunchKernelGGL(k_mesh_scatter<kMeshRef6>, dim3(map_tiles(mp)), dim3(256), 0, st, mp, (float *)out, base, cap);
+    else hipLaunchKernelGGL(k_mesh_scatter<kMeshXyzRgba8>, dim3(map_tiles(mp)), dim3(256), 0, st, mp, (float *)out, base, cap);
     return hipGetLastError();
 }
 
-hipError_t launch_mesh_map(const dsm_surfel *rec, const int32_t *n_ptr, int n_upper, int select, int32_t *tile_cnt, int32_t *total, int layout,
-                           void *out, int base, int cap, hipStream_t st) {
-    return layout == kMeshRef6 ? launch_mesh_map_as<kMeshRef6>(rec, n_ptr, n_upper, select, tile_cnt, total, (float *)out, base, cap, st)
-                               : launch_mesh_map_as<kMeshXyzRgba8>(rec, n_ptr, n_upper, select, tile_cnt, total, (float *)out, base, cap, st);
-}
-
-hipError_t launch_mesh_gather(const dsm_surfel *src, const int32_t *seg, int n_seg, int total, int layout, void *out, int cap, hipStream_t st) {
-    const int lim = total < cap ? total : cap;
-    if (n_seg == 0 || lim <= 0) return hipSuccess;
-    int blocks = (lim + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (layout == kMeshRef6) hipLaunchKernelGGL(k_mesh_gather<kMeshRef6>, dim3(blocks), dim3(256), 0, st, src, seg, n_seg, total, (float *)out, cap);
-    else hipLaunchKernelGGL(k_mesh_gather<kMeshXyzRgba8>, dim3(blocks), dim3(256), 0, st, src, seg, n_seg, total, (float *)out, cap);
+hipError_t launch_mesh_gather(const dsm_surfel *src, const RunTable &rt, int layout, void *out, int cap, hipStream_t st) {
+    const int lim = rt.total < cap ? rt.total : cap;
+    if (rt.n_seg == 0 || lim <= 0) return hipSuccess;
+    if (layout == kMeshRef6) hipLaunchKernelGGL(k_mesh_gather<kMeshRef6>, dim3(run_blocks(lim)), dim3(256), 0, st, src, rt, (float *)out, cap);
+    else hipLaunchKernelGGL(k_mesh_gather<kMeshXyzRgba8>, dim3(run_blocks(lim)), dim3(256), 0, st, src, rt, (float *)out, cap);
     return hipGetLastError();
 }
 

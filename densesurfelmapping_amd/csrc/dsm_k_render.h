@@ -2,12 +2,10 @@
 // and intensity of the nearest disc along every pixel's ray.  The definition (render_setup / render_hit / render_key) is in
 // dsm_math.h and shared with the host checker tests/render_host.cpp; this file is how it is evaluated:
 //   k_render_clear     the key plane u64 [h][w] to all ones (no hit)
-//   k_render_setup_map the map records that pass `select` (k_cloud_count / k_cloud_scan give the tile offsets, the ballots are
-//   k_render_setup_run recomputed as in k_mesh_scatter), and the runs of the store's records through k_cloud_gather's (begin,
-//                      count, offset) table: a lane per surfel does render_setup; survivors are appended as RenderSplat
-//                      records to ONE array -- boxes of at most kRenderSmallW x kRenderSmallArea from the front, larger ones
-//                      from the back (they cannot meet: the array is as long as the sequence) -- by a wave ballot and one
-//                      atomic add per wave and list.  slot_of[number] = where the record went (k_render_resolve's way back).
+//   k_render_setup_map the map part and the runs of the surfel sequence (dsm_k_sequence.h: map_tile_walk, run_source): a lane
+//   k_render_setup_run per surfel does render_setup; survivors are appended as RenderSplat records to ONE array -- boxes of at
+//                      most kRenderSmallW x kRenderSmallArea from the front, larger ones from the back (two_ended_slot).
+//                      slot_of[number] = where the record went (k_render_resolve's way back).
 //   k_render_splat     the small list: 16 lanes per splat, four splats per wave; the 16 lanes take one box row per trip, so a
 //                      wave's atomic instruction touches up to four runs of 128 bytes instead of 64 scattered lines
 //   k_render_splat_big the large list: a workgroup per splat in turn (grid-stride), 16 rows at a time, so a disc in front of the
@@ -45,73 +43,31 @@ __device__ __forceinline__ void render_emit(const RenderSetupArgs &a, bool valid
     if (valid) keep = render_setup<E33>(a.cam, a.inv, a.flags, *r, number, s);
     const int bw = (int)s.x1 - (int)s.x0, bh = (int)s.y1 - (int)s.y0;
     const bool small = keep && bw <= kRenderSmallW && bw * bh <= kRenderSmallArea;
-    const bool big = keep && !small;
-    const unsigned long long m_small = __ballot(small), m_big = __ballot(big);
-    const int lane = lane_id();
-    int base_small = 0, base_big = 0;
-    if (lane == 0) {
-        if (m_small) base_small = atomicAdd(&counts[0], __popcll(m_small));
-        if (m_big) base_big = atomicAdd(&counts[1], __popcll(m_big));
-    }
-    base_small = __shfl(base_small, 0, 64);
-    base_big = __shfl(base_big, 0, 64);
-    if (keep) {
-        const int slot = small ? base_small + rank_below(m_small) : a.n_seq - 1 - (base_big + rank_below(m_big));
-        if (slot >= 0 && slot < a.n_seq && number >= 0 && number < a.n_seq) { // (always: survivors <= sequence <= n_seq)
-            splats[slot] = s;
-            slot_of[number] = slot;
-        }
+    const int slot = two_ended_slot(small, keep && !small, counts, a.n_seq);
+    if (keep && slot >= 0 && slot < a.n_seq && number >= 0 && number < a.n_seq) { // (always: survivors <= sequence <= n_seq)
+        splats[slot] = s;
+        slot_of[number] = slot;
     }
 }
 
 template <bool E33>
-__global__ __launch_bounds__(256) void k_render_setup_map(const dsm_surfel *__restrict__ rec, const int32_t *__restrict__ n_ptr, int n_upper, int select,
-                                                          const int32_t *__restrict__ tile_off, int base, const RenderSetupArgs a,
-                                                          RenderSplat *__restrict__ splats, int32_t *__restrict__ slot_of, int32_t *__restrict__ counts) {
-    __shared__ int s_cnt[4];
-    const int n = cloud_map_size(n_ptr, n_upper);
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int first = blockIdx.x * kCloudTile + wv * 64 * kCloudChunks;
-    unsigned long long mask[kCloudChunks];
-    int cnt = 0;
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const int i = first + c * 64 + lane;
-        mask[c] = __ballot(i < n && cloud_pass(select, rec[i].update_times));
-        cnt += __popcll(mask[c]);
-    }
-    if (lane == 0) s_cnt[wv] = cnt;
-    __syncthreads();
-    int at = base + tile_off[blockIdx.x];
-    for (int k = 0; k < wv; k++) at += s_cnt[k];
-#pragma unroll
-    for (int c = 0; c < kCloudChunks; c++) {
-        const unsigned long long m = mask[c];
+__global__ __launch_bounds__(256) void k_render_setup_map(const MapPart mp, int base, const RenderSetupArgs a, RenderSplat *__restrict__ splats,
+                                                          int32_t *__restrict__ slot_of, int32_t *__restrict__ counts) {
+    map_tile_walk(mp, base, [&](unsigned long long m, int at, int i) {
         if (m) // (wave-uniform)
-            render_emit<E33>(a, (m >> lane) & 1ull, rec + first + c * 64 + lane, at + rank_below(m), splats, slot_of, counts);
-        at += __popcll(m);
-    }
+            render_emit<E33>(a, (m >> lane_id()) & 1ull, mp.rec + i, at + rank_below(m), splats, slot_of, counts);
+    });
 }
 
-// seg: k_cloud_gather's table; output j of the runs is surfel j of the sequence.  A wave takes 64 consecutive outputs at a time.
+// output j of the runs is surfel j of the sequence.  A wave takes 64 consecutive outputs at a time.
 template <bool E33>
-__global__ __launch_bounds__(256) void k_render_setup_run(const dsm_surfel *__restrict__ src, const int32_t *__restrict__ seg, int n_seg, int total,
-                                                          const RenderSetupArgs a, RenderSplat *__restrict__ splats, int32_t *__restrict__ slot_of,
-                                                          int32_t *__restrict__ counts) {
+__global__ __launch_bounds__(256) void k_render_setup_run(const dsm_surfel *__restrict__ src, const RunTable rt, const RenderSetupArgs a,
+                                                          RenderSplat *__restrict__ splats, int32_t *__restrict__ slot_of, int32_t *__restrict__ counts) {
     const int lane = lane_id(), wv = threadIdx.x >> 6;
-    for (int64_t j0 = ((int64_t)blockIdx.x * 4 + wv) * 64; j0 < total; j0 += (int64_t)gridDim.x * 256) {
+    for (int64_t j0 = ((int64_t)blockIdx.x * 4 + wv) * 64; j0 < rt.total; j0 += (int64_t)gridDim.x * 256) {
         const int j = (int)j0 + lane;
-        const bool valid = j < total;
-        const dsm_surfel *r = src;
-        if (valid) {
-            int lo = 0, hi = n_seg; // last run whose offset is <= j
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (seg[3 * mid + 2] <= j) lo = mid; else hi = mid;
-            }
-            r = src + ((int64_t)seg[3 * lo] + (j - seg[3 * lo + 2]));
-        }
-        render_emit<E33>(a, valid, r, j, splats, slot_of, counts);
+        const bool valid = j < rt.total;
+        render_emit<E33>(a, valid, valid ? src + run_source(rt, j) : src, j, splats, slot_of, counts);
     }
 }
 
@@ -196,9 +152,8 @@ __global__ __launch_bounds__(256) void k_render_resolve(const unsigned long long
 }
 
 // keys, then the lists: launched in this order on one stream
-hipError_t launch_render(const dsm_surfel *store, const int32_t *seg, int n_seg, int runs_total, const dsm_surfel *rec, const int32_t *n_ptr, int n_upper,
-                         int select, int32_t *tile_cnt, int32_t *total, const RenderCam &cam, const float *inv16, uint32_t flags, bool eigen33,
-                         const RenderScratch &sc, const float *ray_x, const float *ray_y, float *depth, int32_t *index, float *normal,
+hipError_t launch_render(const dsm_surfel *store, const RunTable &rt, const MapPart &mp, const RenderCam &cam, const float *inv16, uint32_t flags,
+                         bool eigen33, const RenderScratch &sc, const float *ray_x, const float *ray_y, float *depth, int32_t *index, float *normal,
                          uint8_t *intensity, hipStream_t st) {
     const int n_px = cam.w * cam.h; // <= 8192 * 8192
     int px_blocks = (n_px + 255) / 256;
@@ -209,21 +164,15 @@ hipError_t launch_render(const dsm_surfel *store, const int32_t *seg, int n_seg,
     for (int k = 0; k < 16; k++) a.inv[k] = inv16[k];
     a.flags = flags;
     a.n_seq = sc.n_seq;
-    if (n_seg > 0 && runs_total > 0) {
-        int blocks = (runs_total + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        if (eigen33) hipLaunchKernelGGL(k_render_setup_run<true>, dim3(blocks), dim3(256), 0, st, store, seg, n_seg, runs_total, a, sc.splats, sc.slot_of, sc.counts);
-        else hipLaunchKernelGGL(k_render_setup_run<false>, dim3(blocks), dim3(256), 0, st, store, seg, n_seg, runs_total, a, sc.splats, sc.slot_of, sc.counts);
+    if (rt.n_seg > 0 && rt.total > 0) {
+        if (eigen33) hipLaunchKernelGGL(k_render_setup_run<true>, dim3(run_blocks(rt.total)), dim3(256), 0, st, store, rt, a, sc.splats, sc.slot_of, sc.counts);
+        else hipLaunchKernelGGL(k_render_setup_run<false>, dim3(run_blocks(rt.total)), dim3(256), 0, st, store, rt, a, sc.splats, sc.slot_of, sc.counts);
     }
-    const int tiles = (n_upper + kCloudTile - 1) / kCloudTile;
-    if (tiles == 0) {
-        const hipError_t e = hipMemsetAsync(total, 0, sizeof(int32_t), st);
-        if (e != hipSuccess) return e;
-    } else {
-        hipLaunchKernelGGL(k_cloud_count, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, tile_cnt);
-        hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, tile_cnt, tiles, total);
-        if (eigen33) hipLaunchKernelGGL(k_render_setup_map<true>, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, (const int32_t *)tile_cnt, runs_total, a, sc.splats, sc.slot_of, sc.counts);
-        else hipLaunchKernelGGL(k_render_setup_map<false>, dim3(tiles), dim3(256), 0, st, rec, n_ptr, n_upper, select, (const int32_t *)tile_cnt, runs_total, a, sc.splats, sc.slot_of, sc.counts);
+    const hipError_t e = launch_map_offsets(mp, st);
+    if (e != hipSuccess) return e;
+    if (map_tiles(mp) > 0) {
+        if (eigen33) hipLaunchKernelGGL(k_render_setup_map<true>, dim3(map_tiles(mp)), dim3(256), 0, st, mp, rt.total, a, sc.splats, sc.slot_of, sc.counts);
+        else hipLaunchKernelGGL(k_render_setup_map<false>, dim3(map_tiles(mp)), dim3(256), 0, st, mp, rt.total, a, sc.splats, sc.slot_of, sc.counts);
     }
     RenderImage im;
     im.keys = sc.keys;

@@ -18,7 +18,8 @@
 //                   SurfelMap::fuse_map refill + swap-with-last, SM.cpp:1077-1109
 //   k_warp          warp_{active,inactive}_surfels_cpu_kernel          SM.cpp:681-789
 //   k_mark_key / k_scan_marks / k_extract_marked   move_add_surfels removal, SM.cpp:1476-1497
-//   k_cloud_*       publish_{active,inactive,all,neighbor,raw}_pointcloud   SM.cpp:1115-1151, 1283-1454 (dsm_k_cloud.h)
+//   k_cloud_*       publish_{active,inactive,all,neighbor,raw}_pointcloud   SM.cpp:1115-1151, 1283-1454 (dsm_k_cloud.h; the walk of
+//                   the surfel sequence that cloud, mesh, render and grid share: dsm_k_sequence.h)
 //   k_mesh_*        save_mesh's hexagons as vertex and index buffers               SM.cpp:1176-1280 (dsm_k_mesh.h)
 //   k_render_*      the map as depth / index / normal / intensity images from any pose (no reference counterpart; dsm_k_render.h)
 //   k_grid_*        the map as a world-aligned occupancy voxel grid with inflation and a cell list (no reference counterpart; dsm_k_grid.h)
