@@ -80,6 +80,8 @@ ABI_SYMBOLS = (
     "dsm_carve_params_init", "dsm_grid_carve", "dsm_grid_classify",
     # connected components of a bit set of the grid: frontier clusters, obstacles as objects
     "dsm_grid_components",
+    # viewpoint gain: candidate camera poses scored against the grid
+    "dsm_grid_view",
 )
 
 # dsm_frame_upload_u16 & co.: how a uint16 depth value becomes metres (include/dsm.h)
@@ -245,6 +247,34 @@ COMPONENT_DTYPE = np.dtype([("root", np.int32), ("count", np.int32), ("sum", np.
                             ("tag", np.int32), ("reserved", np.int32)])
 assert COMPONENT_DTYPE.itemsize == 64
 CONNECT_FACES, CONNECT_ALL = 6, 26
+
+# dsm_view_score (include/dsm.h): 32 bytes, one per pose of dsm_grid_view
+VIEW_SCORE_DTYPE = np.dtype([("in_view", np.int32), ("visible", np.int32), ("unknown", np.int32), ("free", np.int32), ("occupied", np.int32),
+                             ("target", np.int32), ("reserved", np.int32, (2,))])
+assert VIEW_SCORE_DTYPE.itemsize == 32
+VIEW_MAX_REACH, VIEW_MAX_POSES, VIEW_UNKNOWN_BLOCKS = 4096, 4096, 1
+VIEW_TARGET_NONE, VIEW_TARGET_FRONTIER = 0, 1
+_VIEW_TARGETS = {None: VIEW_TARGET_NONE, "none": VIEW_TARGET_NONE, "frontier": VIEW_TARGET_FRONTIER}
+
+
+class _ViewQuery(C.Structure):  # dsm_view_query of include/dsm_surfel_map.h
+    _fields_ = [("struct_size", C.c_uint32), ("camera", _RenderCamera), ("flags", C.c_uint32), ("target", C.c_int32)]
+
+
+def view_query(camera, target="frontier", flags=0) -> _ViewQuery:
+    """a dsm_view_query: the view camera (anything render_camera takes), target "frontier" / "none" / None (or a VIEW_TARGET_* code,
+    passed on for the library to judge), flags VIEW_UNKNOWN_BLOCKS or 0"""
+    q = _ViewQuery()
+    q.struct_size = C.sizeof(_ViewQuery)
+    q.camera = render_camera(camera)
+    q.flags = int(flags)
+    q.target = _VIEW_TARGETS[target] if (target is None or isinstance(target, str)) else int(target)
+    return q
+
+
+def view_poses(poses) -> np.ndarray:
+    """4x4 cam -> world matrices (row-major numpy, as everywhere here; one or many) as [n, 16] column-major floats"""
+    return np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1, 16)
 
 
 class _AlignParams(C.Structure):
@@ -518,6 +548,7 @@ def load_library():
     lib.dsm_grid_carve.argtypes = [_vp, C.POINTER(_GridSpec), C.POINTER(_CarveParams), C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]
     lib.dsm_grid_classify.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_SpacePlanes), _vp]
     lib.dsm_grid_components.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_ComponentPlanes), _vp, _vp]
+    lib.dsm_grid_view.argtypes = [_vp, C.POINTER(_GridSpec), C.POINTER(_RenderCamera), C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
     lib.dsm_align_params_init.argtypes = [C.POINTER(_AlignParams)]
     lib.dsm_align_params_init.restype = None
     lib.dsm_align_equations.argtypes = [_vp, C.c_int, C.POINTER(_RenderCamera), _vp, _vp, _vp, C.POINTER(_AlignParams), _vp, _vp]
@@ -989,6 +1020,27 @@ class FusionFunctions:
             self.grid_components(dims, d_src.data_ptr(), connectivity, min_count, tag_ptr, table_ptr=d_table.data_ptr(), table_cap=n)
             table = d_table.cpu().numpy().view(COMPONENT_DTYPE).copy()
         return table, n_all, (d_label.cpu().numpy() if labels else None)
+
+    # ---- viewpoint gain ---------------------------------------------------------------------------------
+    def grid_view(self, spec, camera, poses, occupied_ptr, free_ptr, target_ptr=None, flags=0, poses_inv=None, visible_ptr=None, scores_ptr=None,
+                  scores=True):
+        """dsm_grid_view: what a camera (anything render_camera takes) at each of `poses` (4x4 cam -> world, row-major numpy; poses_inv
+        their inverses or None = the library's closed form) would see of the grid `spec`, given the bit sets [nz, ny, wx] at the device
+        pointers occupied_ptr and free_ptr and optionally target_ptr.  flags: VIEW_UNKNOWN_BLOCKS or 0.  visible_ptr: a device plane
+        uint32 [n_poses, nz, ny, wx] for the visible set of every pose, or None.  Returns the scores as a VIEW_SCORE_DTYPE array
+        [n_poses]; with scores_ptr (device memory, 32 bytes a pose) they are written there and None is returned; scores=False asks
+        for the planes alone."""
+        cam = render_camera(camera)
+        ps = view_poses(poses)
+        pi = None if poses_inv is None else view_poses(poses_inv)
+        if pi is not None and len(pi) != len(ps):
+            raise ValueError("one inverse per pose")
+        out = np.zeros(len(ps), VIEW_SCORE_DTYPE) if (scores and not scores_ptr) else None
+        dst = _vp(scores_ptr) if scores_ptr else (_ptr(out) if out is not None and len(out) else None)
+        self._check(self._lib.dsm_grid_view(self._h, C.byref(spec), C.byref(cam), int(flags), len(ps), _ptr(ps) if len(ps) else None,
+                                            None if pi is None else _ptr(pi), _vp(occupied_ptr) if occupied_ptr else None, _vp(free_ptr) if free_ptr else None,
+                                            _vp(target_ptr) if target_ptr else None, dst, 1 if scores_ptr else 0, _vp(visible_ptr) if visible_ptr else None))
+        return out
 
     # ---- a depth frame against the rendered map -----------------------------------------------------
     def align_equations(self, slot, model_cam, model_depth_ptr, model_normal_ptr, T, params=None):

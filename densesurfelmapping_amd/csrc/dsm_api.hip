@@ -254,7 +254,8 @@ struct dsm_handle {
     int store_cap = 0, store_n = 0;
     // the scratch of the synchronous calls, each DevScratch grown by scratch_grow with the headroom its call site states:
     //   store_tmp      tail copy of dsm_store_erase, argument blocks of the warps
-    //   pub            the words of the map products (PubWords): counts, tile counts of the compaction, the run table
+    //   pub            the words of the map products (PubWords): counts, tile counts of the compaction, the run table; the frames of
+    //                  dsm_grid_carve; the pose table and the scores of dsm_grid_view
     //   pub_out        what a product writes on its way to a HOST destination: points, vertices, indices, render planes
     //   render_keys    dsm_render_compose: the key plane with the ray tables behind it
     //   render_splats  ... its splat records with the number -> record table behind them
@@ -272,6 +273,8 @@ struct dsm_handle {
     // dsm_grid_carve: the frames' matrices and plane offsets as built on the host, until the call has synchronised (the device copy
     // lies in `pub`)
     std::vector<CarveFrame> carve_frames;
+    // dsm_grid_view: the poses' table as built on the host, until the call has synchronised
+    std::vector<ViewPose> view_poses;
     int64_t *h_align_sums = nullptr;
     // drop-in calls (dsm_fuse_map / dsm_fuse_initialize_map): page-locked staging owned by the handle
     uint8_t *pin_frame = nullptr; // one frame, image then depth, rows at the frame slots' pitch
@@ -1870,7 +1873,8 @@ int pub_reserve(dsm_handle *h, size_t ints, size_t points) {
 
 // The layout of dsm_handle::pub, known here alone ("scratch of the map products"): the map part's count @0, the
 // splat counters @16, the cell list's total @32, then from @64 the tile counts of the map part's compaction with the run table
-// behind them.  dsm_grid_carve keeps a 64-bit count at `total` and its frames at `tiles`.
+// behind them.  dsm_grid_carve keeps a 64-bit count at `total` and its frames at `tiles`; dsm_grid_view its pose table at `tiles`
+// and the scores behind it.
 struct PubWords {
     int32_t *total, *counts, *cells_total, *tiles, *seg;
 };
@@ -1918,6 +1922,17 @@ int plane_scratch_grow(dsm_handle *h, DevScratch &s, size_t bytes) {
 int pose_finite(dsm_handle *h, const float *pose16, const float *pose_inv16) {
     for (int k = 0; k < 16; k++)
         if (!std::isfinite(pose16[k]) || (pose_inv16 && !std::isfinite(pose_inv16[k]))) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
+    return DSM_OK;
+}
+
+// what dsm_render_compose and dsm_grid_view ask of a dsm_render_camera
+int render_camera_check(dsm_handle *h, const dsm_render_camera &c) {
+    if (c.width < 1 || c.width > kRenderMaxSide || c.height < 1 || c.height > kRenderMaxSide)
+        return fail(h, DSM_E_INVALID, "render image %d x %d outside 1..%d", c.width, c.height, kRenderMaxSide);
+    if (!(c.fx > 0.0f && c.fy > 0.0f) || !std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy))
+        return fail(h, DSM_E_INVALID, "render camera fx %g fy %g cx %g cy %g", (double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy);
+    if (!(c.near_dist > 0.0f) || !(c.near_dist < c.far_dist) || !std::isfinite(c.far_dist))
+        return fail(h, DSM_E_INVALID, "render depth range (%g, %g)", (double)c.near_dist, (double)c.far_dist);
     return DSM_OK;
 }
 
@@ -2037,12 +2052,7 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
     if (!camera || !pose16 || !planes) return fail(h, DSM_E_INVALID, "null camera, pose or planes");
     if (flags & ~(uint32_t)DSM_RENDER_CULL_BACKFACES) return fail(h, DSM_E_INVALID, "render flags 0x%x", flags);
     const dsm_render_camera &c = *camera;
-    if (c.width < 1 || c.width > kRenderMaxSide || c.height < 1 || c.height > kRenderMaxSide)
-        return fail(h, DSM_E_INVALID, "render image %d x %d outside 1..%d", c.width, c.height, kRenderMaxSide);
-    if (!(c.fx > 0.0f && c.fy > 0.0f) || !std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy))
-        return fail(h, DSM_E_INVALID, "render camera fx %g fy %g cx %g cy %g", (double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy);
-    if (!(c.near_dist > 0.0f) || !(c.near_dist < c.far_dist) || !std::isfinite(c.far_dist))
-        return fail(h, DSM_E_INVALID, "render depth range (%g, %g)", (double)c.near_dist, (double)c.far_dist);
+    if (int bad = render_camera_check(h, c)) return bad;
     if (!planes->depth && !planes->index && !planes->normal && !planes->intensity) return fail(h, DSM_E_INVALID, "no output plane");
     int rc = pose_finite(h, pose16, pose_inv16);
     if (rc) return rc;
@@ -2462,6 +2472,75 @@ int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const v
     const int32_t cells = h->h_scalars[7];
     *n_frontier = cells;
     if (p.cells && cells > p.cells_cap) return fail(h, DSM_E_CAPACITY, "%d frontier cells, room for %d", cells, p.cells_cap);
+    return DSM_OK;
+}
+
+// ------------------------------------------------------------------ viewpoint gain (dsm_k_view.h)
+
+static_assert(sizeof(dsm_view_score) == 32 && sizeof(ViewCounts) == sizeof(dsm_view_score), "dsm_view_score is 32 bytes, ViewCounts its image");
+static_assert(kViewMaxReach == DSM_VIEW_MAX_REACH && kViewMaxPoses == DSM_VIEW_MAX_POSES && kViewUnknownBlocks == DSM_VIEW_UNKNOWN_BLOCKS, "dsm_view.h and dsm.h agree");
+
+int dsm_grid_view(dsm_handle *h, const dsm_grid_spec *spec, const dsm_render_camera *camera, uint32_t flags, int32_t n_poses, const float *poses16,
+                  const float *poses_inv16, const void *occupied_device, const void *free_device, const void *target_device, dsm_view_score *scores,
+                  int scores_on_device, uint32_t *visible_device) {
+    if (!h) return DSM_E_INVALID;
+    if (!spec || !camera || !poses16) return fail(h, DSM_E_INVALID, "grid view: null spec, camera or poses");
+    if (!occupied_device || !free_device) return fail(h, DSM_E_INVALID, "grid view: null source");
+    if (!scores && !visible_device) return fail(h, DSM_E_INVALID, "grid view: no output");
+    if (flags & ~(uint32_t)DSM_VIEW_UNKNOWN_BLOCKS) return fail(h, DSM_E_INVALID, "view flags 0x%x", flags);
+    if ((((uintptr_t)occupied_device | (uintptr_t)free_device | (uintptr_t)target_device | (uintptr_t)visible_device) & 3) ||
+        (scores_on_device && ((uintptr_t)scores & 3)))
+        return fail(h, DSM_E_INVALID, "grid view: a device pointer is not 4-byte aligned");
+    if (int bad = grid_spec_check(h, spec)) return bad;
+    if (int bad = render_camera_check(h, *camera)) return bad;
+    if (n_poses < 1 || n_poses > kViewMaxPoses) return fail(h, DSM_E_INVALID, "view of %d poses, outside 1..%d", n_poses, kViewMaxPoses);
+    const int32_t dims[3] = {spec->nx, spec->ny, spec->nz};
+    for (int f = 0; f < n_poses; f++) {
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(poses16[16 * f + k]) || (poses_inv16 && !std::isfinite(poses_inv16[16 * f + k])))
+                return fail(h, DSM_E_INVALID, "view pose %d: pose entry %d is not finite", f, k);
+        for (int a = 0; a < 3; a++)
+            if (!view_reach_ok(comp_from_voxel(poses16[16 * f + 12 + a], spec->origin[a], spec->voxel), dims[a]))
+                return fail(h, DSM_E_INVALID, "view pose %d: the camera's voxel is more than %d voxels outside the grid along axis %d", f, kViewMaxReach, a);
+    }
+    const size_t n_words = (size_t)((spec->nx + 31) / 32) * spec->ny * spec->nz, set_bytes = n_words * sizeof(uint32_t);
+    const size_t score_bytes = sizeof(dsm_view_score) * (size_t)n_poses, vis_bytes = set_bytes * (size_t)n_poses;
+    for (const void *src : {occupied_device, free_device, target_device}) {
+        if (!src) continue;
+        if ((visible_device && ranges_overlap(visible_device, vis_bytes, src, set_bytes)) || (scores && scores_on_device && ranges_overlap(scores, score_bytes, src, set_bytes)))
+            return fail(h, DSM_E_INVALID, "grid view: an output overlaps a source");
+    }
+    if (visible_device && scores && scores_on_device && ranges_overlap(visible_device, vis_bytes, scores, score_bytes))
+        return fail(h, DSM_E_INVALID, "grid view: the two outputs overlap");
+    int rc = bind_device(h);
+    if (rc) return rc;
+    // scratch (dsm_handle::pub, behind its 64 words, as dsm_grid_carve keeps its frames): the pose table, then the scores
+    constexpr size_t kPoseInts = sizeof(ViewPose) / sizeof(int32_t), kScoreInts = sizeof(ViewCounts) / sizeof(int32_t);
+    if ((rc = pub_reserve(h, 64 + (kPoseInts + kScoreInts) * (size_t)n_poses, 0))) return rc;
+    if ((rc = pub_order_dst(h))) return rc;
+    h->view_poses.resize((size_t)n_poses);
+    for (int f = 0; f < n_poses; f++) {
+        ViewPose &vp = h->view_poses[(size_t)f];
+        if (poses_inv16) memcpy(vp.inv, poses_inv16 + 16 * f, sizeof vp.inv);
+        else inverse4<float>(poses16 + 16 * f, vp.inv);
+        for (int a = 0; a < 3; a++) vp.a[a] = comp_from_voxel(poses16[16 * f + 12 + a], spec->origin[a], spec->voxel);
+        vp.reserved = 0;
+    }
+    ViewPose *d_poses = (ViewPose *)pub_words(h, 0).tiles;
+    ViewCounts *d_scores = (ViewCounts *)(d_poses + n_poses);
+    HIP_TRY(h, hipMemcpyAsync(d_poses, h->view_poses.data(), sizeof(ViewPose) * (size_t)n_poses, hipMemcpyHostToDevice, h->stream));
+    CarveConst c;
+    memset(&c, 0, sizeof c);
+    for (int a = 0; a < 3; a++) c.origin[a] = spec->origin[a];
+    c.voxel = spec->voxel;
+    c.w = camera->width; c.h = camera->height; c.pitch = camera->width;
+    c.fx = camera->fx; c.fy = camera->fy; c.cx = camera->cx; c.cy = camera->cy;
+    c.near_d = camera->near_dist; c.far_d = camera->far_dist;
+    const hipError_t e = launch_view(d_poses, n_poses, c, flags, spec->nx, spec->ny, spec->nz, (const uint32_t *)occupied_device, (const uint32_t *)free_device,
+                                     (const uint32_t *)target_device, d_scores, visible_device, h->stream);
+    if (e != hipSuccess) return fail(h, DSM_E_HIP, "view launch: %s", hipGetErrorString(e));
+    if (scores) HIP_TRY(h, hipMemcpyAsync(scores, d_scores, score_bytes, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return DSM_OK;
 }
 

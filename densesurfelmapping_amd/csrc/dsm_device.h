@@ -293,6 +293,13 @@ hipError_t launch_carve(const float *depth_base, const CarveFrame *frames, int n
 hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, int nx, int ny, int nz, uint8_t *state, uint32_t *known_free, uint32_t *frontier,
                         int32_t *cells, int cells_cap, int32_t *cell_tiles, int32_t *cells_total, hipStream_t st);
 
+// ---- candidate camera poses scored against the grid (dsm_k_view.h; the definition is in dsm_view.h)
+// occ / fre / target: [nz][ny][wx] words, pad bits ignored; target may be null.  c: the grid's origin and voxel and the view camera,
+// everything but inv, which is the pose's.  scores: [n_poses], cleared on `st` first; visible: [n_poses][nz][ny][wx] or null, pad
+// bits written 0.
+hipError_t launch_view(const ViewPose *poses, int n_poses, const CarveConst &c, uint32_t flags, int nx, int ny, int nz, const uint32_t *occ,
+                       const uint32_t *fre, const uint32_t *target, ViewCounts *scores, uint32_t *visible, hipStream_t st);
+
 // ---- connected components of a bit set (dsm_k_components.h; the definition is in dsm_components.h)
 // src: [nz][ny][wx] words, pad bits ignored; at most kFieldMaxVoxels voxels.  label: [voxels], always written (the caller's plane or
 // scratch); work: [voxels] of scratch; root_bits / keep_bits: [words]; root_tiles / keep_tiles: (words + 255) / 256 ints each.  table

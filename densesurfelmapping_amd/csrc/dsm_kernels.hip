@@ -25,6 +25,7 @@
 //   k_grid_*        the map as a world-aligned occupancy voxel grid with inflation and a cell list (no reference counterpart; dsm_k_grid.h)
 //   k_field_*       the truncated Euclidean distance field of the grid's bit set (no reference counterpart; dsm_k_field.h)
 //   k_carve / k_space_*   free space carved out of the grid by depth frames; the three-state map and its frontier (no reference counterpart; dsm_k_carve.h)
+//   k_view          candidate camera poses scored against the grid: in view, line of sight, counts by state (no reference counterpart; dsm_k_view.h)
 //   k_comp_*        connected components of a bit set of the grid: labels by lowest index, a table of sizes, centroids and boxes (no reference counterpart; dsm_k_components.h)
 //   k_align         the normal equations of a depth frame against the rendered map (no reference counterpart; dsm_k_align.h)
 //
@@ -50,6 +51,7 @@
 #include "dsm_k_grid.h"
 #include "dsm_k_field.h"
 #include "dsm_k_carve.h"
+#include "dsm_k_view.h"
 #include "dsm_k_components.h"
 #include "dsm_k_align.h"
 

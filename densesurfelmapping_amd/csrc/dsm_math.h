@@ -1038,3 +1038,5 @@ DSM_HD int chunk_of(int n, int i) {
 #include "dsm_align.h"
 // free space carved out of the grid by depth frames: carve_voxel, and the three states of a voxel
 #include "dsm_carve.h"
+// viewpoint gain: what a camera at a candidate pose would see of the grid -- in view, the line to the voxel, blockers
+#include "dsm_view.h"

@@ -1,5 +1,6 @@
 // dsm_surfel_map_space.cpp -- the node's free and unknown space (include/dsm_surfel_map.h: dsm_surfel_map_set_free_space,
-// _free_space*, _space*, _carve_last) over the engine's dsm_grid_carve and dsm_grid_classify.  The accumulator is a bit set in
+// _free_space*, _space*, _carve_last, _frontier_clusters*, _view_gain*) over the engine's dsm_grid_carve, dsm_grid_classify,
+// dsm_grid_components and dsm_grid_view.  The accumulator is a bit set in
 // device memory that this file owns; dsm_surfel_map.cpp reaches it through the function pointers of struct dsm_surfel_map
 // (on_carve at the fuse site, on_warped after a warp, release_space at destruction), all null until dsm_surfel_map_set_free_space
 // installs them.  The per-fuse carve is the SYNCHRONISING dsm_grid_carve: it is enqueued behind the fuse on the engine's stream and
@@ -251,6 +252,41 @@ int frontier_clusters(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, 
     return DSM_OK;
 }
 
+// dsm_surfel_map_view_gain: classify as space() does, then score the poses against the two sets (and the frontier)
+int view_gain(dsm_surfel_map *m, int kind, const dsm_view_query *q, int32_t n_poses, const float *poses16, dsm_view_score *scores, uint32_t *visible,
+              int on_device) {
+    if (!m || !q) return DSM_E_INVALID;
+    int rc = DSM_OK;
+    Space *s = ready(m, &rc);
+    if (!s) return rc;
+    if (q->struct_size != sizeof(dsm_view_query)) return space_fail(m, DSM_E_INVALID, "dsm_view_query struct_size %u, not %zu", q->struct_size, sizeof(dsm_view_query));
+    if (q->target != DSM_VIEW_TARGET_NONE && q->target != DSM_VIEW_TARGET_FRONTIER) return space_fail(m, DSM_E_INVALID, "view gain: target %d", q->target);
+    if (!scores && !visible) return space_fail(m, DSM_E_INVALID, "view gain: no output");
+    if (!poses16 || n_poses < 1 || n_poses > DSM_VIEW_MAX_POSES) return space_fail(m, DSM_E_INVALID, "view gain: %d poses, outside 1..%d, or none given", n_poses, DSM_VIEW_MAX_POSES);
+    if ((rc = compose_occupied(m, s, kind, "view gain", nullptr))) return rc;
+    const int nx = s->spec.nx, ny = s->spec.ny, nz = s->spec.nz;
+    const bool frontier = q->target == DSM_VIEW_TARGET_FRONTIER, stage = visible && !on_device;
+    const size_t set_bytes = s->n_words * sizeof(uint32_t);
+    // device staging, each part from a 256-byte boundary: the frontier, then the visible planes on their way to host memory
+    size_t at = 0;
+    const auto take = [&](bool here, size_t bytes) { const size_t was = at; if (here) at += (bytes + 255) & ~(size_t)255; return was; };
+    const size_t at_fr = take(frontier, set_bytes);
+    const size_t at_vis = take(stage, set_bytes * (size_t)n_poses);
+    if ((rc = tmp_reserve(m, s, at))) return rc;
+    uint32_t *d_frontier = frontier ? (uint32_t *)(s->d_tmp + at_fr) : nullptr;
+    if (frontier) {
+        const dsm_space_planes sp = {nullptr, nullptr, d_frontier, nullptr, 0};
+        int32_t nf = 0;
+        rc = dsm_grid_classify(m->engine, nx, ny, nz, s->d_occ, s->d_free, &sp, &nf);
+        if (rc) return space_fail(m, rc, "dsm_grid_classify: %s", dsm_last_error(m->engine));
+    }
+    uint32_t *d_visible = stage ? (uint32_t *)(s->d_tmp + at_vis) : visible;
+    rc = dsm_grid_view(m->engine, &s->spec, &q->camera, q->flags, n_poses, poses16, nullptr, s->d_occ, s->d_free, d_frontier, scores, on_device, d_visible);
+    if (rc) return space_fail(m, rc, "dsm_grid_view: %s", dsm_last_error(m->engine));
+    if (stage) SPACE_HIP(m, hipMemcpy(visible, d_visible, set_bytes * (size_t)n_poses, hipMemcpyDeviceToHost));
+    return DSM_OK;
+}
+
 int free_space(dsm_surfel_map *m, void *dst, int on_device, int64_t *n_free) {
     if (!m || !dst) return DSM_E_INVALID;
     int rc = DSM_OK;
@@ -327,6 +363,35 @@ int dsm_surfel_map_frontier_clusters(dsm_surfel_map *m, int kind, const dsm_fron
 int dsm_surfel_map_frontier_clusters_device(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, dsm_component *table_device, int32_t table_cap,
                                             int32_t *label_device, int32_t *n_clusters, int32_t *n_all, int32_t *from_root) {
     return frontier_clusters(m, kind, q, table_device, table_cap, label_device, 1, n_clusters, n_all, from_root);
+}
+
+void dsm_view_query_init(const dsm_surfel_map *m, dsm_view_query *q) {
+    if (!q) return;
+    memset(q, 0, sizeof *q);
+    q->struct_size = (uint32_t)sizeof(dsm_view_query);
+    q->target = DSM_VIEW_TARGET_FRONTIER;
+    if (!m) return;
+    dsm_carve_params p;
+    if (m->space) p = ((const Space *)m->space)->params;
+    else dsm_carve_params_init(&p);
+    q->camera.width = m->cfg.cam_width;
+    q->camera.height = m->cfg.cam_height;
+    q->camera.fx = m->cfg.cam_fx;
+    q->camera.fy = m->cfg.cam_fy;
+    q->camera.cx = m->cfg.cam_cx;
+    q->camera.cy = m->cfg.cam_cy;
+    q->camera.near_dist = p.near_dist;
+    q->camera.far_dist = p.far_dist;
+}
+
+int dsm_surfel_map_view_gain(dsm_surfel_map *m, int kind, const dsm_view_query *q, int32_t n_poses, const float *poses16, dsm_view_score *scores,
+                             uint32_t *visible) {
+    return view_gain(m, kind, q, n_poses, poses16, scores, visible, 0);
+}
+
+int dsm_surfel_map_view_gain_device(dsm_surfel_map *m, int kind, const dsm_view_query *q, int32_t n_poses, const float *poses16,
+                                    dsm_view_score *scores_device, uint32_t *visible_device) {
+    return view_gain(m, kind, q, n_poses, poses16, scores_device, visible_device, 1);
 }
 
 int dsm_surfel_map_carve_last(dsm_surfel_map *m, const dsm_grid_spec *spec, const dsm_carve_params *params, uint32_t flags, void *free_device) {

@@ -99,12 +99,26 @@ def read_log(path):
     return cam, dfp, events()
 
 
+def yaw_poses(pose, n) -> np.ndarray:
+    """`pose` (4x4 cam -> world) turned about its own camera y axis by 2 pi k / n, k = 0 .. n - 1: float32 [n, 4, 4], made in double and
+    rounded once (poses are inputs: what is scored is exactly what is returned)"""
+    T = np.asarray(pose, np.float64).reshape(4, 4)
+    out = np.zeros((int(n), 4, 4), np.float32)
+    for k in range(int(n)):
+        a = 2.0 * np.pi * k / int(n)
+        R = np.eye(4)
+        R[0, 0], R[0, 2], R[2, 0], R[2, 2] = np.cos(a), np.sin(a), -np.sin(a), np.cos(a)
+        out[k] = (T @ R).astype(np.float32)
+    return out
+
+
 EIGEN_PRODUCTS = {"3.2": 0, "3.3": api.DSM_FLAG_EIGEN33_PRODUCTS}  # --eigen-products -> SurfelMap(engine_flags=...)
 
 
 def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, eigen_products="3.2", save_mesh_binary=None, render=None, align=None,
            save_grid=None, grid_voxel=0.1, grid_dims=(64, 64, 32), grid_inflate=0, save_field=None, field_max_dist=16,
-           save_space=None, carve_near=None, carve_far=None, carve_margin=None, save_frontier_clusters=None, cluster_min=1, cluster_connect=26):
+           save_space=None, carve_near=None, carve_far=None, carve_margin=None, save_frontier_clusters=None, cluster_min=1, cluster_connect=26,
+           save_view_gain=None, view_yaws=8):
     """Feed a log to a SurfelMap on the GPU; returns a summary dict.  align = a cloud kind: after every fused frame that frame is
     aligned against the surfels of that kind at the pose it was fused with (SurfelMap.align_last, the library's defaults) and a
     JSON line says how it went; the poses fed to the map are not changed.  save_grid: the whole map as an occupancy grid of grid_dims voxels
@@ -113,12 +127,15 @@ def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, e
     replay, in a grid of grid_dims voxels around the first pose of the log, and the three-state map and its frontier are written as an
     .npz (SurfelMap.set_free_space / space).  save_frontier_clusters: with the same accumulator, the frontier as clusters of
     cluster_connect-connectivity with at least cluster_min voxels, and whether each can be reached through known-free space from the
-    pose of the last fuse (SurfelMap.frontier_clusters), as an .npz."""
+    pose of the last fuse (SurfelMap.frontier_clusters), as an .npz.  save_view_gain: with the same accumulator, view_yaws candidate
+    poses -- the pose of the last fuse turned about its own camera y axis by 2 pi k / view_yaws (yaw_poses) -- scored by what the
+    node's camera would see from each (SurfelMap.view_gain, the frontier as target), as an .npz with the poses, the scores and the
+    camera."""
     from . import surfel_map
     cam, dfp, events = read_log(path)
     node = surfel_map.SurfelMap(cam, drift_free_poses=dfp, device=device, surfel_capacity=surfel_capacity,
                                 engine_flags=EIGEN_PRODUCTS[eigen_products])
-    if save_space or save_frontier_clusters:  # (the node turns the SLAM frame so that the first camera sits at the world's origin: the grid lies around it)
+    if save_space or save_frontier_clusters or save_view_gain:  # (the node turns the SLAM frame so that the first camera sits at the world's origin: the grid lies around it)
         carve = {k: v for k, v in (("near_dist", carve_near), ("far_dist", carve_far), ("margin", carve_margin)) if v is not None}
         node.set_free_space(api.grid_spec_around((0.0, 0.0, 0.0), grid_voxel, tuple(grid_dims)), carve)
     n = 0
@@ -173,6 +190,15 @@ def replay(path, save_cloud=None, save_mesh=None, device=0, surfel_capacity=0, e
                  n_all=np.int32(fc["n_all"]), origin_point=np.asarray(origin, np.float32))
         out["frontier_clusters"], out["frontier_clusters_all"] = int(len(fc["table"])), int(fc["n_all"])
         out["frontier_clusters_reachable"] = int((fc["table"]["tag"] == fc["from_root"]).sum()) if fc["from_root"] >= 0 else 0
+    if save_view_gain:  # the last pose turned about its own y axis: what would the node's camera see from each?
+        poses = yaw_poses(node.last_pose(), view_yaws)
+        q = node.view_query()
+        scores = node.view_gain(poses, "all", camera=q.camera, target="frontier")
+        g = node._space_spec
+        np.savez(save_view_gain, origin=np.array(g.origin[:], np.float32), voxel=np.float32(g.voxel), dims=np.array([g.nx, g.ny, g.nz], np.int32),
+                 poses=poses, scores=scores, camera=np.array([getattr(q.camera, f[0]) for f in api._RenderCamera._fields_], np.float64))
+        out["view_poses"], out["view_best_yaw"] = int(len(poses)), int(np.argmax(scores["unknown"]))
+        out["view_unknown_seen"] = [int(v) for v in scores["unknown"]]
     node.close()
     return out
 
@@ -204,6 +230,10 @@ def main():
                     "frontier as connected clusters: origin, voxel, dims, table (root, count, sum, lo, hi, tag), from_root, n_all; from = the pose of the last fuse")
     ap.add_argument("--cluster-min", type=int, default=1, metavar="N", help="clusters of fewer voxels are left out (default 1)")
     ap.add_argument("--cluster-connect", type=int, default=26, choices=(6, 26), help="connectivity of the clusters (default 26)")
+    ap.add_argument("--save-view-gain", metavar="PATH.npz", help="with the accumulator of --save-space (the same --grid-* and --carve-* options): --view-yaws "
+                    "poses, the last fused pose turned about its own camera y axis, scored by what the node's camera would see: origin, voxel, dims, poses, "
+                    "scores (in_view, visible, unknown, free, occupied, target = frontier), camera")
+    ap.add_argument("--view-yaws", type=int, default=8, metavar="N", help="number of yaw poses of --save-view-gain, 1..4096 (default 8)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--eigen-products", choices=sorted(EIGEN_PRODUCTS), default="3.2",
                     help="product order of the Eigen the reference to match was built against (3.3: Eigen 3.3 / 3.4)")
@@ -217,7 +247,8 @@ def main():
                             save_grid=args.save_grid, grid_voxel=args.grid_voxel, grid_dims=args.grid_dims, grid_inflate=args.grid_inflate,
                             save_field=args.save_field, field_max_dist=args.field_max_dist,
                             save_space=args.save_space, carve_near=args.carve_near, carve_far=args.carve_far, carve_margin=args.carve_margin,
-                            save_frontier_clusters=args.save_frontier_clusters, cluster_min=args.cluster_min, cluster_connect=args.cluster_connect)))
+                            save_frontier_clusters=args.save_frontier_clusters, cluster_min=args.cluster_min, cluster_connect=args.cluster_connect,
+                            save_view_gain=args.save_view_gain, view_yaws=args.view_yaws)))
 
 
 if __name__ == "__main__":

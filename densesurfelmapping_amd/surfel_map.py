@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "dsm_surfel_map_set_free_space", "dsm_surfel_map_free_space_resets", "dsm_surfel_map_free_space", "dsm_surfel_map_free_space_device",
     "dsm_surfel_map_space", "dsm_surfel_map_space_device", "dsm_surfel_map_carve_last",
     "dsm_frontier_query_init", "dsm_surfel_map_frontier_clusters", "dsm_surfel_map_frontier_clusters_device",
+    "dsm_view_query_init", "dsm_surfel_map_view_gain", "dsm_surfel_map_view_gain_device",
 )
 
 # dsm_cloud_kind of include/dsm_surfel_map.h
@@ -131,6 +132,11 @@ def _bind(lib):
             lib.dsm_frontier_query_init.restype = None
             for name in ("dsm_surfel_map_frontier_clusters", "dsm_surfel_map_frontier_clusters_device"):
                 getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(_FrontierQuery), _vp, C.c_int32, _vp, _vp, _vp, _vp]
+        if hasattr(lib, "dsm_surfel_map_view_gain"):  # (nor viewpoint gain)
+            lib.dsm_view_query_init.argtypes = [_vp, C.POINTER(api._ViewQuery)]
+            lib.dsm_view_query_init.restype = None
+            for name in ("dsm_surfel_map_view_gain", "dsm_surfel_map_view_gain_device"):
+                getattr(lib, name).argtypes = [_vp, C.c_int, C.POINTER(api._ViewQuery), C.c_int32, _vp, _vp, _vp]
         lib._dsm_surfel_map_bound = True
     return lib
 
@@ -380,6 +386,37 @@ class SurfelMap:
             out["cells"] = out["cells"][: nf.value]
         out["n_surfels"], out["n_frontier"], out["spec"] = n.value, nf.value, spec
         return out
+
+    def view_query(self):
+        """dsm_view_query_init: the node's own camera with the accumulator's carve range, flags 0, the frontier as target"""
+        q = api._ViewQuery()
+        self._lib.dsm_view_query_init(self._h, C.byref(q))
+        return q
+
+    def view_gain(self, poses, kind="all", camera=None, target="frontier", flags=0, visible=False, dst_ptrs=None):
+        """Candidate poses (4x4 cam -> world, row-major numpy; one or many) scored against space(kind): what a camera there would see
+        (dsm_grid_view of include/dsm.h).  camera: anything api.render_camera takes, None = view_query()'s; target "frontier" / "none";
+        flags api.VIEW_UNKNOWN_BLOCKS or 0.  Returns the scores as an api.VIEW_SCORE_DTYPE array [n_poses], or, with visible=True,
+        (scores, the visible sets uint32 [n_poses, nz, ny, wx]).  With dst_ptrs = {"scores": device pointer, "visible": device pointer}
+        (either may be missing) both are written on the device and None is returned."""
+        k = self._kind(kind)
+        q = self.view_query()
+        if camera is not None:
+            q.camera = api.render_camera(camera)
+        q.flags = int(flags)
+        q.target = api._VIEW_TARGETS[target] if (target is None or isinstance(target, str)) else int(target)
+        ps = api.view_poses(poses)
+        if dst_ptrs is not None:
+            s, v = dst_ptrs.get("scores"), dst_ptrs.get("visible")
+            self._check(self._lib.dsm_surfel_map_view_gain_device(self._h, k, C.byref(q), len(ps), _ptr(ps) if len(ps) else None, _vp(s) if s else None,
+                                                                  _vp(v) if v else None))
+            return None
+        spec = getattr(self, "_space_spec", None)
+        scores = np.zeros(len(ps), api.VIEW_SCORE_DTYPE)
+        vis = np.zeros((len(ps),) + api.grid_shapes(spec)[1], np.uint32) if visible and spec is not None else None
+        self._check(self._lib.dsm_surfel_map_view_gain(self._h, k, C.byref(q), len(ps), _ptr(ps) if len(ps) else None, _ptr(scores) if len(ps) else None,
+                                                       None if vis is None else _ptr(vis)))
+        return (scores, vis) if visible else scores
 
     def frontier_clusters(self, kind="all", connectivity=26, min_count=1, origin=None, labels=False, dst_ptrs=None, table_cap=None):
         """The frontier of space(kind) as connected clusters (connectivity 6 or 26) of at least min_count voxels.  origin: a world

@@ -236,8 +236,8 @@ int dsm_surfel_map_carve_last(dsm_surfel_map *m, const dsm_grid_spec *spec, cons
  * NULL) = all of them.  DSM_E_STATE before dsm_surfel_map_set_free_space or before the first fuse; DSM_E_INVALID for a wrong
  * struct_size, a kind dsm_surfel_map_space refuses, and what dsm_grid_components refuses (more than 2^26 voxels among it).  The map
  * and the accumulator are not changed.  Synchronises.
- * Not provided: clusters tracked across calls, viewpoints or goal poses, and labelling across a loop-closure reset (the
- * accumulator starts again there, and so do the clusters). */
+ * Not provided: clusters tracked across calls, pose search (dsm_surfel_map_view_gain below scores the poses a caller proposes),
+ * and labelling across a loop-closure reset (the accumulator starts again there, and so do the clusters). */
 typedef struct dsm_frontier_query {
     uint32_t struct_size; /* sizeof(dsm_frontier_query) */
     int32_t connectivity; /* of the frontier clusters: DSM_CONNECT_FACES or DSM_CONNECT_ALL */
@@ -252,6 +252,32 @@ int dsm_surfel_map_frontier_clusters(dsm_surfel_map *m, int kind, const dsm_fron
 /* the same with table (8-byte aligned) and label (4-byte aligned) in device memory of the node's GPU */
 int dsm_surfel_map_frontier_clusters_device(dsm_surfel_map *m, int kind, const dsm_frontier_query *q, dsm_component *table_device, int32_t table_cap,
                                             int32_t *label_device, int32_t *n_clusters, int32_t *n_all, int32_t *from_root);
+
+/* ---- viewpoint gain: what a camera at a candidate pose would see of the node's space (dsm_grid_view of dsm.h, where it is defined) ----
+ * The occupied set of `kind` in the accumulator's grid is composed and classified against the accumulated free set exactly as
+ * dsm_surfel_map_space does it; then the n_poses poses (cam -> world, 16 column-major floats each; the closed-form inverse is
+ * taken) are scored by dsm_grid_view with q->camera and q->flags (DSM_VIEW_*), the frontier being the target set with
+ * DSM_VIEW_TARGET_FRONTIER.  scores: [n_poses], visible: [n_poses][nz][ny][wx] words (may be NULL), in host memory; one of them
+ * may be NULL, not both.  DSM_E_STATE before dsm_surfel_map_set_free_space or before the first fuse; DSM_E_INVALID for a wrong
+ * struct_size, an unknown target, a kind dsm_surfel_map_space refuses, and what dsm_grid_view refuses.  After a loop-closure
+ * reset the accumulator is empty, so everything but the occupied set is unknown again.  The map and the accumulator are not
+ * changed.  Synchronises. */
+#define DSM_VIEW_TARGET_NONE 0
+#define DSM_VIEW_TARGET_FRONTIER 1
+typedef struct dsm_view_query {
+    uint32_t struct_size;     /* sizeof(dsm_view_query) */
+    dsm_render_camera camera; /* the view camera: any size and intrinsics, as for dsm_grid_view */
+    uint32_t flags;           /* DSM_VIEW_UNKNOWN_BLOCKS or 0 */
+    int32_t target;           /* DSM_VIEW_TARGET_NONE or DSM_VIEW_TARGET_FRONTIER */
+} dsm_view_query;
+/* The node's own image size and intrinsics with the accumulator's carve range (dsm_carve_params_init's range while free space is
+ * switched off); flags 0; the frontier as target.  m NULL: the camera is left zero for the caller to fill. */
+void dsm_view_query_init(const dsm_surfel_map *m, dsm_view_query *q);
+int dsm_surfel_map_view_gain(dsm_surfel_map *m, int kind, const dsm_view_query *q, int32_t n_poses, const float *poses16, dsm_view_score *scores,
+                             uint32_t *visible);
+/* the same with scores and visible (4-byte aligned) in device memory of the node's GPU */
+int dsm_surfel_map_view_gain_device(dsm_surfel_map *m, int kind, const dsm_view_query *q, int32_t n_poses, const float *poses16,
+                                    dsm_view_score *scores_device, uint32_t *visible_device);
 
 /* ---- the latest frame against the map (dsm_align_frame of dsm.h, where the alignment is defined) ----
  * Aligns the depth frame of the latest fuse, still in its engine slot, against the surfel set of `kind` with the rules and runs of

@@ -319,6 +319,20 @@ class SurfelMap {
                                  int32_t *n_clusters, int32_t *n_all = nullptr, int32_t *from_root = nullptr) {
         return check(dsm_surfel_map_frontier_clusters_device(m_, kind, &query, table_device, table_cap, label_device, n_clusters, n_all, from_root));
     }
+    // candidate poses (cam -> world, 16 column-major floats each) scored against space(kind): dsm_grid_view of dsm.h; view_query()
+    // gives the query's defaults (the node's camera with the carve range, the frontier as target); scores and visible in host memory
+    dsm_view_query view_query() const {
+        dsm_view_query q;
+        dsm_view_query_init(m_, &q);
+        return q;
+    }
+    int view_gain(dsm_cloud_kind kind, const dsm_view_query &query, int32_t n_poses, const float *poses16, dsm_view_score *scores, uint32_t *visible = nullptr) {
+        return check(dsm_surfel_map_view_gain(m_, kind, &query, n_poses, poses16, scores, visible));
+    }
+    int view_gain_device(dsm_cloud_kind kind, const dsm_view_query &query, int32_t n_poses, const float *poses16, dsm_view_score *scores_device,
+                         uint32_t *visible_device = nullptr) {
+        return check(dsm_surfel_map_view_gain_device(m_, kind, &query, n_poses, poses16, scores_device, visible_device));
+    }
     // one carve of the latest fused frame into a caller's set in device memory: the stateless counterpart
     int carve_last(const dsm_grid_spec &spec, const dsm_carve_params *params, uint32_t flags, void *free_device) {
         return check(dsm_surfel_map_carve_last(m_, &spec, params, flags, free_device));
