@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_NAME = "libdsm_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ["dsm_kernels.hip", "dsm_api.hip", "dsm_surfel_map.cpp", "dsm_surfel_map_clouds.cpp", "dsm_surfel_map_mesh.cpp", "dsm_surfel_map_render.cpp", "dsm_surfel_map_grid.cpp", "dsm_surfel_map_field.cpp", "dsm_surfel_map_space.cpp", "dsm_surfel_map_align.cpp"]
-HEADERS = ["dsm_math.h", "dsm_align.h", "dsm_carve.h", "dsm_view.h", "dsm_device.h", "dsm_k_common.h", "dsm_k_superpixel.h", "dsm_k_planes.h", "dsm_k_map.h", "dsm_k_sequence.h", "dsm_k_cloud.h", "dsm_k_mesh.h", "dsm_k_render.h", "dsm_k_grid.h", "dsm_k_field.h", "dsm_k_carve.h", "dsm_k_view.h", "dsm_k_components.h", "dsm_components.h", "dsm_k_align.h", "dsm_mesh_ply.h", "dsm_surfel_map_node.h", "dsm_frame_format.h", "dsm_frame_copy.h", "dsm_ranges.h", "dsm_frame_rings.h", os.path.join("..", "..", "include", "dsm.h"),
+HEADERS = ["dsm_math.h", "dsm_align.h", "dsm_carve.h", "dsm_view.h", "dsm_device.h", "dsm_k_common.h", "dsm_k_superpixel.h", "dsm_k_planes.h", "dsm_k_map.h", "dsm_k_sequence.h", "dsm_k_cloud.h", "dsm_k_mesh.h", "dsm_k_render.h", "dsm_k_grid.h", "dsm_k_field.h", "dsm_k_carve.h", "dsm_k_view.h", "dsm_k_components.h", "dsm_components.h", "dsm_k_align.h", "dsm_mesh_ply.h", "dsm_surfel_map_node.h", "dsm_frame_format.h", "dsm_frame_copy.h", "dsm_ranges.h", "dsm_grid_shape.h", "dsm_frame_rings.h", os.path.join("..", "..", "include", "dsm.h"),
            os.path.join("..", "..", "include", "dsm_surfel_map.h")]
 
 

@@ -144,6 +144,22 @@ struct DevScratch {
     template <typename T> T *as() const { return (T *)p; }
 };
 
+// the slots of dsm_handle::h_scalars: what comes down from the device lands here
+enum HostScalar {
+    kHsLocal = 0,         // n_local: the size of the map
+    kHsNew = 1,           // n_new of the latest frame
+    kHsStatus = 2,        // the device's status word
+    kHsScratch = 3,       // a count on its way up or down (set_map, the holes of an extract)
+    kHsDeltaGroups = 4,   // the groups of a drop-in delta
+    kHsSequence = 5,      // the map part's share of a product's sequence
+    kHsGridCells = 6,     // the cells of dsm_grid_compose
+    kHsFrontierCells = 7, // the frontier cells of dsm_grid_classify
+    kHsCarved = 8,        // the free voxels of dsm_grid_carve: 64 bits, slots 8 and 9
+    kHsKept = 10,         // the components dsm_grid_components kept
+    kHsComponents = 11,   // all of its components, read with kHsKept in one copy
+    kHsDevice = 64        // [64, 128): the device's scalar block as it came (the offsets of dsm_handle::d_scalars)
+};
+
 struct dsm_handle {
     uint64_t generation = 0; // unique per dsm_create: a batch remembers it, so that a new handle at a destroyed handle's address is not taken for the old one
     dsm_config cfg;
@@ -179,7 +195,7 @@ struct dsm_handle {
     std::vector<void *> allocs; // every hipMalloc of this handle
     std::vector<hipGraphExec_t> retired; // graphs replaced while possibly in flight (map_grows): destroyed at the next synchronisation point
     FrameParams *h_params = nullptr; // pinned staging ring
-    int32_t *h_scalars = nullptr;    // pinned: [0] n_local, [1] n_new, [2] status, [3] scratch, [4] delta groups, [5] cloud size, [6] grid cells, [7] frontier cells, [8..9] carved voxels (64 bits), [10] components kept, [11] components; [64..127] the device's scalar block as it came
+    int32_t *h_scalars = nullptr;    // pinned: 128 ints, the slots of HostScalar
     int32_t *d_scalars = nullptr;    // the device's scalar block (64 ints: n_local @8, n_local_next @16, n_new @24, n_holes @32, status @48, delta count @56)
     FrameParams *d_params = nullptr;
     uint8_t *d_stage_img = nullptr; // one tightly packed frame on its way into a pitched slot
@@ -873,8 +889,8 @@ hipError_t add_stage_times(dsm_stage_times *out, hipEvent_t *ev, dsm_handle *con
     out->event_overhead_ms += (double)cal * n;
     out->frames += n;
     for (int j = 0; j < n; j++) {
-        out->sum_new += hs[j]->h_scalars[1];
-        out->sum_local += hs[j]->h_scalars[0];
+        out->sum_new += hs[j]->h_scalars[kHsNew];
+        out->sum_local += hs[j]->h_scalars[kHsLocal];
     }
     return hipSuccess;
 }
@@ -953,7 +969,7 @@ int dropin_delta_begin(dsm_handle *h) {
     HIP_TRY(h, hipMemsetAsync(h->d_scalars + 56, 0, 4, h->stream));
     return DSM_OK;
 }
-// m_bound: the largest size the map can have now.  Synchronises; on return h_scalars[0..2] hold the frame's counts.
+// m_bound: the largest size the map can have now.  Synchronises; on return h_scalars[kHsLocal .. kHsStatus] hold the frame's counts.
 int dropin_delta_end(dsm_handle *h, dsm_surfel *local, int32_t cap_local, int m_bound, int *m_out) {
     const hipError_t e = launch_delta_pack(h->hc, h->d_delta, h->d_delta_idx, h->d_scalars + 56, h->delta_cap_groups, m_bound, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "delta pack: %s", hipGetErrorString(e));
@@ -971,7 +987,7 @@ int dropin_delta_end(dsm_handle *h, dsm_surfel *local, int32_t cap_local, int m_
         std::chrono::steady_clock::time_point t;
         ~PatchTimer() { h->dropin_us[3] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t).count(); }
     } patch_timer{h, t_w1};
-    const int m = h->h_scalars[0], n_grp = h->h_scalars[4];
+    const int m = h->h_scalars[kHsLocal], n_grp = h->h_scalars[kHsDeltaGroups];
     *m_out = m;
     h->dropin_calls++;
     h->dropin_last_groups = n_grp;
@@ -1039,16 +1055,16 @@ int dropin_map_in(dsm_handle *h, const dsm_surfel *local, int n) {
         par_copy(h, h->pin_map, local, bytes);
         HIP_TRY(h, hipMemcpyAsync(h->hc.local, h->pin_map, bytes, hipMemcpyHostToDevice, h->stream));
     }
-    h->h_scalars[3] = n;
-    HIP_TRY(h, hipMemcpyAsync(h->hc.n_local, &h->h_scalars[3], 4, hipMemcpyHostToDevice, h->stream));
+    h->h_scalars[kHsScratch] = n;
+    HIP_TRY(h, hipMemcpyAsync(h->hc.n_local, &h->h_scalars[kHsScratch], 4, hipMemcpyHostToDevice, h->stream));
     h->map_upper = n;
     h->map_valid = true;
     return DSM_OK;
 }
 
 int check_status(dsm_handle *h) {
-    // caller has synchronised and copied status into h_scalars[2]
-    const int st = h->h_scalars[2];
+    // caller has synchronised and copied status into h_scalars[kHsStatus]
+    const int st = h->h_scalars[kHsStatus];
     if (st) (void)hipMemsetAsync(h->hc.status, 0, 4, h->stream); // report once, then start clean
     if (st & kStatusCapacity) return fail(h, DSM_E_CAPACITY, "resident surfel capacity %d exceeded", h->hc.cap);
     if (st & kStatusBadLabels) return fail(h, DSM_E_INVALID, "a superpixel had more member pixels than its 15x15 reach allows: the label image was not produced by the assignment stage (dsm_debug_set_label_buffer?)");
@@ -1058,15 +1074,15 @@ int check_status(dsm_handle *h) {
 
 int sync_and_fetch_counts(dsm_handle *h) {
     // ONE transfer for the whole scalar block (a call into the runtime costs more than the 256 bytes)
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[64], h->d_scalars, 64 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[kHsDevice], h->d_scalars, 64 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     retire_graphs(h); // (they ran on this stream)
-    h->h_scalars[0] = h->h_scalars[64 + 8];
-    h->h_scalars[1] = h->h_scalars[64 + 24];
-    h->h_scalars[2] = h->h_scalars[64 + 48];
-    h->h_scalars[4] = h->h_scalars[64 + 56];
+    h->h_scalars[kHsLocal] = h->h_scalars[kHsDevice + 8];
+    h->h_scalars[kHsNew] = h->h_scalars[kHsDevice + 24];
+    h->h_scalars[kHsStatus] = h->h_scalars[kHsDevice + 48];
+    h->h_scalars[kHsDeltaGroups] = h->h_scalars[kHsDevice + 56];
     h->frames_done = h->frames_submitted;
-    h->map_upper = h->h_scalars[0];
+    h->map_upper = h->h_scalars[kHsLocal];
     h->fence_pending = false; // nothing is in flight any more
     std::fill(h->slot_used.begin(), h->slot_used.end(), 0);
     return check_status(h);
@@ -1123,8 +1139,8 @@ int set_map(dsm_handle *h, const dsm_surfel *src, int n) {
     if (n > h->hc.cap) return fail(h, DSM_E_CAPACITY, "%d surfels exceed the handle's capacity %d", n, h->hc.cap);
     if (n) HIP_TRY(h, hipMemcpyAsync(h->hc.local, src, (size_t)n * sizeof(dsm_surfel), hipMemcpyHostToDevice, h->stream));
     // the 4-byte count goes through a pinned scratch word; wait so that it can be reused at once
-    h->h_scalars[3] = n;
-    HIP_TRY(h, hipMemcpyAsync(h->hc.n_local, &h->h_scalars[3], 4, hipMemcpyHostToDevice, h->stream));
+    h->h_scalars[kHsScratch] = n;
+    HIP_TRY(h, hipMemcpyAsync(h->hc.n_local, &h->h_scalars[kHsScratch], 4, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->frames_done = h->frames_submitted;
     h->map_upper = n;
@@ -1545,7 +1561,7 @@ int dsm_fuse_initialize_map_inv(dsm_handle *h, int reference_frame_index, const 
     HIP_TRY(h, hipMemcpyAsync(h->pin_map + n_local, h->hc.fresh, (size_t)S * sizeof(dsm_surfel), hipMemcpyDeviceToHost, h->stream));
     int m = 0;
     if ((rc = dropin_delta_end(h, local, n_local, n_local, &m))) { h->shadow_n = -1; return rc; }
-    const int k = h->h_scalars[1];
+    const int k = h->h_scalars[kHsNew];
     *n_new = k;
     h->shadow_n = n_local; // no compaction: the device map keeps its size
     if (k > new_cap) return fail(h, DSM_E_CAPACITY, "%d new surfels exceed new_cap %d", k, new_cap);
@@ -1590,12 +1606,12 @@ int dsm_fuse_map_inv(dsm_handle *h, int reference_frame_index, const uint8_t *im
         // the caller's array is too small (not the handle's capacity, reported by check_status before m is known: *n_local stays):
         // the size it needs; nothing of it was written, the shadow is not trusted again
         if (rc == DSM_E_CAPACITY && m > cap) {
-            *n_new = h->h_scalars[1];
+            *n_new = h->h_scalars[kHsNew];
             *n_local = m;
         }
         return rc;
     }
-    *n_new = h->h_scalars[1];
+    *n_new = h->h_scalars[kHsNew];
     *n_local = m;
     h->shadow_n = m;
     return DSM_OK;
@@ -1615,7 +1631,7 @@ int dsm_map_size(dsm_handle *h, int32_t *n) {
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    *n = h->h_scalars[0];
+    *n = h->h_scalars[kHsLocal];
     return DSM_OK;
 }
 
@@ -1630,7 +1646,7 @@ int dsm_map_download(dsm_handle *h, dsm_surfel *out, int32_t cap, int32_t *n) {
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    const int m = h->h_scalars[0];
+    const int m = h->h_scalars[kHsLocal];
     *n = m;
     if (m > cap) return fail(h, DSM_E_CAPACITY, "%d surfels exceed the caller's capacity %d", m, cap);
     if (m && !out) return fail(h, DSM_E_INVALID, "null output");
@@ -1643,7 +1659,7 @@ int dsm_map_copy_to_device(dsm_handle *h, void *dst_device, int32_t cap, int32_t
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    const int m = h->h_scalars[0];
+    const int m = h->h_scalars[kHsLocal];
     *n = m;
     if (m > cap) return fail(h, DSM_E_CAPACITY, "%d surfels exceed the caller's capacity %d", m, cap);
     if (m && !dst_device) return fail(h, DSM_E_INVALID, "null output");
@@ -1696,15 +1712,15 @@ int dsm_map_extract(dsm_handle *h, int32_t key, dsm_surfel *out, int32_t cap, in
     if (rc) return rc;
     // staged in `fresh`'s neighbour: the holes array doubles as the index list, the copy goes to a scratch buffer
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    const int m = h->h_scalars[0];
+    const int m = h->h_scalars[kHsLocal];
     dsm_surfel *d_out = nullptr;
     HIP_TRY(h, hipMalloc((void **)&d_out, sizeof(dsm_surfel) * (size_t)(m > 0 ? m : 1)));
     hipError_t e = launch_extract(h->hc, key, d_out, m, m, h->stream);
     int32_t k = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h->h_scalars[3], h->hc.n_holes, 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h->h_scalars[kHsScratch], h->hc.n_holes, 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) {
-        k = h->h_scalars[3];
+        k = h->h_scalars[kHsScratch];
         if (k > cap) { (void)hipFree(d_out); *n = k; return fail(h, DSM_E_CAPACITY, "%d surfels of keyframe %d exceed cap %d (map left with them deleted)", k, key, cap); }
         if (k) e = hipMemcpy(out, d_out, sizeof(dsm_surfel) * (size_t)k, hipMemcpyDeviceToHost);
     }
@@ -1721,7 +1737,7 @@ int dsm_map_append(dsm_handle *h, const dsm_surfel *surfels, int32_t n) {
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    const int m = h->h_scalars[0];
+    const int m = h->h_scalars[kHsLocal];
     if (m + n > h->hc.cap) return fail(h, DSM_E_CAPACITY, "%d + %d surfels exceed the handle's capacity %d", m, n, h->hc.cap);
     if (n) HIP_TRY(h, hipMemcpy(h->hc.local + m, surfels, sizeof(dsm_surfel) * (size_t)n, hipMemcpyHostToDevice));
     hipError_t e = launch_append_count(h->hc, n, h->stream);
@@ -1772,12 +1788,12 @@ int dsm_store_deactivate(dsm_handle *h, int32_t key, int32_t *begin, int32_t *n)
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    const int m = h->h_scalars[0];
+    const int m = h->h_scalars[kHsLocal];
     hipError_t e = launch_mark(h->hc, key, m, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h->h_scalars[3], h->hc.n_holes, 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h->h_scalars[kHsScratch], h->hc.n_holes, 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "deactivate: %s", hipGetErrorString(e));
-    const int k = h->h_scalars[3];
+    const int k = h->h_scalars[kHsScratch];
     if ((rc = store_reserve(h, h->store_n + k))) return rc;
     if (k) {
         e = launch_extract_marked(h->hc, h->d_store + h->store_n, k, h->d_cloud + h->store_n, h->stream);
@@ -1797,7 +1813,7 @@ int dsm_store_activate(dsm_handle *h, int32_t begin, int32_t n) {
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    const int m = h->h_scalars[0];
+    const int m = h->h_scalars[kHsLocal];
     if (m + n > h->hc.cap) return fail(h, DSM_E_CAPACITY, "%d + %d surfels exceed the handle's capacity %d", m, n, h->hc.cap);
     if (n) HIP_TRY(h, hipMemcpyAsync(h->hc.local + m, h->d_store + begin, sizeof(dsm_surfel) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
     hipError_t e = launch_append_count(h->hc, n, h->stream);
@@ -1919,10 +1935,21 @@ int plane_scratch_grow(dsm_handle *h, DevScratch &s, size_t bytes) {
     return scratch_grow(h, s, bytes, bytes + bytes / 4 + 256);
 }
 
-int pose_finite(dsm_handle *h, const float *pose16, const float *pose_inv16) {
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(pose16[k]) || (pose_inv16 && !std::isfinite(pose_inv16[k]))) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
+// every entry of pose f of a table, and of its inverse where the table has inverses, is finite.  each: what the text calls a pose of
+// the table ("carve frame"), null for a call with one pose
+int pose_finite(dsm_handle *h, const char *each, int f, const float *poses16, const float *inv16) {
+    for (int k = 0; k < 16; k++) {
+        if (std::isfinite(poses16[16 * f + k]) && (!inv16 || std::isfinite(inv16[16 * f + k]))) continue;
+        if (!each) return fail(h, DSM_E_INVALID, "pose entry %d is not finite", k);
+        return fail(h, DSM_E_INVALID, "%s %d: pose entry %d is not finite", each, f, k);
+    }
     return DSM_OK;
+}
+
+// world -> camera of pose f of a table: the caller's inverse where the table has inverses, else the closed form
+void pose_inverse(int f, const float *poses16, const float *inv16, float *out16) {
+    if (inv16) memcpy(out16, inv16 + 16 * f, 16 * sizeof(float));
+    else inverse4<float>(poses16 + 16 * f, out16);
 }
 
 // what dsm_render_compose and dsm_grid_view ask of a dsm_render_camera
@@ -1954,9 +1981,9 @@ int pub_sequence(dsm_handle *h, const MapSequence &sq, size_t points, PubSequenc
 
 // the length of the sequence behind a product's launches: the map part's count comes down, the stream is through
 int pub_sequence_length(dsm_handle *h, const PubSequence &ps, int64_t &total) {
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[5], ps.mp.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[kHsSequence], ps.mp.total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    total = (int64_t)h->h_scalars[5] + ps.rt.total;
+    total = (int64_t)h->h_scalars[kHsSequence] + ps.rt.total;
     return DSM_OK;
 }
 
@@ -2054,7 +2081,7 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
     const dsm_render_camera &c = *camera;
     if (int bad = render_camera_check(h, c)) return bad;
     if (!planes->depth && !planes->index && !planes->normal && !planes->intensity) return fail(h, DSM_E_INVALID, "no output plane");
-    int rc = pose_finite(h, pose16, pose_inv16);
+    int rc = pose_finite(h, nullptr, 0, pose16, pose_inv16);
     if (rc) return rc;
     MapSequence sq;
     if ((rc = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX - 4096, sq))) return rc;
@@ -2071,8 +2098,7 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
     if ((rc = scratch_grow(h, h->render_splats, n_seq * splat_rec, (n_seq + n_seq / 4 + 64) * splat_rec))) return rc;
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
     float pose_inv[16];
-    if (pose_inv16) memcpy(pose_inv, pose_inv16, sizeof pose_inv);
-    else inverse4<float>(pose16, pose_inv);
+    pose_inverse(0, pose16, pose_inv16, pose_inv);
     RenderCam cam;
     cam.w = w; cam.h = hh;
     cam.fx = c.fx; cam.fy = c.fy; cam.cx = c.cx; cam.cy = c.cy;
@@ -2120,15 +2146,8 @@ int dsm_render_compose(dsm_handle *h, int select, int32_t n_segments, const int3
 
 namespace {
 
-// a dimension < 1 or more than `limit` voxels: false
-bool grid_dims_ok(int32_t nx, int32_t ny, int32_t nz, int64_t limit = kGridMaxVoxels) {
-    if (nx < 1 || ny < 1 || nz < 1) return false;
-    const int64_t xy = (int64_t)nx * ny; // < 2^62
-    return xy <= limit && xy * nz <= limit;
-}
-
-// what dsm_grid_compose and dsm_field_compose ask of a dsm_grid_spec
-int grid_spec_check(dsm_handle *h, const dsm_grid_spec *spec) {
+// what dsm_grid_compose, dsm_field_compose, dsm_grid_carve and dsm_grid_view ask of a dsm_grid_spec; d: its shape, once it is sound
+int grid_spec_check(dsm_handle *h, const dsm_grid_spec *spec, GridDims &d) {
     if (spec->struct_size != sizeof(dsm_grid_spec)) return fail(h, DSM_E_INVALID, "dsm_grid_spec struct_size %u, not %zu", spec->struct_size, sizeof(dsm_grid_spec));
     for (int a = 0; a < 3; a++)
         if (!std::isfinite(spec->origin[a])) return fail(h, DSM_E_INVALID, "grid origin %d is not finite", a);
@@ -2136,6 +2155,36 @@ int grid_spec_check(dsm_handle *h, const dsm_grid_spec *spec) {
     if (!grid_dims_ok(spec->nx, spec->ny, spec->nz))
         return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", spec->nx, spec->ny, spec->nz);
     if (spec->inflate < 0 || spec->inflate > kGridMaxInflate) return fail(h, DSM_E_INVALID, "grid inflate %d outside 0..%d", spec->inflate, kGridMaxInflate);
+    d = grid_dims(spec->nx, spec->ny, spec->nz);
+    return DSM_OK;
+}
+
+// what the calls on a caller's bit sets ask of their dimensions: at most 2^`log2_limit` voxels; d as above
+int grid_dims_check(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int log2_limit, GridDims &d) {
+    if (!grid_dims_ok(nx, ny, nz, (int64_t)1 << log2_limit))
+        return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^%d voxels", nx, ny, nz, log2_limit);
+    d = grid_dims(nx, ny, nz);
+    return DSM_OK;
+}
+static_assert(kGridMaxVoxels == (int64_t)1 << 28 && kFieldMaxVoxels == (int64_t)1 << 26, "the limits the texts name");
+
+// memory a caller handed over: a plane or a source, null where there is none
+struct Span {
+    const void *p;
+    size_t bytes;
+};
+// does a plane that is there share a byte with a source that is there?
+bool any_overlap(std::initializer_list<Span> planes, std::initializer_list<Span> sources) {
+    for (const Span &q : planes)
+        for (const Span &s : sources)
+            if (q.p && s.p && ranges_overlap(q.p, q.bytes, s.p, s.bytes)) return true;
+    return false;
+}
+
+// a count of the device (`bytes` of it) into h_scalars[slot]; the stream is through
+int count_down(dsm_handle *h, int slot, const void *d_count, size_t bytes) {
+    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[slot], d_count, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return DSM_OK;
 }
 
@@ -2164,7 +2213,8 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     if (!h || !n_surfels || !n_cells) return DSM_E_INVALID;
     if (!spec || !planes) return fail(h, DSM_E_INVALID, "null grid spec or planes");
     if (flags & ~(uint32_t)DSM_GRID_CELLS_OF_INFLATED) return fail(h, DSM_E_INVALID, "grid flags 0x%x", flags);
-    if (int bad = grid_spec_check(h, spec)) return bad;
+    GridDims d;
+    if (int bad = grid_spec_check(h, spec, d)) return bad;
     if (!planes->occupied && !planes->inflated && !planes->index && !planes->cells) return fail(h, DSM_E_INVALID, "no output plane");
     if (planes->cells && planes->cells_cap < 0) return fail(h, DSM_E_INVALID, "cells_cap %d", planes->cells_cap);
     if (dst_on_device && ((((uintptr_t)planes->occupied | (uintptr_t)planes->inflated | (uintptr_t)planes->index | (uintptr_t)planes->cells) & 3)))
@@ -2176,39 +2226,36 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     if (rc) return rc;
     const size_t n_seq = (size_t)sq.bound;
     if ((rc = bind_device(h))) return rc;
-    const int nx = spec->nx, ny = spec->ny, nz = spec->nz, wx = (nx + 31) / 32;
-    const size_t rows = (size_t)ny * nz, n_vox = rows * nx, n_words = rows * wx;
+    const size_t n_vox = (size_t)d.n_vox();
     const bool cells_of_inflated = (flags & DSM_GRID_CELLS_OF_INFLATED) != 0;
     const bool want_inflated = planes->inflated || (planes->cells && cells_of_inflated);
-    const size_t cells_cap = planes->cells ? ((size_t)planes->cells_cap < n_vox ? (size_t)planes->cells_cap : n_vox) : 0; // (no more cells than voxels)
+    const size_t cells_cap = planes->cells ? capped(planes->cells_cap, d.n_vox()) : 0;
     // what is not the caller's device memory lies in the handle's scratch, each part from a 16-byte boundary
-    const auto pad4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-    size_t words = 0;
-    const auto take = [&](bool here, size_t n) { const size_t at = words; if (here) words += pad4(n); return at; };
-    const size_t at_occ = take(!(dst_on_device && planes->occupied), n_words);
-    const size_t at_infl = take(want_inflated && !(dst_on_device && planes->inflated), n_words);
-    const size_t at_index = take(planes->index && !dst_on_device, n_vox);
-    const size_t at_cells = take(planes->cells && !dst_on_device, cells_cap);
-    const size_t at_tiles = take(planes->cells != nullptr, (n_words + 255) / 256);
+    ScratchPlan plan(16);
+    const size_t at_occ = plan.take(!(dst_on_device && planes->occupied), d.set_bytes());
+    const size_t at_infl = plan.take(want_inflated && !(dst_on_device && planes->inflated), d.set_bytes());
+    const size_t at_index = plan.take(planes->index && !dst_on_device, n_vox * sizeof(int32_t));
+    const size_t at_cells = plan.take(planes->cells && !dst_on_device, cells_cap * sizeof(int32_t));
+    const size_t at_tiles = plan.take(planes->cells != nullptr, (size_t)d.cell_tiles() * sizeof(int32_t));
     // (dsm_field_compose composes into dsm_handle::field: no grower reached from here may touch that buffer)
     if ((rc = scratch_grow(h, h->grid_splats, n_seq * sizeof(GridSplat), (n_seq + n_seq / 4 + 64) * sizeof(GridSplat)))) return rc;
-    if ((rc = plane_scratch_grow(h, h->grid_planes, words * sizeof(uint32_t)))) return rc;
+    if ((rc = plane_scratch_grow(h, h->grid_planes, plan.bytes()))) return rc;
     if (dst_on_device && (rc = pub_order_dst(h))) return rc;
     PubSequence ps;
     if ((rc = pub_sequence(h, sq, 0, ps))) return rc;
-    uint32_t *scratch = h->grid_planes.as<uint32_t>();
+    uint8_t *scratch = h->grid_planes.as<uint8_t>();
     GridSpec g;
     for (int a = 0; a < 3; a++) g.origin[a] = spec->origin[a];
     g.voxel = spec->voxel;
-    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
+    g.n[0] = d.nx; g.n[1] = d.ny; g.n[2] = d.nz;
     GridScratch sc;
     sc.splats = h->grid_splats.as<GridSplat>();
     sc.counts = ps.w.counts;
     sc.n_seq = (int32_t)n_seq;
     sc.cell_tiles = (int32_t *)(scratch + at_tiles);
     GridOut out;
-    out.occupied = dst_on_device && planes->occupied ? planes->occupied : scratch + at_occ;
-    out.inflated = !want_inflated ? nullptr : dst_on_device && planes->inflated ? planes->inflated : scratch + at_infl;
+    out.occupied = dst_on_device && planes->occupied ? planes->occupied : (uint32_t *)(scratch + at_occ);
+    out.inflated = !want_inflated ? nullptr : dst_on_device && planes->inflated ? planes->inflated : (uint32_t *)(scratch + at_infl);
     out.index = !planes->index ? nullptr : dst_on_device ? planes->index : (int32_t *)(scratch + at_index);
     out.cells = !planes->cells ? nullptr : dst_on_device ? planes->cells : (int32_t *)(scratch + at_cells);
     out.cells_cap = (int32_t)cells_cap;
@@ -2216,18 +2263,18 @@ int dsm_grid_compose(dsm_handle *h, int select, int32_t n_segments, const int32_
     out.cells_of_inflated = cells_of_inflated;
     const hipError_t e = launch_grid(h->d_store, ps.rt, ps.mp, g, spec->inflate, sc, out, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "grid launch: %s", hipGetErrorString(e));
-    h->h_scalars[6] = 0;
-    if (planes->cells) HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[6], ps.w.cells_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    h->h_scalars[kHsGridCells] = 0;
+    if (planes->cells) HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[kHsGridCells], ps.w.cells_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     int64_t total;
     if ((rc = pub_sequence_length(h, ps, total))) return rc;
     *n_surfels = (int32_t)total;
-    const int32_t cells = h->h_scalars[6];
+    const int32_t cells = h->h_scalars[kHsGridCells];
     *n_cells = cells;
     if (!dst_on_device) {
-        if (planes->occupied) HIP_TRY(h, hipMemcpy(planes->occupied, out.occupied, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (planes->inflated) HIP_TRY(h, hipMemcpy(planes->inflated, out.inflated, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (planes->occupied) HIP_TRY(h, hipMemcpy(planes->occupied, out.occupied, d.set_bytes(), hipMemcpyDeviceToHost));
+        if (planes->inflated) HIP_TRY(h, hipMemcpy(planes->inflated, out.inflated, d.set_bytes(), hipMemcpyDeviceToHost));
         if (planes->index) HIP_TRY(h, hipMemcpy(planes->index, out.index, n_vox * sizeof(int32_t), hipMemcpyDeviceToHost));
-        const size_t n_out = (size_t)cells < cells_cap ? (size_t)cells : cells_cap;
+        const size_t n_out = capped(cells, (int64_t)cells_cap);
         if (planes->cells && n_out) HIP_TRY(h, hipMemcpy(planes->cells, out.cells, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     if (planes->cells && cells > planes->cells_cap) return fail(h, DSM_E_CAPACITY, "%d cells, room for %d", cells, planes->cells_cap);
@@ -2238,14 +2285,14 @@ int dsm_grid_inflate(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t 
     if (!h) return DSM_E_INVALID;
     if (!src_device || !dst_device || src_device == dst_device) return fail(h, DSM_E_INVALID, "grid inflate: null source or destination, or the same");
     if ((((uintptr_t)src_device | (uintptr_t)dst_device) & 3)) return fail(h, DSM_E_INVALID, "grid inflate: a bit set not 4-byte aligned");
-    if (!grid_dims_ok(nx, ny, nz)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", nx, ny, nz);
-    const size_t set_bytes = (size_t)((nx + 31) / 32) * ny * nz * sizeof(uint32_t); // <= 2^30
-    if (ranges_overlap(src_device, set_bytes, dst_device, set_bytes)) return fail(h, DSM_E_INVALID, "grid inflate: source and destination overlap");
+    GridDims d;
+    if (int bad = grid_dims_check(h, nx, ny, nz, 28, d)) return bad;
+    if (any_overlap({{dst_device, d.set_bytes()}}, {{src_device, d.set_bytes()}})) return fail(h, DSM_E_INVALID, "grid inflate: source and destination overlap");
     if (radius < 0 || radius > kGridMaxInflate) return fail(h, DSM_E_INVALID, "grid inflate %d outside 0..%d", radius, kGridMaxInflate);
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = pub_order_dst(h))) return rc;
-    const hipError_t e = launch_grid_inflate((const uint32_t *)src_device, (uint32_t *)dst_device, nx, ny, nz, radius, h->stream);
+    const hipError_t e = launch_grid_inflate((const uint32_t *)src_device, (uint32_t *)dst_device, d, radius, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "grid inflate launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return DSM_OK;
@@ -2270,25 +2317,25 @@ const char *field_request_error(int32_t max_dist, float voxel, const dsm_field_p
 struct FieldLayout {
     size_t table, ox, mid, bits, dist2, nearest, distance, bytes;
 };
-FieldLayout field_layout(size_t n_vox, size_t n_words, bool with_bits, const dsm_field_planes *p, bool on_device) {
+FieldLayout field_layout(const GridDims &d, bool with_bits, const dsm_field_planes *p, bool on_device) {
+    const size_t n_vox = (size_t)d.n_vox();
+    ScratchPlan plan(256);
     FieldLayout l;
-    size_t at = 0;
-    const auto take = [&](bool here, size_t n) { const size_t was = at; if (here) at += (n + 255) & ~(size_t)255; return was; };
-    l.table = take(true, (size_t)(kFieldMaxDist * kFieldMaxDist + 1) * sizeof(float));
-    l.ox = take(true, n_vox);
-    l.mid = take(true, n_vox * sizeof(uint32_t));
-    l.bits = take(with_bits, n_words * sizeof(uint32_t));
-    l.dist2 = take(p->dist2 && !on_device, n_vox * sizeof(uint16_t));
-    l.nearest = take(p->nearest && !on_device, n_vox * sizeof(int32_t));
-    l.distance = take(p->distance && !on_device, n_vox * sizeof(float));
-    l.bytes = at;
+    l.table = plan.take(true, (size_t)(kFieldMaxDist * kFieldMaxDist + 1) * sizeof(float));
+    l.ox = plan.take(true, n_vox);
+    l.mid = plan.take(true, n_vox * sizeof(uint32_t));
+    l.bits = plan.take(with_bits, d.set_bytes());
+    l.dist2 = plan.take(p->dist2 && !on_device, n_vox * sizeof(uint16_t));
+    l.nearest = plan.take(p->nearest && !on_device, n_vox * sizeof(int32_t));
+    l.distance = plan.take(p->distance && !on_device, n_vox * sizeof(float));
+    l.bytes = plan.bytes();
     return l;
 }
 
 // the table, the three passes, the copies to host planes; synchronises.  The scratch is reserved for `l`.
-int field_run(dsm_handle *h, const uint32_t *bits, int nx, int ny, int nz, int r, float voxel, const dsm_field_planes *p, bool on_device, const FieldLayout &l) {
+int field_run(dsm_handle *h, const uint32_t *bits, const GridDims &d, int r, float voxel, const dsm_field_planes *p, bool on_device, const FieldLayout &l) {
     uint8_t *sc = h->field.as<uint8_t>();
-    const size_t n_vox = (size_t)nx * ny * nz;
+    const size_t n_vox = (size_t)d.n_vox();
     if (p->distance) {
         h->field_table.resize((size_t)(r * r + 1));
         for (int k = 0; k <= r * r; k++) h->field_table[(size_t)k] = field_table_entry(voxel, k);
@@ -2297,7 +2344,7 @@ int field_run(dsm_handle *h, const uint32_t *bits, int nx, int ny, int nz, int r
     uint16_t *dist2 = !p->dist2 ? nullptr : on_device ? p->dist2 : (uint16_t *)(sc + l.dist2);
     int32_t *nearest = !p->nearest ? nullptr : on_device ? p->nearest : (int32_t *)(sc + l.nearest);
     float *distance = !p->distance ? nullptr : on_device ? p->distance : (float *)(sc + l.distance);
-    const hipError_t e = launch_field(bits, nx, ny, nz, r, (const float *)(sc + l.table), (int8_t *)(sc + l.ox), (uint32_t *)(sc + l.mid), dist2, nearest, distance, h->stream);
+    const hipError_t e = launch_field(bits, d, r, (const float *)(sc + l.table), (int8_t *)(sc + l.ox), (uint32_t *)(sc + l.mid), dist2, nearest, distance, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "field launch: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (!on_device) {
@@ -2315,22 +2362,19 @@ int dsm_grid_distance(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32_t
     if (!h) return DSM_E_INVALID;
     if (!src_device || !planes_device) return fail(h, DSM_E_INVALID, "grid distance: null source or planes");
     if (((uintptr_t)src_device & 3)) return fail(h, DSM_E_INVALID, "grid distance: the bit set is not 4-byte aligned");
-    if (!grid_dims_ok(nx, ny, nz, kFieldMaxVoxels)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^26 voxels", nx, ny, nz);
+    GridDims d;
+    if (int bad = grid_dims_check(h, nx, ny, nz, 26, d)) return bad;
     if (const char *bad = field_request_error(max_dist, voxel, planes_device, true)) return fail(h, DSM_E_INVALID, "grid distance: %s", bad);
-    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
-    {
-        const void *const q[3] = {planes_device->dist2, planes_device->nearest, planes_device->distance};
-        const size_t elem[3] = {sizeof(uint16_t), sizeof(int32_t), sizeof(float)};
-        for (int k = 0; k < 3; k++)
-            if (q[k] && ranges_overlap(q[k], n_vox * elem[k], src_device, n_words * sizeof(uint32_t)))
-                return fail(h, DSM_E_INVALID, "grid distance: a plane overlaps the source");
-    }
+    const dsm_field_planes &p = *planes_device;
+    const size_t n_vox = (size_t)d.n_vox();
+    if (any_overlap({{p.dist2, n_vox * sizeof(uint16_t)}, {p.nearest, n_vox * sizeof(int32_t)}, {p.distance, n_vox * sizeof(float)}}, {{src_device, d.set_bytes()}}))
+        return fail(h, DSM_E_INVALID, "grid distance: a plane overlaps the source");
     int rc = bind_device(h);
     if (rc) return rc;
-    const FieldLayout l = field_layout(n_vox, n_words, false, planes_device, true);
+    const FieldLayout l = field_layout(d, false, planes_device, true);
     if ((rc = plane_scratch_grow(h, h->field, l.bytes))) return rc;
     if ((rc = pub_order_dst(h))) return rc;
-    return field_run(h, (const uint32_t *)src_device, nx, ny, nz, max_dist, voxel, planes_device, true, l);
+    return field_run(h, (const uint32_t *)src_device, d, max_dist, voxel, planes_device, true, l);
 }
 
 int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32_t *store_begin, const int32_t *store_count, const dsm_grid_spec *spec,
@@ -2338,9 +2382,9 @@ int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32
     if (!h || !n_surfels) return DSM_E_INVALID;
     if (!spec || !planes) return fail(h, DSM_E_INVALID, "null grid spec or field planes");
     if (flags) return fail(h, DSM_E_INVALID, "field flags 0x%x", flags);
-    if (int bad = grid_spec_check(h, spec)) return bad;
-    if (!grid_dims_ok(spec->nx, spec->ny, spec->nz, kFieldMaxVoxels))
-        return fail(h, DSM_E_INVALID, "field of %d x %d x %d: more than 2^26 voxels", spec->nx, spec->ny, spec->nz);
+    GridDims d;
+    if (int bad = grid_spec_check(h, spec, d)) return bad;
+    if (!grid_dims_ok(d.nx, d.ny, d.nz, kFieldMaxVoxels)) return fail(h, DSM_E_INVALID, "field of %d x %d x %d: more than 2^26 voxels", d.nx, d.ny, d.nz);
     if (const char *bad = field_request_error(max_dist, spec->voxel, planes, dst_on_device != 0)) return fail(h, DSM_E_INVALID, "field: %s", bad);
     {
         MapSequence sq; // the sequence is checked here, before the scratch grows
@@ -2348,9 +2392,7 @@ int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32
     }
     int rc = bind_device(h);
     if (rc) return rc;
-    const int nx = spec->nx, ny = spec->ny, nz = spec->nz;
-    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
-    const FieldLayout l = field_layout(n_vox, n_words, true, planes, dst_on_device != 0);
+    const FieldLayout l = field_layout(d, true, planes, dst_on_device != 0);
     if ((rc = plane_scratch_grow(h, h->field, l.bytes))) return rc;
     // the occupied set by dsm_grid_compose itself, into the scratch as a device destination: no grower reached from there touches
     // dsm_handle::field
@@ -2358,12 +2400,29 @@ int dsm_field_compose(dsm_handle *h, int select, int32_t n_segments, const int32
     const dsm_grid_planes occupied = {bits, nullptr, nullptr, nullptr, 0};
     int32_t n = 0, cells = 0;
     if ((rc = dsm_grid_compose(h, select, n_segments, store_begin, store_count, spec, 0, &occupied, 1, &n, &cells))) return rc;
-    if ((rc = field_run(h, bits, nx, ny, nz, max_dist, spec->voxel, planes, dst_on_device != 0, l))) return rc;
+    if ((rc = field_run(h, bits, d, max_dist, spec->voxel, planes, dst_on_device != 0, l))) return rc;
     *n_surfels = n;
     return DSM_OK;
 }
 
 // ------------------------------------------------------------------ free space, the three states, the frontier (dsm_k_carve.h)
+
+namespace {
+
+// what k_carve and k_view share: the grid's corner and voxel, a camera, its depth range.  inv is the frame's or the pose's; margin
+// and flags are dsm_grid_carve's
+CarveConst carve_const(const dsm_grid_spec *spec, int w, int h, int pitch, float fx, float fy, float cx, float cy, float near_d, float far_d) {
+    CarveConst c;
+    memset(&c, 0, sizeof c);
+    for (int a = 0; a < 3; a++) c.origin[a] = spec->origin[a];
+    c.voxel = spec->voxel;
+    c.w = w; c.h = h; c.pitch = pitch;
+    c.fx = fx; c.fy = fy; c.cx = cx; c.cy = cy;
+    c.near_d = near_d; c.far_d = far_d;
+    return c;
+}
+
+} // namespace
 
 void dsm_carve_params_init(dsm_carve_params *p) {
     if (!p) return;
@@ -2380,7 +2439,8 @@ int dsm_grid_carve(dsm_handle *h, const dsm_grid_spec *spec, const dsm_carve_par
     if (!spec || !params || !slots || !poses16) return fail(h, DSM_E_INVALID, "grid carve: null spec, params, slots or poses");
     if (!free_device || ((uintptr_t)free_device & 3)) return fail(h, DSM_E_INVALID, "grid carve: the free set is null or not 4-byte aligned");
     if (flags & ~(uint32_t)(DSM_CARVE_REPLACE | DSM_CARVE_TRUST_INFINITE)) return fail(h, DSM_E_INVALID, "carve flags 0x%x", flags);
-    if (int bad = grid_spec_check(h, spec)) return bad;
+    GridDims d;
+    if (int bad = grid_spec_check(h, spec, d)) return bad;
     if (params->struct_size != sizeof(dsm_carve_params))
         return fail(h, DSM_E_INVALID, "dsm_carve_params struct_size %u, not %zu", params->struct_size, sizeof(dsm_carve_params));
     if (!(params->near_dist > 0.0f) || !(params->near_dist < params->far_dist) || !std::isfinite(params->far_dist))
@@ -2389,9 +2449,7 @@ int dsm_grid_carve(dsm_handle *h, const dsm_grid_spec *spec, const dsm_carve_par
     if (n_frames < 1 || n_frames > kCarveMaxFrames) return fail(h, DSM_E_INVALID, "carve of %d frames, outside 1..%d", n_frames, kCarveMaxFrames);
     for (int f = 0; f < n_frames; f++) {
         if (slots[f] < 0 || slots[f] >= h->hc.n_slots) return fail(h, DSM_E_INVALID, "frame slot %d out of range [0,%d)", slots[f], h->hc.n_slots);
-        for (int k = 0; k < 16; k++)
-            if (!std::isfinite(poses16[16 * f + k]) || (poses_inv16 && !std::isfinite(poses_inv16[16 * f + k])))
-                return fail(h, DSM_E_INVALID, "carve frame %d: pose entry %d is not finite", f, k);
+        if (int bad = pose_finite(h, "carve frame", f, poses16, poses_inv16)) return bad;
     }
     int rc = bind_device(h);
     if (rc) return rc;
@@ -2407,29 +2465,21 @@ int dsm_grid_carve(dsm_handle *h, const dsm_grid_spec *spec, const dsm_carve_par
     h->carve_frames.resize((size_t)n_frames);
     for (int f = 0; f < n_frames; f++) {
         CarveFrame &cf = h->carve_frames[(size_t)f];
-        if (poses_inv16) memcpy(cf.inv, poses_inv16 + 16 * f, sizeof cf.inv);
-        else inverse4<float>(poses16 + 16 * f, cf.inv);
+        pose_inverse(f, poses16, poses_inv16, cf.inv);
         cf.depth_off = (int64_t)slots[f] * h->hc.slot_elems;
     }
     const PubWords pw = pub_words(h, 0);
     unsigned long long *d_count = (unsigned long long *)pw.total;
     CarveFrame *d_frames = (CarveFrame *)pw.tiles;
     HIP_TRY(h, hipMemcpyAsync(d_frames, h->carve_frames.data(), sizeof(CarveFrame) * (size_t)n_frames, hipMemcpyHostToDevice, h->stream));
-    CarveConst c;
-    memset(&c, 0, sizeof c);
-    for (int a = 0; a < 3; a++) c.origin[a] = spec->origin[a];
-    c.voxel = spec->voxel;
-    c.w = h->hc.w; c.h = h->hc.h; c.pitch = h->hc.pitch;
-    c.fx = h->cfg.fx; c.fy = h->cfg.fy; c.cx = h->cfg.cx; c.cy = h->cfg.cy;
-    c.near_d = params->near_dist; c.far_d = params->far_dist; c.margin = params->margin;
+    CarveConst c = carve_const(spec, h->hc.w, h->hc.h, h->hc.pitch, h->cfg.fx, h->cfg.fy, h->cfg.cx, h->cfg.cy, params->near_dist, params->far_dist);
+    c.margin = params->margin;
     c.flags = flags;
-    const hipError_t e = launch_carve((const float *)h->hc.depth_base, d_frames, n_frames, c, spec->nx, spec->ny, spec->nz, (uint32_t *)free_device, d_count,
-                                      h->stream);
+    const hipError_t e = launch_carve((const float *)h->hc.depth_base, d_frames, n_frames, c, d, (uint32_t *)free_device, d_count, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "carve launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[8], d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     // the call returns when the set is there: nothing enqueued later (an upload into one of the slots) can overtake the reads
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (n_free) memcpy(n_free, &h->h_scalars[8], sizeof(int64_t));
+    if ((rc = count_down(h, kHsCarved, d_count, sizeof(unsigned long long)))) return rc;
+    if (n_free) memcpy(n_free, &h->h_scalars[kHsCarved], sizeof(int64_t));
     return DSM_OK;
 }
 
@@ -2438,38 +2488,35 @@ int dsm_grid_classify(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, const v
     if (!h || !n_frontier) return DSM_E_INVALID;
     if (!occupied_device || !free_device || !planes_device) return fail(h, DSM_E_INVALID, "grid classify: null source or planes");
     if ((((uintptr_t)occupied_device | (uintptr_t)free_device) & 3)) return fail(h, DSM_E_INVALID, "grid classify: a bit set is not 4-byte aligned");
-    if (!grid_dims_ok(nx, ny, nz)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^28 voxels", nx, ny, nz);
+    GridDims d;
+    if (int bad = grid_dims_check(h, nx, ny, nz, 28, d)) return bad;
     const dsm_space_planes &p = *planes_device;
     if (!p.state && !p.known_free && !p.frontier && !p.cells) return fail(h, DSM_E_INVALID, "grid classify: no output plane");
     if (p.cells && p.cells_cap < 0) return fail(h, DSM_E_INVALID, "cells_cap %d", p.cells_cap);
     if ((((uintptr_t)p.known_free | (uintptr_t)p.frontier | (uintptr_t)p.cells) & 3)) return fail(h, DSM_E_INVALID, "grid classify: a device plane is not 4-byte aligned");
-    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
-    const size_t cells_cap = p.cells ? ((size_t)p.cells_cap < n_vox ? (size_t)p.cells_cap : n_vox) : 0; // (no more cells than voxels)
-    {
-        const void *const q[4] = {p.state, p.known_free, p.frontier, p.cells};
-        const size_t bytes[4] = {n_vox, n_words * sizeof(uint32_t), n_words * sizeof(uint32_t), cells_cap ? cells_cap * sizeof(int32_t) : 1};
-        if (!planes_distinct(q, 4)) return fail(h, DSM_E_INVALID, "grid classify: two output planes are the same memory");
-        for (int a = 0; a < 4; a++)
-            for (const void *src : {occupied_device, free_device})
-                if (q[a] && ranges_overlap(q[a], bytes[a], src, n_words * sizeof(uint32_t)))
-                    return fail(h, DSM_E_INVALID, "grid classify: a plane overlaps a source");
-    }
+    const size_t cells_cap = p.cells ? capped(p.cells_cap, d.n_vox()) : 0;
+    const void *const given[4] = {p.state, p.known_free, p.frontier, p.cells};
+    if (!planes_distinct(given, 4)) return fail(h, DSM_E_INVALID, "grid classify: two output planes are the same memory");
+    if (any_overlap({{p.state, (size_t)d.n_vox()}, {p.known_free, d.set_bytes()}, {p.frontier, d.set_bytes()}, {p.cells, cells_cap ? cells_cap * sizeof(int32_t) : 1}},
+                    {{occupied_device, d.set_bytes()}, {free_device, d.set_bytes()}}))
+        return fail(h, DSM_E_INVALID, "grid classify: a plane overlaps a source");
     int rc = bind_device(h);
     if (rc) return rc;
-    // scratch: the frontier words where the caller takes none, then the tile counts of the cell list
-    const size_t tiles = (n_words + 255) / 256;
-    const size_t at_tiles = p.frontier ? 0 : (n_words + 3) & ~(size_t)3;
+    // scratch: the frontier words where the caller takes none, then the tile counts of the cell list (nothing lies behind them: no pad)
+    ScratchPlan plan(16);
+    const size_t tile_bytes = (size_t)d.cell_tiles() * sizeof(int32_t);
+    const size_t at_frontier = plan.take(!p.frontier, d.set_bytes()), at_tiles = plan.take(true, tile_bytes);
     if ((rc = pub_reserve(h, 64, 0))) return rc;
-    if ((rc = plane_scratch_grow(h, h->grid_planes, (at_tiles + tiles) * sizeof(uint32_t)))) return rc;
+    if ((rc = plane_scratch_grow(h, h->grid_planes, at_tiles + tile_bytes))) return rc;
     if ((rc = pub_order_dst(h))) return rc;
-    uint32_t *scratch = h->grid_planes.as<uint32_t>();
+    uint8_t *scratch = h->grid_planes.as<uint8_t>();
     int32_t *d_total = pub_words(h, 0).cells_total;
-    const hipError_t e = launch_space((const uint32_t *)occupied_device, (const uint32_t *)free_device, nx, ny, nz, p.state, p.known_free,
-                                      p.frontier ? p.frontier : scratch, p.cells, (int)cells_cap, (int32_t *)(scratch + at_tiles), d_total, h->stream);
+    const hipError_t e = launch_space((const uint32_t *)occupied_device, (const uint32_t *)free_device, d, p.state, p.known_free,
+                                      p.frontier ? p.frontier : (uint32_t *)(scratch + at_frontier), p.cells, (int)cells_cap, (int32_t *)(scratch + at_tiles), d_total,
+                                      h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "classify launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[7], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const int32_t cells = h->h_scalars[7];
+    if ((rc = count_down(h, kHsFrontierCells, d_total, sizeof(int32_t)))) return rc;
+    const int32_t cells = h->h_scalars[kHsFrontierCells];
     *n_frontier = cells;
     if (p.cells && cells > p.cells_cap) return fail(h, DSM_E_CAPACITY, "%d frontier cells, room for %d", cells, p.cells_cap);
     return DSM_OK;
@@ -2491,27 +2538,22 @@ int dsm_grid_view(dsm_handle *h, const dsm_grid_spec *spec, const dsm_render_cam
     if ((((uintptr_t)occupied_device | (uintptr_t)free_device | (uintptr_t)target_device | (uintptr_t)visible_device) & 3) ||
         (scores_on_device && ((uintptr_t)scores & 3)))
         return fail(h, DSM_E_INVALID, "grid view: a device pointer is not 4-byte aligned");
-    if (int bad = grid_spec_check(h, spec)) return bad;
+    GridDims d;
+    if (int bad = grid_spec_check(h, spec, d)) return bad;
     if (int bad = render_camera_check(h, *camera)) return bad;
     if (n_poses < 1 || n_poses > kViewMaxPoses) return fail(h, DSM_E_INVALID, "view of %d poses, outside 1..%d", n_poses, kViewMaxPoses);
-    const int32_t dims[3] = {spec->nx, spec->ny, spec->nz};
+    const int32_t dims[3] = {d.nx, d.ny, d.nz};
     for (int f = 0; f < n_poses; f++) {
-        for (int k = 0; k < 16; k++)
-            if (!std::isfinite(poses16[16 * f + k]) || (poses_inv16 && !std::isfinite(poses_inv16[16 * f + k])))
-                return fail(h, DSM_E_INVALID, "view pose %d: pose entry %d is not finite", f, k);
+        if (int bad = pose_finite(h, "view pose", f, poses16, poses_inv16)) return bad;
         for (int a = 0; a < 3; a++)
             if (!view_reach_ok(comp_from_voxel(poses16[16 * f + 12 + a], spec->origin[a], spec->voxel), dims[a]))
                 return fail(h, DSM_E_INVALID, "view pose %d: the camera's voxel is more than %d voxels outside the grid along axis %d", f, kViewMaxReach, a);
     }
-    const size_t n_words = (size_t)((spec->nx + 31) / 32) * spec->ny * spec->nz, set_bytes = n_words * sizeof(uint32_t);
-    const size_t score_bytes = sizeof(dsm_view_score) * (size_t)n_poses, vis_bytes = set_bytes * (size_t)n_poses;
-    for (const void *src : {occupied_device, free_device, target_device}) {
-        if (!src) continue;
-        if ((visible_device && ranges_overlap(visible_device, vis_bytes, src, set_bytes)) || (scores && scores_on_device && ranges_overlap(scores, score_bytes, src, set_bytes)))
-            return fail(h, DSM_E_INVALID, "grid view: an output overlaps a source");
-    }
-    if (visible_device && scores && scores_on_device && ranges_overlap(visible_device, vis_bytes, scores, score_bytes))
-        return fail(h, DSM_E_INVALID, "grid view: the two outputs overlap");
+    const size_t score_bytes = sizeof(dsm_view_score) * (size_t)n_poses, vis_bytes = d.set_bytes() * (size_t)n_poses;
+    const Span vis = {visible_device, vis_bytes}, dev_scores = {scores_on_device ? scores : nullptr, score_bytes};
+    if (any_overlap({vis, dev_scores}, {{occupied_device, d.set_bytes()}, {free_device, d.set_bytes()}, {target_device, d.set_bytes()}}))
+        return fail(h, DSM_E_INVALID, "grid view: an output overlaps a source");
+    if (any_overlap({vis}, {dev_scores})) return fail(h, DSM_E_INVALID, "grid view: the two outputs overlap");
     int rc = bind_device(h);
     if (rc) return rc;
     // scratch (dsm_handle::pub, behind its 64 words, as dsm_grid_carve keeps its frames): the pose table, then the scores
@@ -2521,22 +2563,16 @@ int dsm_grid_view(dsm_handle *h, const dsm_grid_spec *spec, const dsm_render_cam
     h->view_poses.resize((size_t)n_poses);
     for (int f = 0; f < n_poses; f++) {
         ViewPose &vp = h->view_poses[(size_t)f];
-        if (poses_inv16) memcpy(vp.inv, poses_inv16 + 16 * f, sizeof vp.inv);
-        else inverse4<float>(poses16 + 16 * f, vp.inv);
+        pose_inverse(f, poses16, poses_inv16, vp.inv);
         for (int a = 0; a < 3; a++) vp.a[a] = comp_from_voxel(poses16[16 * f + 12 + a], spec->origin[a], spec->voxel);
         vp.reserved = 0;
     }
     ViewPose *d_poses = (ViewPose *)pub_words(h, 0).tiles;
     ViewCounts *d_scores = (ViewCounts *)(d_poses + n_poses);
     HIP_TRY(h, hipMemcpyAsync(d_poses, h->view_poses.data(), sizeof(ViewPose) * (size_t)n_poses, hipMemcpyHostToDevice, h->stream));
-    CarveConst c;
-    memset(&c, 0, sizeof c);
-    for (int a = 0; a < 3; a++) c.origin[a] = spec->origin[a];
-    c.voxel = spec->voxel;
-    c.w = camera->width; c.h = camera->height; c.pitch = camera->width;
-    c.fx = camera->fx; c.fy = camera->fy; c.cx = camera->cx; c.cy = camera->cy;
-    c.near_d = camera->near_dist; c.far_d = camera->far_dist;
-    const hipError_t e = launch_view(d_poses, n_poses, c, flags, spec->nx, spec->ny, spec->nz, (const uint32_t *)occupied_device, (const uint32_t *)free_device,
+    const CarveConst c = carve_const(spec, camera->width, camera->height, camera->width, camera->fx, camera->fy, camera->cx, camera->cy, camera->near_dist,
+                                     camera->far_dist);
+    const hipError_t e = launch_view(d_poses, n_poses, c, flags, d, (const uint32_t *)occupied_device, (const uint32_t *)free_device,
                                      (const uint32_t *)target_device, d_scores, visible_device, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "view launch: %s", hipGetErrorString(e));
     if (scores) HIP_TRY(h, hipMemcpyAsync(scores, d_scores, score_bytes, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
@@ -2551,52 +2587,47 @@ int dsm_grid_components(dsm_handle *h, int32_t nx, int32_t ny, int32_t nz, int32
     if (!h || !n_components) return DSM_E_INVALID;
     if (!src_device || !planes_device) return fail(h, DSM_E_INVALID, "grid components: null source or planes");
     if ((((uintptr_t)src_device | (uintptr_t)tag_src_device) & 3)) return fail(h, DSM_E_INVALID, "grid components: the bit set or the tag plane is not 4-byte aligned");
-    if (!grid_dims_ok(nx, ny, nz, kFieldMaxVoxels)) return fail(h, DSM_E_INVALID, "grid %d x %d x %d: a dimension below 1 or more than 2^26 voxels", nx, ny, nz);
+    GridDims d;
+    if (int bad = grid_dims_check(h, nx, ny, nz, 26, d)) return bad;
     if (connectivity != kConnectFaces && connectivity != kConnectAll) return fail(h, DSM_E_INVALID, "grid components: connectivity %d, neither 6 nor 26", connectivity);
     if (min_count < 1) return fail(h, DSM_E_INVALID, "grid components: min_count %d", min_count);
     const dsm_component_planes &p = *planes_device;
     if (!p.label && !p.table) return fail(h, DSM_E_INVALID, "grid components: no output plane");
     if (p.table && p.table_cap < 0) return fail(h, DSM_E_INVALID, "table_cap %d", p.table_cap);
     if (((uintptr_t)p.label & 3) || ((uintptr_t)p.table & 7)) return fail(h, DSM_E_INVALID, "grid components: a device plane is not aligned to its element");
-    const size_t n_vox = (size_t)nx * ny * nz, n_words = (size_t)((nx + 31) / 32) * ny * nz;
-    const size_t cap = p.table ? ((size_t)p.table_cap < n_vox ? (size_t)p.table_cap : n_vox) : 0; // (no more components than voxels)
-    {
-        const void *const q[2] = {p.label, p.table};
-        const size_t bytes[2] = {n_vox * sizeof(int32_t), cap ? cap * sizeof(dsm_component) : 1};
-        if (!planes_distinct(q, 2) || (p.label && p.table && ranges_overlap(p.label, bytes[0], p.table, bytes[1])))
-            return fail(h, DSM_E_INVALID, "grid components: two output planes are the same memory");
-        for (int a = 0; a < 2; a++) {
-            if (q[a] && ranges_overlap(q[a], bytes[a], src_device, n_words * sizeof(uint32_t)))
-                return fail(h, DSM_E_INVALID, "grid components: a plane overlaps the source");
-            if (q[a] && tag_src_device && ranges_overlap(q[a], bytes[a], tag_src_device, n_vox * sizeof(int32_t)))
-                return fail(h, DSM_E_INVALID, "grid components: a plane overlaps the tag plane");
-        }
+    const size_t n_vox = (size_t)d.n_vox();
+    const size_t cap = p.table ? capped(p.table_cap, d.n_vox()) : 0;
+    const Span label = {p.label, n_vox * sizeof(int32_t)}, table = {p.table, cap ? cap * sizeof(dsm_component) : 1};
+    // (the same start is an overlap too: both spans hold a byte at least, the table of no room the one it is taken for)
+    if (any_overlap({label}, {table})) return fail(h, DSM_E_INVALID, "grid components: two output planes are the same memory");
+    for (const Span &q : {label, table}) {
+        if (any_overlap({q}, {{src_device, d.set_bytes()}})) return fail(h, DSM_E_INVALID, "grid components: a plane overlaps the source");
+        if (any_overlap({q}, {{tag_src_device, n_vox * sizeof(int32_t)}})) return fail(h, DSM_E_INVALID, "grid components: a plane overlaps the tag plane");
     }
     int rc = bind_device(h);
     if (rc) return rc;
     // scratch, every part from a 256-byte boundary: the label plane where the caller takes none, the work plane, the two bit planes,
     // the tile counts of both
-    const size_t tiles = (n_words + 255) / 256;
-    size_t at = 0;
-    const auto take = [&](bool here, size_t bytes) { const size_t was = at; if (here) at += (bytes + 255) & ~(size_t)255; return was; };
-    const size_t at_label = take(!p.label, n_vox * sizeof(int32_t)), at_work = take(true, n_vox * sizeof(int32_t));
-    const size_t at_roots = take(true, n_words * sizeof(uint32_t)), at_keep = take(true, n_words * sizeof(uint32_t));
-    const size_t at_root_tiles = take(true, tiles * sizeof(int32_t)), at_keep_tiles = take(true, tiles * sizeof(int32_t));
+    ScratchPlan plan(256);
+    const size_t tile_bytes = (size_t)d.cell_tiles() * sizeof(int32_t);
+    const size_t at_label = plan.take(!p.label, n_vox * sizeof(int32_t)), at_work = plan.take(true, n_vox * sizeof(int32_t));
+    const size_t at_roots = plan.take(true, d.set_bytes()), at_keep = plan.take(true, d.set_bytes());
+    const size_t at_root_tiles = plan.take(true, tile_bytes), at_keep_tiles = plan.take(true, tile_bytes);
     if ((rc = pub_reserve(h, 64, 0))) return rc;
-    if ((rc = plane_scratch_grow(h, h->components, at))) return rc;
+    if ((rc = plane_scratch_grow(h, h->components, plan.bytes()))) return rc;
     if ((rc = pub_order_dst(h))) return rc;
     uint8_t *sc = h->components.as<uint8_t>();
     int32_t *d_kept = pub_words(h, 0).cells_total, *d_all = d_kept + 1;
-    const hipError_t e = launch_components((const uint32_t *)src_device, tag_src_device, nx, ny, nz, connectivity, min_count,
+    const hipError_t e = launch_components((const uint32_t *)src_device, tag_src_device, d, connectivity, min_count,
                                            p.label ? p.label : (int32_t *)(sc + at_label), (int32_t *)(sc + at_work), (uint32_t *)(sc + at_roots),
                                            (uint32_t *)(sc + at_keep), (int32_t *)(sc + at_root_tiles), (int32_t *)(sc + at_keep_tiles), p.table, (int)cap,
                                            d_all, d_kept, h->stream);
     if (e != hipSuccess) return fail(h, DSM_E_HIP, "components launch: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(&h->h_scalars[10], d_kept, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const int32_t kept = h->h_scalars[10];
+    static_assert(kHsComponents == kHsKept + 1, "the two counts come down in one copy");
+    if ((rc = count_down(h, kHsKept, d_kept, 2 * sizeof(int32_t)))) return rc;
+    const int32_t kept = h->h_scalars[kHsKept];
     *n_components = kept;
-    if (n_all) *n_all = h->h_scalars[11];
+    if (n_all) *n_all = h->h_scalars[kHsComponents];
     if (p.table && kept > p.table_cap) return fail(h, DSM_E_CAPACITY, "%d components, room for %d", kept, p.table_cap);
     return DSM_OK;
 }
@@ -2706,7 +2737,7 @@ int dsm_align_frame(dsm_handle *h, int slot, int select, int32_t n_segments, con
     int rc = align_setup(h, slot, model_cam, params, c);
     if (rc) return rc;
     // dsm_render_compose's own checks of what it is handed below, made here so that they too come before any device work
-    if ((rc = pose_finite(h, pose16_guess, nullptr))) return rc;
+    if ((rc = pose_finite(h, nullptr, 0, pose16_guess, nullptr))) return rc;
     MapSequence sq;
     if ((rc = check_sequence(h, select, n_segments, store_begin, store_count, INT32_MAX - 4096, sq))) return rc;
     if ((rc = bind_device(h))) return rc;
@@ -3106,7 +3137,7 @@ int dsm_last_new_count(dsm_handle *h, int32_t *n_new) {
     int rc = bind_device(h);
     if (rc) return rc;
     if ((rc = sync_and_fetch_counts(h))) return rc;
-    *n_new = h->h_scalars[1];
+    *n_new = h->h_scalars[kHsNew];
     return DSM_OK;
 }
 

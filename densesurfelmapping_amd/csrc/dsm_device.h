@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/dsm.h"
+#include "dsm_grid_shape.h"
 #include "dsm_math.h"
 
 namespace dsm {
@@ -269,13 +270,13 @@ struct GridOut {          // device memory; row-major [nz][ny][..]
 hipError_t launch_grid(const dsm_surfel *store, const RunTable &rt, const MapPart &mp, const GridSpec &g, int inflate, const GridScratch &sc,
                        const GridOut &out, hipStream_t st);
 // dst = src dilated by the voxels within radius r; pad bits of src ignored, of dst 0.  src != dst.
-hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int ny, int nz, int r, hipStream_t st);
+hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, const GridDims &d, int r, hipStream_t st);
 
 // ---- the distance field of a bit set (dsm_k_field.h; the definition is field_key of dsm_math.h)
 // bits: [nz][ny][wx] words, pad bits ignored.  1 <= r <= kFieldMaxDist, at most kFieldMaxVoxels voxels.  table: [r^2 + 1] metres by
 // squared distance (field_table_entry).  ox: [voxels] bytes and mid: [voxels] words of scratch.  dist2 / nearest / distance: tight
 // [nz][ny][nx] planes, any may be null.
-hipError_t launch_field(const uint32_t *bits, int nx, int ny, int nz, int r, const float *table, int8_t *ox, uint32_t *mid, uint16_t *dist2,
+hipError_t launch_field(const uint32_t *bits, const GridDims &d, int r, const float *table, int8_t *ox, uint32_t *mid, uint16_t *dist2,
                         int32_t *nearest, float *distance, hipStream_t st);
 
 // ---- free space carved by depth frames, the three-state map and its frontier (dsm_k_carve.h; the definition is carve_voxel of dsm_carve.h)
@@ -285,26 +286,26 @@ struct CarveFrame {    // 72 bytes, in device memory: one per frame of the call
 };
 // bits |= the voxels that carve_voxel frees against any of the n_frames frames (c.flags & kCarveReplace: bits = those voxels); pad bits
 // are written 0.  c: everything but inv.  *count = the population of bits afterwards (cleared on `st` first).
-hipError_t launch_carve(const float *depth_base, const CarveFrame *frames, int n_frames, const CarveConst &c, int nx, int ny, int nz, uint32_t *bits,
+hipError_t launch_carve(const float *depth_base, const CarveFrame *frames, int n_frames, const CarveConst &c, const GridDims &d, uint32_t *bits,
                         unsigned long long *count, hipStream_t st);
 // occ / fre: [nz][ny][wx] words, pad bits ignored.  frontier ([nz][ny][wx]) is always written: the list and the count are taken from
 // it; state ([nz][ny][nx] bytes), known_free and cells may be null.  cell_tiles: (words + 255) / 256 ints of scratch; *cells_total =
 // the number of frontier voxels; no cell is written at or beyond cells_cap.
-hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, int nx, int ny, int nz, uint8_t *state, uint32_t *known_free, uint32_t *frontier,
+hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, const GridDims &d, uint8_t *state, uint32_t *known_free, uint32_t *frontier,
                         int32_t *cells, int cells_cap, int32_t *cell_tiles, int32_t *cells_total, hipStream_t st);
 
 // ---- candidate camera poses scored against the grid (dsm_k_view.h; the definition is in dsm_view.h)
 // occ / fre / target: [nz][ny][wx] words, pad bits ignored; target may be null.  c: the grid's origin and voxel and the view camera,
 // everything but inv, which is the pose's.  scores: [n_poses], cleared on `st` first; visible: [n_poses][nz][ny][wx] or null, pad
 // bits written 0.
-hipError_t launch_view(const ViewPose *poses, int n_poses, const CarveConst &c, uint32_t flags, int nx, int ny, int nz, const uint32_t *occ,
+hipError_t launch_view(const ViewPose *poses, int n_poses, const CarveConst &c, uint32_t flags, const GridDims &d, const uint32_t *occ,
                        const uint32_t *fre, const uint32_t *target, ViewCounts *scores, uint32_t *visible, hipStream_t st);
 
 // ---- connected components of a bit set (dsm_k_components.h; the definition is in dsm_components.h)
 // src: [nz][ny][wx] words, pad bits ignored; at most kFieldMaxVoxels voxels.  label: [voxels], always written (the caller's plane or
 // scratch); work: [voxels] of scratch; root_bits / keep_bits: [words]; root_tiles / keep_tiles: (words + 255) / 256 ints each.  table
 // may be null: no statistics; no entry is written at or beyond cap.  *n_all = the components, *n_kept = those with count >= min_count.
-hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, int nx, int ny, int nz, int connectivity, int min_count, int32_t *label,
+hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, const GridDims &d, int connectivity, int min_count, int32_t *label,
                              int32_t *work, uint32_t *root_bits, uint32_t *keep_bits, int32_t *root_tiles, int32_t *keep_tiles, dsm_component *table,
                              int cap, int32_t *n_all, int32_t *n_kept, hipStream_t st);
 

@@ -24,22 +24,25 @@ namespace dsm {
 
 struct CarveArgs {
     CarveConst c; // all but inv, which is the frame's
-    int nx, ny, nz, wx, n_frames;
+    GridDims g;
+    int n_frames;
 };
+static_assert(offsetof(CarveArgs, g) == sizeof(CarveConst) && offsetof(CarveArgs, n_frames) == sizeof(CarveConst) + 16 && sizeof(CarveArgs) == sizeof(CarveConst) + 20,
+              "as the kernel was built for");
 
 __global__ __launch_bounds__(256) void k_carve(const float *__restrict__ depth_base, const CarveFrame *__restrict__ frames, uint32_t *__restrict__ bits,
                                                unsigned long long *__restrict__ count, const CarveArgs a) {
     const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int per_row = (a.nx + 63) >> 6;
-    const int64_t units = (int64_t)a.ny * a.nz * per_row;
+    const int per_row = (a.g.nx + 63) >> 6;
+    const int64_t units = (int64_t)a.g.ny * a.g.nz * per_row;
     const bool replace = (a.c.flags & kCarveReplace) != 0;
     unsigned long long freed = 0; // (wave-uniform)
     for (int64_t u = (int64_t)blockIdx.x * 4 + wv; u < units; u += (int64_t)gridDim.x * 4) {
         const int64_t row = u / per_row;
-        const int x = (int)(u % per_row) * 64 + lane, y = (int)(row % a.ny), z = (int)(row / a.ny);
+        const int x = (int)(u % per_row) * 64 + lane, y = (int)(row % a.g.ny), z = (int)(row / a.g.ny);
         const int w = x >> 5;
-        const bool inside = x < a.nx; // (then w < wx)
-        bool is_free = inside && !replace && ((bits[row * a.wx + w] >> (x & 31)) & 1u);
+        const bool inside = x < a.g.nx; // (then w < wx)
+        bool is_free = inside && !replace && ((bits[row * a.g.wx + w] >> (x & 31)) & 1u);
         if (inside && !is_free) {
             CarveConst c = a.c;
             for (int f = 0; f < a.n_frames; f++) {
@@ -51,35 +54,36 @@ __global__ __launch_bounds__(256) void k_carve(const float *__restrict__ depth_b
             }
         }
         const unsigned long long m = __ballot(is_free);
-        if ((lane & 31) == 0 && w < a.wx) bits[row * a.wx + w] = (uint32_t)(m >> (lane & 32));
+        if ((lane & 31) == 0 && w < a.g.wx) bits[row * a.g.wx + w] = (uint32_t)(m >> (lane & 32));
         freed += (unsigned long long)__popcll(m);
     }
     if (lane == 0 && freed) atomicAdd(count, freed);
 }
 
 struct SpaceArgs {
-    int nx, ny, nz, wx;
+    GridDims g;
 };
+static_assert(sizeof(SpaceArgs) == 16, "as the kernels were built for");
 
 // the unknown voxels of word w of row (y, z): 0 outside the grid, the pad bits 0
 __device__ __forceinline__ uint32_t space_unknown(const uint32_t *__restrict__ occ, const uint32_t *__restrict__ fre, int w, int y, int z, const SpaceArgs &a,
                                                   uint32_t last_mask) {
-    if (w < 0 || w >= a.wx || y < 0 || y >= a.ny || z < 0 || z >= a.nz) return 0u;
-    const int64_t i = ((int64_t)z * a.ny + y) * a.wx + w;
+    if (w < 0 || w >= a.g.wx || y < 0 || y >= a.g.ny || z < 0 || z >= a.g.nz) return 0u;
+    const int64_t i = ((int64_t)z * a.g.ny + y) * a.g.wx + w;
     const uint32_t unknown = ~(occ[i] | fre[i]);
-    return w == a.wx - 1 ? unknown & last_mask : unknown;
+    return w == a.g.wx - 1 ? unknown & last_mask : unknown;
 }
 
 __global__ __launch_bounds__(256) void k_space_words(const uint32_t *__restrict__ occ, const uint32_t *__restrict__ fre, uint32_t *__restrict__ known_free,
                                                      uint32_t *__restrict__ frontier, const SpaceArgs a) {
-    const int64_t n_words = (int64_t)a.wx * a.ny * a.nz;
-    const uint32_t last_mask = (a.nx & 31) ? (1u << (a.nx & 31)) - 1u : 0xffffffffu;
+    const int64_t n_words = (int64_t)a.g.wx * a.g.ny * a.g.nz;
+    const uint32_t last_mask = (a.g.nx & 31) ? (1u << (a.g.nx & 31)) - 1u : 0xffffffffu;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * 256) {
-        const int w = (int)(i % a.wx);
-        const int64_t row = i / a.wx;
-        const int y = (int)(row % a.ny), z = (int)(row / a.ny);
+        const int w = (int)(i % a.g.wx);
+        const int64_t row = i / a.g.wx;
+        const int y = (int)(row % a.g.ny), z = (int)(row / a.g.ny);
         uint32_t kf = fre[i] & ~occ[i];
-        if (w == a.wx - 1) kf &= last_mask;
+        if (w == a.g.wx - 1) kf &= last_mask;
         if (known_free) known_free[i] = kf;
         if (frontier) {
             const uint32_t here = space_unknown(occ, fre, w, y, z, a, last_mask);
@@ -94,44 +98,35 @@ __global__ __launch_bounds__(256) void k_space_words(const uint32_t *__restrict_
 
 __global__ __launch_bounds__(256) void k_space_state(const uint32_t *__restrict__ occ, const uint32_t *__restrict__ fre, uint8_t *__restrict__ state,
                                                      const SpaceArgs a) {
-    const int64_t n_vox = (int64_t)a.nx * a.ny * a.nz;
+    const int64_t n_vox = (int64_t)a.g.nx * a.g.ny * a.g.nz;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_vox; i += (int64_t)gridDim.x * 256) {
-        const int64_t row = i / a.nx;
-        const int x = (int)(i - row * a.nx);
-        const int64_t wi = row * a.wx + (x >> 5);
+        const int64_t row = i / a.g.nx;
+        const int x = (int)(i - row * a.g.nx);
+        const int64_t wi = row * a.g.wx + (x >> 5);
         state[i] = space_state((occ[wi] >> (x & 31)) & 1u, (fre[wi] >> (x & 31)) & 1u);
     }
 }
 
-hipError_t launch_carve(const float *depth_base, const CarveFrame *frames, int n_frames, const CarveConst &c, int nx, int ny, int nz, uint32_t *bits,
+hipError_t launch_carve(const float *depth_base, const CarveFrame *frames, int n_frames, const CarveConst &c, const GridDims &d, uint32_t *bits,
                         unsigned long long *count, hipStream_t st) {
     const hipError_t e0 = hipMemsetAsync(count, 0, sizeof(unsigned long long), st);
     if (e0 != hipSuccess) return e0;
     CarveArgs a;
     a.c = c;
-    a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32; a.n_frames = n_frames;
-    const int64_t units = (int64_t)ny * nz * ((nx + 63) / 64); // <= 2^28
-    const int blocks = (int)((units + 3) / 4 < 16384 ? (units + 3) / 4 : 16384);
-    hipLaunchKernelGGL(k_carve, dim3(blocks), dim3(256), 0, st, depth_base, frames, bits, count, a);
+    a.g = d;
+    a.n_frames = n_frames;
+    hipLaunchKernelGGL(k_carve, dim3(launch_blocks(d.units64(), 4, 16384)), dim3(256), 0, st, depth_base, frames, bits, count, a);
     return hipGetLastError();
 }
 
-// frontier: always written (the list and the count are taken from it); known_free, state, cells may be null.  cell_tiles: (n_words +
-// 255) / 256 ints of scratch, cells_total: one int.
-hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, int nx, int ny, int nz, uint8_t *state, uint32_t *known_free, uint32_t *frontier,
+// frontier: always written (the list and the count are taken from it); known_free, state, cells may be null.  cell_tiles:
+// d.cell_tiles() ints of scratch, cells_total: one int.
+hipError_t launch_space(const uint32_t *occ, const uint32_t *fre, const GridDims &d, uint8_t *state, uint32_t *known_free, uint32_t *frontier,
                         int32_t *cells, int cells_cap, int32_t *cell_tiles, int32_t *cells_total, hipStream_t st) {
-    SpaceArgs a;
-    a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32;
-    const int64_t n_words = (int64_t)a.wx * ny * nz, n_vox = (int64_t)nx * ny * nz;
-    {
-        const int blocks = (int)((n_words + 255) / 256 < 8192 ? (n_words + 255) / 256 : 8192);
-        hipLaunchKernelGGL(k_space_words, dim3(blocks), dim3(256), 0, st, occ, fre, known_free, frontier, a);
-    }
-    if (state) {
-        const int blocks = (int)((n_vox + 255) / 256 < 16384 ? (n_vox + 255) / 256 : 16384);
-        hipLaunchKernelGGL(k_space_state, dim3(blocks), dim3(256), 0, st, occ, fre, state, a);
-    }
-    launch_cell_list(frontier, n_words, nx, a.wx, cell_tiles, cells_total, cells, cells_cap, st);
+    const SpaceArgs a = {d};
+    hipLaunchKernelGGL(k_space_words, dim3(launch_blocks(d.n_words(), 256, 8192)), dim3(256), 0, st, occ, fre, known_free, frontier, a);
+    if (state) hipLaunchKernelGGL(k_space_state, dim3(launch_blocks(d.n_vox(), 256, 16384)), dim3(256), 0, st, occ, fre, state, a);
+    launch_cell_list(frontier, d, cell_tiles, cells_total, cells, cells_cap, st);
     return hipGetLastError();
 }
 

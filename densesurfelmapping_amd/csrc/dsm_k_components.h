@@ -34,14 +34,15 @@ constexpr int kCompTileZ = 1;        // slices
 constexpr int kCompBlockWords = 256; // words per workgroup trip of the word passes: the tile of k_grid_cell_count
 
 struct CompArgs {
-    int nx, ny, nz, wx;
+    GridDims g;
     uint32_t last_mask; // the valid bits of the last word of a row
 };
+static_assert(sizeof(CompArgs) == 20 && offsetof(CompArgs, last_mask) == 16, "as the kernels were built for");
 
 // word w of row (y, z), inside the grid; the pad bits 0
 __device__ __forceinline__ uint32_t comp_word(const uint32_t *__restrict__ src, int w, int y, int z, const CompArgs &a) {
-    const uint32_t v = src[((int64_t)z * a.ny + y) * a.wx + w];
-    return w == a.wx - 1 ? v & a.last_mask : v;
+    const uint32_t v = src[((int64_t)z * a.g.ny + y) * a.g.wx + w];
+    return w == a.g.wx - 1 ? v & a.last_mask : v;
 }
 
 // The parent plane is read with relaxed device-scope loads.  A value that is out of date is an EARLIER parent of the same voxel:
@@ -83,11 +84,11 @@ __device__ __forceinline__ void comp_union(int32_t *label, int32_t a0, int32_t b
 }
 
 __global__ __launch_bounds__(256) void k_comp_init(const uint32_t *__restrict__ src, int32_t *__restrict__ label, const CompArgs a) {
-    const int64_t n_vox = (int64_t)a.nx * a.ny * a.nz;
+    const int64_t n_vox = (int64_t)a.g.nx * a.g.ny * a.g.nz;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_vox; i += (int64_t)gridDim.x * 256) {
-        const int64_t row = i / a.nx;
-        const int x = (int)(i - row * a.nx), b = x & 31;
-        const uint32_t word = src[row * a.wx + (x >> 5)];
+        const int64_t row = i / a.g.nx;
+        const int x = (int)(i - row * a.g.nx), b = x & 31;
+        const uint32_t word = src[row * a.g.wx + (x >> 5)];
         int32_t l = -1;
         if ((word >> b) & 1u) {
             const uint32_t gaps_below = ~word & ((1u << b) - 1u); // the clear bits below mine: none of them a pad bit
@@ -118,14 +119,14 @@ __device__ __forceinline__ void comp_union_runs(int32_t *label, uint32_t m, int3
 
 template <int CONN>
 __global__ __launch_bounds__(256) void k_comp_merge(const uint32_t *__restrict__ src, int32_t *label, const CompArgs a) {
-    const int64_t n_words = (int64_t)a.wx * a.ny * a.nz;
+    const int64_t n_words = (int64_t)a.g.wx * a.g.ny * a.g.nz;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * 256) {
-        const int w = (int)(i % a.wx);
-        const int64_t row = i / a.wx;
-        const int y = (int)(row % a.ny), z = (int)(row / a.ny);
+        const int w = (int)(i % a.g.wx);
+        const int64_t row = i / a.g.wx;
+        const int y = (int)(row % a.g.ny), z = (int)(row / a.g.ny);
         const uint32_t mine = comp_word(src, w, y, z, a);
         if (!mine) continue;
-        const int32_t base = (int32_t)(row * a.nx + w * 32);
+        const int32_t base = (int32_t)(row * a.g.nx + w * 32);
         // the run that continues from the word to the left (never the last word of a row: no pad bits there)
         if ((mine & 1u) && w > 0 && (src[i - 1] >> 31)) comp_union(label, base, base - 1);
 #pragma unroll
@@ -137,15 +138,15 @@ __global__ __launch_bounds__(256) void k_comp_merge(const uint32_t *__restrict__
                 const bool straight = comp_adjacent(0, dy, dz, conn), diagonal = comp_adjacent(1, dy, dz, conn);
                 if (!straight && !diagonal) continue;
                 const int yy = y + dy, zz = z + dz;
-                if (yy < 0 || yy >= a.ny || zz < 0) continue;
+                if (yy < 0 || yy >= a.g.ny || zz < 0) continue;
                 const uint32_t n = comp_word(src, w, yy, zz, a);
-                const int32_t off = (int32_t)(((int64_t)dz * a.ny + dy) * a.nx);
+                const int32_t off = (int32_t)(((int64_t)dz * a.g.ny + dy) * a.g.nx);
                 if (straight) comp_union_runs(label, mine & n, base, off);
                 if (diagonal) {
                     // bit b of `left` / `right`: the voxel at x - 1 / x + 1 of the other row.  Where the voxel at x of that row is
                     // set as well it has joined both already (it is in the neighbour's run): those bits are left out.
                     const uint32_t lo = w > 0 ? comp_word(src, w - 1, yy, zz, a) >> 31 : 0u;
-                    const uint32_t hi = w + 1 < a.wx ? comp_word(src, w + 1, yy, zz, a) & 1u : 0u;
+                    const uint32_t hi = w + 1 < a.g.wx ? comp_word(src, w + 1, yy, zz, a) & 1u : 0u;
                     const uint32_t left = (n << 1) | lo, right = (n >> 1) | (hi << 31);
                     comp_union_runs(label, mine & left & ~n, base, off - 1);
                     comp_union_runs(label, mine & right & ~n, base, off + 1);
@@ -183,17 +184,17 @@ __device__ __forceinline__ int comp_wave_max(int v) {
 // the thread, and the lanes of a wave that end with the root of the wave's first such lane share one atomic.
 __global__ __launch_bounds__(256) void k_comp_count(const uint32_t *__restrict__ src, const int32_t *__restrict__ label, int32_t *__restrict__ count,
                                                     uint32_t *__restrict__ root_bits, const CompArgs a) {
-    const int64_t n_words = (int64_t)a.wx * a.ny * a.nz;
+    const int64_t n_words = (int64_t)a.g.wx * a.g.ny * a.g.nz;
     const int lane = lane_id();
     for (int64_t tile = blockIdx.x; tile * kCompBlockWords < n_words; tile += gridDim.x) {
         const int64_t i = tile * kCompBlockWords + threadIdx.x;
         int32_t r = -1, n = 0;
         if (i < n_words) {
-            const int w = (int)(i % a.wx);
-            const int64_t row = i / a.wx;
+            const int w = (int)(i % a.g.wx);
+            const int64_t row = i / a.g.wx;
             uint32_t m = src[i];
-            if (w == a.wx - 1) m &= a.last_mask;
-            const int32_t base = (int32_t)(row * a.nx + w * 32);
+            if (w == a.g.wx - 1) m &= a.last_mask;
+            const int32_t base = (int32_t)(row * a.g.nx + w * 32);
             uint32_t roots = 0u;
             while (m) {
                 int s, len;
@@ -219,9 +220,9 @@ __global__ __launch_bounds__(256) void k_comp_count(const uint32_t *__restrict__
 
 __global__ __launch_bounds__(256) void k_comp_keep(const uint32_t *__restrict__ root_bits, const int32_t *__restrict__ count, uint32_t *__restrict__ keep_bits,
                                                    int min_count, const CompArgs a) {
-    const int64_t n_words = (int64_t)a.wx * a.ny * a.nz;
+    const int64_t n_words = (int64_t)a.g.wx * a.g.ny * a.g.nz;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * 256) {
-        const int32_t base = (int32_t)((i / a.wx) * a.nx + (i % a.wx) * 32);
+        const int32_t base = (int32_t)((i / a.g.wx) * a.g.nx + (i % a.g.wx) * 32);
         uint32_t v = root_bits[i], keep = 0u;
         while (v) {
             const int b = __ffs((int)v) - 1;
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(256) void k_comp_rank(const uint32_t *__restrict__ 
                                                    const int32_t *__restrict__ tile_off, int32_t *__restrict__ work, const int32_t *__restrict__ tag_src,
                                                    dsm_component *__restrict__ table, int cap, const CompArgs a) {
     __shared__ int s_cnt[4];
-    const int64_t n_words = (int64_t)a.wx * a.ny * a.nz;
+    const int64_t n_words = (int64_t)a.g.wx * a.g.ny * a.g.nz;
     const int lane = lane_id(), wv = threadIdx.x >> 6;
     for (int64_t tile = blockIdx.x; tile * kCompBlockWords < n_words; tile += gridDim.x) {
         const int64_t i = tile * kCompBlockWords + threadIdx.x;
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(256) void k_comp_rank(const uint32_t *__restrict__ 
         __syncthreads();
         int at = tile_off[tile] + (incl - c);
         for (int k = 0; k < wv; k++) at += s_cnt[k];
-        const int32_t base = i < n_words ? (int32_t)((i / a.wx) * a.nx + (i % a.wx) * 32) : 0;
+        const int32_t base = i < n_words ? (int32_t)((i / a.g.wx) * a.g.nx + (i % a.g.wx) * 32) : 0;
         while (roots) {
             const int b = __ffs((int)roots) - 1;
             roots &= roots - 1;
@@ -295,19 +296,19 @@ __device__ __forceinline__ void comp_part_flush(dsm_component *table, const Comp
 // per word, after k_comp_rank: the runs of the kept components into their table entries.  The same sharing as k_comp_count.
 __global__ __launch_bounds__(256) void k_comp_stats(const uint32_t *__restrict__ src, const int32_t *__restrict__ label, const int32_t *__restrict__ work,
                                                     dsm_component *table, const CompArgs a) {
-    const int64_t n_words = (int64_t)a.wx * a.ny * a.nz;
+    const int64_t n_words = (int64_t)a.g.wx * a.g.ny * a.g.nz;
     const int lane = lane_id();
     for (int64_t tile = blockIdx.x; tile * kCompBlockWords < n_words; tile += gridDim.x) {
         const int64_t i = tile * kCompBlockWords + threadIdx.x;
         CompPart p;
         p.k = -1;
         if (i < n_words) {
-            const int w = (int)(i % a.wx);
-            const int64_t row = i / a.wx;
-            const int y = (int)(row % a.ny), z = (int)(row / a.ny);
+            const int w = (int)(i % a.g.wx);
+            const int64_t row = i / a.g.wx;
+            const int y = (int)(row % a.g.ny), z = (int)(row / a.g.ny);
             uint32_t m = src[i];
-            if (w == a.wx - 1) m &= a.last_mask;
-            const int32_t base = (int32_t)(row * a.nx + w * 32);
+            if (w == a.g.wx - 1) m &= a.last_mask;
+            const int32_t base = (int32_t)(row * a.g.nx + w * 32);
             while (m) {
                 int s, len;
                 comp_first_run(m, s, len);
@@ -351,16 +352,13 @@ __global__ __launch_bounds__(256) void k_comp_stats(const uint32_t *__restrict__
 }
 
 // label: [voxels] (the caller's plane or scratch), work: [voxels], root_bits / keep_bits: [words], root_tiles / keep_tiles:
-// (words + 255) / 256 ints each; *n_all / *n_kept: the counts.  table may be null (cap 0): no statistics are taken.
-hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, int nx, int ny, int nz, int connectivity, int min_count, int32_t *label,
+// d.cell_tiles() ints each; *n_all / *n_kept: the counts.  table may be null (cap 0): no statistics are taken.
+hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, const GridDims &d, int connectivity, int min_count, int32_t *label,
                              int32_t *work, uint32_t *root_bits, uint32_t *keep_bits, int32_t *root_tiles, int32_t *keep_tiles, dsm_component *table,
                              int cap, int32_t *n_all, int32_t *n_kept, hipStream_t st) {
-    CompArgs a;
-    a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32;
-    a.last_mask = (nx & 31) ? (1u << (nx & 31)) - 1u : 0xffffffffu;
-    const int64_t n_words = (int64_t)a.wx * ny * nz, n_vox = (int64_t)nx * ny * nz; // <= 2^26 each
-    const int vox_blocks = (int)((n_vox + 255) / 256 < 16384 ? (n_vox + 255) / 256 : 16384);
-    const int word_blocks = (int)((n_words + 255) / 256 < 8192 ? (n_words + 255) / 256 : 8192);
+    const CompArgs a = {d, d.last_mask()};
+    const int64_t n_vox = d.n_vox(); // <= 2^26, as the words
+    const int vox_blocks = launch_blocks(n_vox, 256, 16384), word_blocks = launch_blocks(d.n_words(), 256, 8192);
     const hipError_t e0 = hipMemsetAsync(work, 0, (size_t)n_vox * sizeof(int32_t), st);
     if (e0 != hipSuccess) return e0;
     hipLaunchKernelGGL(k_comp_init, dim3(vox_blocks), dim3(256), 0, st, src, label, a);
@@ -370,8 +368,8 @@ hipError_t launch_components(const uint32_t *src, const int32_t *tag_src, int nx
     hipLaunchKernelGGL(k_comp_count, dim3(word_blocks), dim3(256), 0, st, src, (const int32_t *)label, work, root_bits, a);
     hipLaunchKernelGGL(k_comp_keep, dim3(word_blocks), dim3(256), 0, st, (const uint32_t *)root_bits, (const int32_t *)work, keep_bits, min_count, a);
     // the counts alone, no list: the tiles of the cell list are k_comp_rank's (kCompBlockWords)
-    launch_cell_list(root_bits, n_words, nx, a.wx, root_tiles, n_all, nullptr, 0, st);
-    launch_cell_list(keep_bits, n_words, nx, a.wx, keep_tiles, n_kept, nullptr, 0, st);
+    launch_cell_list(root_bits, d, root_tiles, n_all, nullptr, 0, st);
+    launch_cell_list(keep_bits, d, keep_tiles, n_kept, nullptr, 0, st);
     if (table && cap > 0) {
         hipLaunchKernelGGL(k_comp_rank, dim3(word_blocks), dim3(256), 0, st, (const uint32_t *)root_bits, (const uint32_t *)keep_bits,
                            (const int32_t *)keep_tiles, work, tag_src, table, cap, a);

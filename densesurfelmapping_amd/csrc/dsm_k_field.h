@@ -26,8 +26,10 @@ constexpr uint32_t kFieldMidNone = 0xffffffffu; // k_field_y: no set voxel withi
 constexpr int kFieldTile = 64;                  // rows (slices) of output per workgroup of the y (z) pass; a wave takes every fourth
 
 struct FieldArgs {
-    int nx, ny, nz, wx, r;
+    GridDims g;
+    int r;
 };
+static_assert(sizeof(FieldArgs) == 20 && offsetof(FieldArgs, r) == 16, "as the kernels were built for");
 
 // word w of a row of the bit set: 0 outside the row, the pad bits of the last word masked
 __device__ __forceinline__ uint32_t field_word(const uint32_t *__restrict__ row, int w, int wx, uint32_t last_mask) {
@@ -46,16 +48,16 @@ __device__ __forceinline__ unsigned long long field_window(const uint32_t *__res
 
 __global__ __launch_bounds__(256) void k_field_x(const uint32_t *__restrict__ bits, int8_t *__restrict__ ox, const FieldArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)a.nx * a.ny * a.nz) return;
-    const int64_t row = i / a.nx;
-    const int x = (int)(i - row * a.nx);
-    const uint32_t *rw = bits + row * a.wx;
-    const uint32_t last_mask = (a.nx & 31) ? (1u << (a.nx & 31)) - 1u : 0xffffffffu;
+    if (i >= (int64_t)a.g.nx * a.g.ny * a.g.nz) return;
+    const int64_t row = i / a.g.nx;
+    const int x = (int)(i - row * a.g.nx);
+    const uint32_t *rw = bits + row * a.g.wx;
+    const uint32_t last_mask = (a.g.nx & 31) ? (1u << (a.g.nx & 31)) - 1u : 0xffffffffu;
     int below = kFieldMaxDist + 1, above = kFieldMaxDist + 1; // distances; R + 1 or more = none
-    const unsigned long long lo = field_window(rw, x - 63, a.wx, last_mask); // bit 63 = x
+    const unsigned long long lo = field_window(rw, x - 63, a.g.wx, last_mask); // bit 63 = x
     if (lo) below = __clzll((long long)lo);
-    else if (x >= 64 && ((field_word(rw, (x - 64) >> 5, a.wx, last_mask) >> ((x - 64) & 31)) & 1u)) below = 64;
-    const unsigned long long hi = field_window(rw, x + 1, a.wx, last_mask); // bit 0 = x + 1
+    else if (x >= 64 && ((field_word(rw, (x - 64) >> 5, a.g.wx, last_mask) >> ((x - 64) & 31)) & 1u)) below = 64;
+    const unsigned long long hi = field_window(rw, x + 1, a.g.wx, last_mask); // bit 0 = x + 1
     if (hi) above = __ffsll((long long)hi);
     int o = kFieldNone;
     if (below <= a.r && below <= above) o = -below; // (the lower x on a tie)
@@ -68,26 +70,26 @@ __global__ __launch_bounds__(256) void k_field_y(const int8_t *__restrict__ ox, 
     extern __shared__ int8_t s_field_ox[];
     __shared__ uint8_t s_any[4][64]; // per wave and column: did its rows of the tile hold an entry?
     const int r = a.r, rows = kFieldTile + 2 * r;
-    const int tiles_x = (a.nx + 63) / 64, tiles_y = (a.ny + kFieldTile - 1) / kFieldTile;
+    const int tiles_x = (a.g.nx + 63) / 64, tiles_y = (a.g.ny + kFieldTile - 1) / kFieldTile;
     const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x % tiles_y, z = blockIdx.x / tiles_x / tiles_y;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = bx * 64 + lane, y0 = by * kFieldTile - r;
-    const int64_t slice = (int64_t)z * a.ny;
+    const int64_t slice = (int64_t)z * a.g.ny;
     bool any = false;
     for (int j = wv; j < rows; j += 4) {
         const int y = y0 + j;
         int8_t v = (int8_t)kFieldNone;
-        if (x < a.nx && y >= 0 && y < a.ny) v = ox[(slice + y) * a.nx + x];
+        if (x < a.g.nx && y >= 0 && y < a.g.ny) v = ox[(slice + y) * a.g.nx + x];
         any |= v != (int8_t)kFieldNone;
         s_field_ox[j * 64 + lane] = v;
     }
     s_any[wv][lane] = any;
     __syncthreads();
-    if (x >= a.nx) return;
+    if (x >= a.g.nx) return;
     const int walk = (s_any[0][lane] | s_any[1][lane] | s_any[2][lane] | s_any[3][lane]) ? r : -1; // an empty column: nothing to walk to
     for (int t = wv; t < kFieldTile; t += 4) {
         const int y = by * kFieldTile + t;
-        if (y >= a.ny) break; // (wave-uniform)
+        if (y >= a.g.ny) break; // (wave-uniform)
         const int c = t + r;  // this row in the tile: c - r >= 0, c + r < rows
         unsigned long long best = ~0ull;
         int best_o = 0, best_dy = 0;
@@ -98,11 +100,11 @@ __global__ __launch_bounds__(256) void k_field_y(const int8_t *__restrict__ ox, 
                 if (o == kFieldNone) continue;
                 const int d2 = o * o + d * d;
                 if (d2 > r * r) continue;
-                const unsigned long long key = field_key((uint32_t)d2, (uint32_t)((y + dy) * a.nx + (x + o))); // (rows of one slice: y' nx + x' orders as lin)
+                const unsigned long long key = field_key((uint32_t)d2, (uint32_t)((y + dy) * a.g.nx + (x + o))); // (rows of one slice: y' nx + x' orders as lin)
                 if (key < best) { best = key; best_o = o; best_dy = dy; }
             }
         }
-        mid[(slice + y) * a.nx + x] =
+        mid[(slice + y) * a.g.nx + x] =
             best == ~0ull ? kFieldMidNone : (uint32_t)(best >> 32) | ((uint32_t)(uint8_t)best_o << 16) | ((uint32_t)(uint8_t)best_dy << 24);
     }
 }
@@ -118,25 +120,25 @@ __global__ __launch_bounds__(256) void k_field_z(const uint32_t *__restrict__ mi
     extern __shared__ uint32_t s_field_mid[];
     __shared__ uint8_t s_any[4][64]; // as in k_field_y
     const int r = a.r, rows = kFieldTile + 2 * r;
-    const int tiles_x = (a.nx + 63) / 64;
-    const int bx = blockIdx.x % tiles_x, y = blockIdx.x / tiles_x % a.ny, bz = blockIdx.x / tiles_x / a.ny;
+    const int tiles_x = (a.g.nx + 63) / 64;
+    const int bx = blockIdx.x % tiles_x, y = blockIdx.x / tiles_x % a.g.ny, bz = blockIdx.x / tiles_x / a.g.ny;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = bx * 64 + lane, z0 = bz * kFieldTile - r;
     bool any = false;
     for (int j = wv; j < rows; j += 4) {
         const int z = z0 + j;
         uint32_t v = kFieldMidNone;
-        if (x < a.nx && z >= 0 && z < a.nz) v = mid[((int64_t)z * a.ny + y) * a.nx + x];
+        if (x < a.g.nx && z >= 0 && z < a.g.nz) v = mid[((int64_t)z * a.g.ny + y) * a.g.nx + x];
         any |= v != kFieldMidNone;
         s_field_mid[j * 64 + lane] = v;
     }
     s_any[wv][lane] = any;
     __syncthreads();
-    if (x >= a.nx) return;
+    if (x >= a.g.nx) return;
     const int walk = (s_any[0][lane] | s_any[1][lane] | s_any[2][lane] | s_any[3][lane]) ? r : -1;
     for (int t = wv; t < kFieldTile; t += 4) {
         const int z = bz * kFieldTile + t;
-        if (z >= a.nz) break; // (wave-uniform)
+        if (z >= a.g.nz) break; // (wave-uniform)
         const int c = t + r;
         unsigned long long best = ~0ull;
         for (int d = 0; d <= walk; d++) {
@@ -147,11 +149,11 @@ __global__ __launch_bounds__(256) void k_field_z(const uint32_t *__restrict__ mi
                 const int d2 = (int)(m & 0xffffu) + d * d;
                 if (d2 > r * r) continue;
                 const int xo = x + (int8_t)(m >> 16), yo = y + (int8_t)(m >> 24);
-                const unsigned long long key = field_key((uint32_t)d2, (uint32_t)(((int64_t)(z + dz) * a.ny + yo) * a.nx + xo)); // < 2^26
+                const unsigned long long key = field_key((uint32_t)d2, (uint32_t)(((int64_t)(z + dz) * a.g.ny + yo) * a.g.nx + xo)); // < 2^26
                 if (key < best) best = key;
             }
         }
-        const int64_t i = ((int64_t)z * a.ny + y) * a.nx + x;
+        const int64_t i = ((int64_t)z * a.g.ny + y) * a.g.nx + x;
         const bool have = best != ~0ull;
         const uint32_t d2 = (uint32_t)(best >> 32);
         if (out.dist2) out.dist2[i] = have ? (uint16_t)d2 : kFieldFar;
@@ -161,12 +163,13 @@ __global__ __launch_bounds__(256) void k_field_z(const uint32_t *__restrict__ mi
 }
 
 // the three passes on one stream.  ox: [voxels] bytes, mid: [voxels] words of scratch.  1 <= r <= kFieldMaxDist, at most kFieldMaxVoxels voxels.
-hipError_t launch_field(const uint32_t *bits, int nx, int ny, int nz, int r, const float *table, int8_t *ox, uint32_t *mid, uint16_t *dist2,
+hipError_t launch_field(const uint32_t *bits, const GridDims &d, int r, const float *table, int8_t *ox, uint32_t *mid, uint16_t *dist2,
                         int32_t *nearest, float *distance, hipStream_t st) {
     FieldArgs a;
-    a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32; a.r = r;
-    const int64_t n_vox = (int64_t)nx * ny * nz, tiles_x = (nx + 63) / 64;
-    const int64_t blocks_y = tiles_x * ((ny + kFieldTile - 1) / kFieldTile) * nz, blocks_z = tiles_x * ny * ((nz + kFieldTile - 1) / kFieldTile);
+    a.g = d;
+    a.r = r;
+    const int64_t n_vox = d.n_vox(), tiles_x = (d.nx + 63) / 64;
+    const int64_t blocks_y = tiles_x * ((d.ny + kFieldTile - 1) / kFieldTile) * d.nz, blocks_z = tiles_x * d.ny * ((d.nz + kFieldTile - 1) / kFieldTile);
     if (n_vox > kFieldMaxVoxels || r < 1 || r > kFieldMaxDist) return hipErrorInvalidValue; // (so every block count is at most 2^26)
     FieldOut out;
     out.dist2 = dist2; out.nearest = nearest; out.distance = distance;

@@ -181,9 +181,11 @@ __global__ __launch_bounds__(256) void k_grid_bits(const uint32_t *__restrict__ 
 // ---- inflation
 constexpr int kGridTileW = 8, kGridTileY = 8, kGridTileZ = 4; // output words per workgroup: 8 along x, 8 rows, 4 slices = 256
 struct GridInflateArgs {
-    int nx, ny, nz, wx, r;
+    GridDims g;
+    int r;
     uint8_t width[kGridMaxInflate * kGridMaxInflate + 1]; // by dy^2 + dz^2: grid_inflate_width (host-built)
 };
+static_assert(sizeof(GridInflateArgs) == 280 && offsetof(GridInflateArgs, r) == 16 && offsetof(GridInflateArgs, width) == 20, "as the kernel was built for");
 
 // OR of v << s for s = 0 .. k (k <= 16) by doubling: after the loop v holds the shifts 0 .. have - 1, and 2 have > k + 1
 __device__ __forceinline__ unsigned long long grid_smear_up(unsigned long long v, int k) {
@@ -208,23 +210,23 @@ __global__ __launch_bounds__(256) void k_grid_inflate(const uint32_t *__restrict
     extern __shared__ uint32_t s_tile[];
     const int r = a.r;
     const int lw = kGridTileW + 2, ly = kGridTileY + 2 * r, lz = kGridTileZ + 2 * r;
-    const int tiles_x = (a.wx + kGridTileW - 1) / kGridTileW, tiles_y = (a.ny + kGridTileY - 1) / kGridTileY;
+    const int tiles_x = (a.g.wx + kGridTileW - 1) / kGridTileW, tiles_y = (a.g.ny + kGridTileY - 1) / kGridTileY;
     const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x % tiles_y, bz = blockIdx.x / tiles_x / tiles_y;
     const int w0 = bx * kGridTileW - 1, y0 = by * kGridTileY - r, z0 = bz * kGridTileZ - r;
-    const uint32_t last_mask = (a.nx & 31) ? (1u << (a.nx & 31)) - 1u : 0xffffffffu;
+    const uint32_t last_mask = (a.g.nx & 31) ? (1u << (a.g.nx & 31)) - 1u : 0xffffffffu;
     for (int i = threadIdx.x; i < lw * ly * lz; i += 256) {
         const int w = w0 + i % lw, y = y0 + i / lw % ly, z = z0 + i / lw / ly;
         uint32_t v = 0;
-        if (w >= 0 && w < a.wx && y >= 0 && y < a.ny && z >= 0 && z < a.nz) {
-            v = src[((int64_t)z * a.ny + y) * a.wx + w];
-            if (w == a.wx - 1) v &= last_mask;
+        if (w >= 0 && w < a.g.wx && y >= 0 && y < a.g.ny && z >= 0 && z < a.g.nz) {
+            v = src[((int64_t)z * a.g.ny + y) * a.g.wx + w];
+            if (w == a.g.wx - 1) v &= last_mask;
         }
         s_tile[i] = v;
     }
     __syncthreads();
     const int tw = threadIdx.x % kGridTileW, ty = threadIdx.x / kGridTileW % kGridTileY, tz = threadIdx.x / kGridTileW / kGridTileY;
     const int w = bx * kGridTileW + tw, y = by * kGridTileY + ty, z = bz * kGridTileZ + tz;
-    if (w >= a.wx || y >= a.ny || z >= a.nz) return;
+    if (w >= a.g.wx || y >= a.g.ny || z >= a.g.nz) return;
     uint32_t out = 0;
     for (int dz = -r; dz <= r; dz++)
         for (int dy = -r; dy <= r; dy++) {
@@ -235,8 +237,8 @@ __global__ __launch_bounds__(256) void k_grid_inflate(const uint32_t *__restrict
             const unsigned long long below = ((unsigned long long)row[1] << 32) | row[0], above = ((unsigned long long)row[2] << 32) | row[1];
             out |= (uint32_t)(grid_smear_up(below, k) >> 32) | (uint32_t)grid_smear_down(above, k);
         }
-    if (w == a.wx - 1) out &= last_mask;
-    dst[((int64_t)z * a.ny + y) * a.wx + w] = out;
+    if (w == a.g.wx - 1) out &= last_mask;
+    dst[((int64_t)z * a.g.ny + y) * a.g.wx + w] = out;
 }
 
 // ---- the cell list: 256 words per workgroup
@@ -283,22 +285,23 @@ __global__ __launch_bounds__(256) void k_grid_cell_scatter(const uint32_t *__res
 }
 
 // *cells_total = the set bits of bits[0, n_words) (rows of wx words, nx voxels); with `cells`, their linear indices ascending, none
-// at or beyond cells_cap.  cell_tiles: (n_words + 255) / 256 ints of scratch (<= 2^20: at most 2^28 words)
-inline void launch_cell_list(const uint32_t *bits, int64_t n_words, int nx, int wx, int32_t *cell_tiles, int32_t *cells_total, int32_t *cells,
-                             int cells_cap, hipStream_t st) {
-    const int64_t tiles = (n_words + 255) / 256;
-    const int blocks = (int)(tiles < 8192 ? tiles : 8192);
+// at or beyond cells_cap.  cell_tiles: d.cell_tiles() ints of scratch (<= 2^20: at most 2^28 words)
+inline void launch_cell_list(const uint32_t *bits, const GridDims &d, int32_t *cell_tiles, int32_t *cells_total, int32_t *cells, int cells_cap,
+                             hipStream_t st) {
+    const int64_t n_words = d.n_words(), tiles = d.cell_tiles();
+    const int blocks = launch_blocks(n_words, 256, 8192);
     hipLaunchKernelGGL(k_grid_cell_count, dim3(blocks), dim3(256), 0, st, bits, n_words, cell_tiles);
     hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, cell_tiles, (int)tiles, cells_total);
     if (cells && cells_cap > 0)
-        hipLaunchKernelGGL(k_grid_cell_scatter, dim3(blocks), dim3(256), 0, st, bits, n_words, nx, wx, (const int32_t *)cell_tiles, cells, cells_cap);
+        hipLaunchKernelGGL(k_grid_cell_scatter, dim3(blocks), dim3(256), 0, st, bits, n_words, d.nx, d.wx, (const int32_t *)cell_tiles, cells, cells_cap);
 }
 
-hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int ny, int nz, int r, hipStream_t st) {
+hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, const GridDims &d, int r, hipStream_t st) {
     GridInflateArgs a;
-    a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32; a.r = r;
+    a.g = d;
+    a.r = r;
     for (int s = 0; s <= kGridMaxInflate * kGridMaxInflate; s++) a.width[s] = (uint8_t)(s <= r * r ? grid_inflate_width(r, s) : 0);
-    const int64_t tiles = (int64_t)((a.wx + kGridTileW - 1) / kGridTileW) * ((ny + kGridTileY - 1) / kGridTileY) * ((nz + kGridTileZ - 1) / kGridTileZ);
+    const int64_t tiles = (int64_t)((d.wx + kGridTileW - 1) / kGridTileW) * ((d.ny + kGridTileY - 1) / kGridTileY) * ((d.nz + kGridTileZ - 1) / kGridTileZ);
     if (tiles > INT32_MAX) return hipErrorInvalidValue; // (never: at most 2^28 voxels, a tile holds at least one)
     const size_t lds = (size_t)(kGridTileW + 2) * (kGridTileY + 2 * r) * (kGridTileZ + 2 * r) * sizeof(uint32_t); // <= 57600 bytes at r = 16
     hipLaunchKernelGGL(k_grid_inflate, dim3((unsigned)tiles), dim3(256), lds, st, src, dst, a);
@@ -308,13 +311,11 @@ hipError_t launch_grid_inflate(const uint32_t *src, uint32_t *dst, int nx, int n
 // the clear, then the lists, then the planes derived from them: launched in this order on one stream
 hipError_t launch_grid(const dsm_surfel *store, const RunTable &rt, const MapPart &mp, const GridSpec &g, int inflate, const GridScratch &sc,
                        const GridOut &out, hipStream_t st) {
-    const int wx = (g.n[0] + 31) / 32;
-    const int64_t rows = (int64_t)g.n[1] * g.n[2], n_vox = rows * g.n[0], n_words = rows * wx; // <= 2^28 each
+    const GridDims d = grid_dims(g.n[0], g.n[1], g.n[2]);
     {
-        const int64_t n = out.index ? n_vox : n_words;
-        const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-        hipLaunchKernelGGL(k_grid_clear, dim3(blocks), dim3(256), 0, st, out.index ? (uint32_t *)out.index : out.occupied, n, out.index ? 0xffffffffu : 0u,
-                           sc.counts);
+        const int64_t n = out.index ? d.n_vox() : d.n_words(); // <= 2^28 each
+        hipLaunchKernelGGL(k_grid_clear, dim3(launch_blocks(n, 256, 8192)), dim3(256), 0, st, out.index ? (uint32_t *)out.index : out.occupied, n,
+                           out.index ? 0xffffffffu : 0u, sc.counts);
     }
     GridSetupArgs a;
     a.g = g;
@@ -325,26 +326,25 @@ hipError_t launch_grid(const dsm_surfel *store, const RunTable &rt, const MapPar
     if (map_tiles(mp) > 0) hipLaunchKernelGGL(k_grid_setup_map, dim3(map_tiles(mp)), dim3(256), 0, st, mp, rt.total, a, sc.splats, sc.counts);
     GridTarget t;
     t.g = g;
-    t.wx = wx;
+    t.wx = d.wx;
     t.index = (uint32_t *)out.index;
     t.bits = out.occupied;
     if (sc.n_seq > 0) {
-        int blocks = (int)(((int64_t)sc.n_seq + 15) / 16 < 16384 ? ((int64_t)sc.n_seq + 15) / 16 : 16384);
+        int blocks = launch_blocks(sc.n_seq, 16, 16384);
         hipLaunchKernelGGL(k_grid_splat, dim3(blocks), dim3(256), 0, st, (const GridSplat *)sc.splats, (const int32_t *)sc.counts, sc.n_seq, t);
         blocks = sc.n_seq < 2048 ? sc.n_seq : 2048;
         hipLaunchKernelGGL(k_grid_splat_big, dim3(blocks), dim3(256), 0, st, (const GridSplat *)sc.splats, (const int32_t *)sc.counts, sc.n_seq, t);
     }
     if (out.index) {
-        const int64_t units = rows * ((g.n[0] + 63) / 64);
-        const int blocks = (int)((units + 3) / 4 < 8192 ? (units + 3) / 4 : 8192);
-        hipLaunchKernelGGL(k_grid_bits, dim3(blocks), dim3(256), 0, st, (const uint32_t *)out.index, out.occupied, g.n[0], wx, rows);
+        hipLaunchKernelGGL(k_grid_bits, dim3(launch_blocks(d.units64(), 4, 8192)), dim3(256), 0, st, (const uint32_t *)out.index, out.occupied, d.nx, d.wx,
+                           d.rows());
     }
     if (out.inflated) {
-        const hipError_t e = launch_grid_inflate(out.occupied, out.inflated, g.n[0], g.n[1], g.n[2], inflate, st);
+        const hipError_t e = launch_grid_inflate(out.occupied, out.inflated, d, inflate, st);
         if (e != hipSuccess) return e;
     }
     if (out.cells_total)
-        launch_cell_list(out.cells_of_inflated ? out.inflated : out.occupied, n_words, g.n[0], wx, sc.cell_tiles, out.cells_total, out.cells, out.cells_cap, st);
+        launch_cell_list(out.cells_of_inflated ? out.inflated : out.occupied, d, sc.cell_tiles, out.cells_total, out.cells, out.cells_cap, st);
     return hipGetLastError();
 }
 

@@ -183,7 +183,7 @@ hipError_t launch_render(const dsm_surfel *store, const RunTable &rt, const MapP
     im.near_d = cam.near_d;
     im.far_d = cam.far_d;
     if (sc.n_seq > 0) {
-        int blocks = (int)(((int64_t)sc.n_seq + 15) / 16 < 16384 ? ((int64_t)sc.n_seq + 15) / 16 : 16384);
+        int blocks = launch_blocks(sc.n_seq, 16, 16384);
         hipLaunchKernelGGL(k_render_splat, dim3(blocks), dim3(256), 0, st, (const RenderSplat *)sc.splats, (const int32_t *)sc.counts, sc.n_seq, im);
         blocks = sc.n_seq < 2048 ? sc.n_seq : 2048;
         hipLaunchKernelGGL(k_render_splat_big, dim3(blocks), dim3(256), 0, st, (const RenderSplat *)sc.splats, (const int32_t *)sc.counts, sc.n_seq, im);

@@ -92,7 +92,7 @@ __device__ __forceinline__ int two_ended_slot(bool small, bool big, int32_t *__r
 __global__ void k_cloud_scan(int32_t *__restrict__ tile_cnt, int n_tiles, int32_t *__restrict__ total); // dsm_k_cloud.h
 
 inline int map_tiles(const MapPart &mp) { return (mp.n_upper + kCloudTile - 1) / kCloudTile; } // the grid of a map_tile_walk kernel
-inline int run_blocks(int total) { return (total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096; } // the grid of a kernel over the runs
+inline int run_blocks(int total) { return launch_blocks(total, 256, 4096); } // the grid of a kernel over the runs
 
 // mp.tile_cnt = the tile offsets and mp.total[0] = the count that a map_tile_walk kernel launched behind this finds
 inline hipError_t launch_map_offsets(const MapPart &mp, hipStream_t st) {

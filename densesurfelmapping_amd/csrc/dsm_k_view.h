@@ -26,9 +26,13 @@ namespace dsm {
 
 struct ViewArgs {
     CarveConst c; // origin, voxel, the view camera; inv is the pose's
-    int nx, ny, nz, wx, n_poses;
+    GridDims g;
+    int n_poses;
     uint32_t flags;
 };
+static_assert(offsetof(ViewArgs, g) == sizeof(CarveConst) && offsetof(ViewArgs, n_poses) == sizeof(CarveConst) + 16 && offsetof(ViewArgs, flags) == sizeof(CarveConst) + 20 &&
+                  sizeof(ViewArgs) == sizeof(CarveConst) + 24,
+              "as the kernel was built for");
 
 constexpr int kViewBlocksX = 1024, kViewBlocksY = 64; // the launch caps: units of 4 waves, poses
 
@@ -36,8 +40,8 @@ __global__ __launch_bounds__(256) void k_view(const ViewPose *__restrict__ poses
                                               const uint32_t *__restrict__ target, ViewCounts *__restrict__ scores, uint32_t *__restrict__ visible,
                                               const ViewArgs a) {
     const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const int per_row = (a.nx + 63) >> 6;
-    const int64_t units = (int64_t)a.ny * a.nz * per_row, n_words = (int64_t)a.ny * a.nz * a.wx;
+    const int per_row = (a.g.nx + 63) >> 6;
+    const int64_t units = (int64_t)a.g.ny * a.g.nz * per_row, n_words = (int64_t)a.g.ny * a.g.nz * a.g.wx;
     const bool unknown_blocks = (a.flags & kViewUnknownBlocks) != 0;
     for (int pose = blockIdx.y; pose < a.n_poses; pose += gridDim.y) {
         CarveConst c = a.c;
@@ -46,9 +50,9 @@ __global__ __launch_bounds__(256) void k_view(const ViewPose *__restrict__ poses
         int n_in = 0, n_vis = 0, n_unk = 0, n_free = 0, n_occ = 0, n_tgt = 0; // (wave-uniform)
         for (int64_t u = (int64_t)blockIdx.x * 4 + wv; u < units; u += (int64_t)gridDim.x * 4) {
             const int64_t row = u / per_row;
-            const int x = (int)(u % per_row) * 64 + lane, y = (int)(row % a.ny), z = (int)(row / a.ny);
+            const int x = (int)(u % per_row) * 64 + lane, y = (int)(row % a.g.ny), z = (int)(row / a.g.ny);
             const int w = x >> 5;
-            const bool inside = x < a.nx; // (then w < wx)
+            const bool inside = x < a.g.nx; // (then w < wx)
             const bool in_view = inside && view_in_view(c, x, y, z);
             bool vis = in_view;
             if (in_view) {
@@ -60,8 +64,8 @@ __global__ __launch_bounds__(256) void k_view(const ViewPose *__restrict__ poses
                     for (int32_t j = 1; j < n; j++) {
                         view_walk_step(wk);
                         const int px = wk.p[0], py = wk.p[1], pz = wk.p[2];
-                        if (px < 0 || px >= a.nx || py < 0 || py >= a.ny || pz < 0 || pz >= a.nz) break; // (outside from here on)
-                        const int64_t wi = ((int64_t)pz * a.ny + py) * a.wx + (px >> 5);
+                        if (px < 0 || px >= a.g.nx || py < 0 || py >= a.g.ny || pz < 0 || pz >= a.g.nz) break; // (outside from here on)
+                        const int64_t wi = ((int64_t)pz * a.g.ny + py) * a.g.wx + (px >> 5);
                         const uint32_t o = occ[wi];
                         const uint32_t blockers = unknown_blocks ? (o | ~fre[wi]) : o;
                         if ((blockers >> (px & 31)) & 1u) {
@@ -73,14 +77,14 @@ __global__ __launch_bounds__(256) void k_view(const ViewPose *__restrict__ poses
             }
             uint32_t o_bit = 0, f_bit = 0, t_bit = 0;
             if (vis) {
-                const int64_t wi = row * a.wx + w;
+                const int64_t wi = row * a.g.wx + w;
                 o_bit = (occ[wi] >> (x & 31)) & 1u;
                 f_bit = (fre[wi] >> (x & 31)) & 1u;
                 if (target) t_bit = (target[wi] >> (x & 31)) & 1u;
             }
             const uint8_t state = space_state(o_bit != 0, f_bit != 0);
             const unsigned long long m = __ballot(vis);
-            if (visible && (lane & 31) == 0 && w < a.wx) visible[(int64_t)pose * n_words + row * a.wx + w] = (uint32_t)(m >> (lane & 32));
+            if (visible && (lane & 31) == 0 && w < a.g.wx) visible[(int64_t)pose * n_words + row * a.g.wx + w] = (uint32_t)(m >> (lane & 32));
             n_in += __popcll(__ballot(in_view));
             n_vis += __popcll(m);
             n_unk += __popcll(__ballot(vis && state == kSpaceUnknown));
@@ -101,16 +105,16 @@ __global__ __launch_bounds__(256) void k_view(const ViewPose *__restrict__ poses
 }
 
 // scores: [n_poses], cleared on `st` first; visible: [n_poses][nz][ny][wx] or null; target may be null.  c: everything but inv.
-hipError_t launch_view(const ViewPose *poses, int n_poses, const CarveConst &c, uint32_t flags, int nx, int ny, int nz, const uint32_t *occ,
+hipError_t launch_view(const ViewPose *poses, int n_poses, const CarveConst &c, uint32_t flags, const GridDims &d, const uint32_t *occ,
                        const uint32_t *fre, const uint32_t *target, ViewCounts *scores, uint32_t *visible, hipStream_t st) {
     const hipError_t e0 = hipMemsetAsync(scores, 0, sizeof(ViewCounts) * (size_t)n_poses, st);
     if (e0 != hipSuccess) return e0;
     ViewArgs a;
     a.c = c;
-    a.nx = nx; a.ny = ny; a.nz = nz; a.wx = (nx + 31) / 32; a.n_poses = n_poses;
+    a.g = d;
+    a.n_poses = n_poses;
     a.flags = flags;
-    const int64_t units = (int64_t)ny * nz * ((nx + 63) / 64); // <= 2^28
-    const int bx = (int)((units + 3) / 4 < kViewBlocksX ? (units + 3) / 4 : kViewBlocksX);
+    const int bx = launch_blocks(d.units64(), 4, kViewBlocksX);
     const int by = n_poses < kViewBlocksY ? n_poses : kViewBlocksY;
     hipLaunchKernelGGL(k_view, dim3(bx, by), dim3(256), 0, st, poses, occ, fre, target, scores, visible, a);
     return hipGetLastError();

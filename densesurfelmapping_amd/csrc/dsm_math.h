@@ -10,6 +10,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "dsm_grid_shape.h" // the limits of a grid: kGridMaxVoxels, kGridMaxInflate, kFieldMaxVoxels
+
 #if defined(__HIPCC__) || defined(__HIP__)
 #define DSM_HD __host__ __device__ __forceinline__
 #else
@@ -931,8 +933,6 @@ struct GridSplat {        // 64 bytes
     int32_t number;       // position in the surfel sequence
     int32_t lo[3], hi[3]; // the voxel box [lo, hi) per axis, inside the grid
 };
-constexpr int kGridMaxInflate = 16;
-constexpr int64_t kGridMaxVoxels = (int64_t)1 << 28;
 constexpr uint32_t kGridCellsOfInflated = 1u; // DSM_GRID_CELLS_OF_INFLATED
 
 DSM_HD float grid_centre(float origin, float voxel, int i) { return origin + ((float)i + 0.5f) * voxel; }
@@ -1015,7 +1015,6 @@ DSM_HD int grid_inflate_width(int r, int s) {
 // voxels, lin(o) = (oz ny + oy) nx + ox): the nearest set voxel, on a tie the one with the lowest linear index.  A minimum over a
 // total order: it does not depend on how the passes split it.
 constexpr int kFieldMaxDist = 64;
-constexpr int64_t kFieldMaxVoxels = (int64_t)1 << 26;
 constexpr uint16_t kFieldFar = 65535; // dist2 of a voxel with no set voxel within R; its `nearest` is -1
 
 DSM_HD uint64_t field_key(uint32_t d2, uint32_t lin) { return ((uint64_t)d2 << 32) | lin; }

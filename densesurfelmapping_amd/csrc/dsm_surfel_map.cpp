@@ -13,7 +13,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -140,20 +139,7 @@ double to_sec(dsm_stamp s) { return (double)s.sec + 1e-9 * (double)s.nsec; }
 
 } // namespace
 
-
 namespace {
-
-int fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (m) m->err = buf;
-    return code;
-}
-
-int engine_fail(dsm_surfel_map *m, int rc, const char *what) { return fail(m, rc, "%s: %s", what, dsm_last_error(m->engine)); }
 
 #define ENGINE_TRY(m, expr)                                  \
     do {                                                     \

@@ -5,36 +5,20 @@
 // it always used.
 #include "dsm_surfel_map_node.h"
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 namespace {
 
 using namespace dsm_node;
 
-int cloud_fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    m->err = buf;
-    return code;
-}
-
-int cloud_engine_fail(dsm_surfel_map *m, int rc, const char *what) {
-    return cloud_fail(m, rc, "%s: %s", what, dsm_last_error(m->engine));
-}
-
 // One cloud of the current state into dst (host or device memory of the node's GPU).
 int build_cloud(dsm_surfel_map *m, int kind, void *dst, int on_device, int32_t cap, int32_t *n) {
-    if (!m->last.valid) return cloud_fail(m, DSM_E_STATE, "no frame fused yet");
+    if (!m->last.valid) return fail(m, DSM_E_STATE, "no frame fused yet");
     if (kind == DSM_CLOUD_RAW) { // :1115-1151 with the latest fuse's frame and fuse_pose_ros
         const dsm_pose_msg &p = m->last.fuse_pose;
         const double pose7[7] = {p.px, p.py, p.pz, p.qx, p.qy, p.qz, p.qw};
         const int rc = dsm_frame_cloud(m->engine, m->last.slot, pose7, dst, on_device, cap, n);
-        return rc ? cloud_engine_fail(m, rc, "dsm_frame_cloud") : DSM_OK;
+        return rc ? engine_fail(m, rc, "dsm_frame_cloud") : DSM_OK;
     }
     int select = DSM_CLOUD_SELECT_NONE;
     std::vector<int32_t> begin, count;
@@ -43,7 +27,7 @@ int build_cloud(dsm_surfel_map *m, int kind, void *dst, int on_device, int32_t c
         if (kind != DSM_CLOUD_ACTIVE) { // (*pointcloud) += (*inactive_pointcloud), :1391, :1441
             int32_t total = 0;
             const int rc = dsm_store_size(m->engine, &total);
-            if (rc) return cloud_engine_fail(m, rc, "dsm_store_size");
+            if (rc) return engine_fail(m, rc, "dsm_store_size");
             begin.push_back(0);
             count.push_back(total);
         }
@@ -59,10 +43,10 @@ int build_cloud(dsm_surfel_map *m, int kind, void *dst, int on_device, int32_t c
             count.push_back(m->segments[(size_t)sg].count);
         }
     } else {
-        return cloud_fail(m, DSM_E_INVALID, "cloud kind %d", kind);
+        return fail(m, DSM_E_INVALID, "cloud kind %d", kind);
     }
     const int rc = dsm_cloud_compose(m->engine, select, (int32_t)begin.size(), begin.data(), count.data(), dst, on_device, cap, n);
-    return rc ? cloud_engine_fail(m, rc, "dsm_cloud_compose") : DSM_OK;
+    return rc ? engine_fail(m, rc, "dsm_cloud_compose") : DSM_OK;
 }
 
 // the publisher installed by dsm_surfel_map_set_publish: page-locked buffers that only grow
@@ -94,7 +78,7 @@ int grow(dsm_surfel_map *m, Publisher *pub, int k, int32_t need) {
     if (want > INT32_MAX) want = INT32_MAX;
     void *p = nullptr;
     const int rc = dsm_host_alloc(&p, (size_t)want * 4 * sizeof(float));
-    if (rc) return cloud_fail(m, rc, "no page-locked memory for %lld cloud points", (long long)want);
+    if (rc) return fail(m, rc, "no page-locked memory for %lld cloud points", (long long)want);
     pub->buf[k] = (float *)p;
     pub->cap[k] = (int32_t)want;
     return DSM_OK;
@@ -141,7 +125,7 @@ int dsm_surfel_map_get_cloud_device(dsm_surfel_map *m, int kind, void *dst_devic
 
 int dsm_surfel_map_set_publish(dsm_surfel_map *m, uint32_t kinds_mask, dsm_surfel_map_publish_fn fn, void *user) {
     if (!m) return DSM_E_INVALID;
-    if (kinds_mask & ~((1u << DSM_CLOUD_KINDS) - 1u)) return cloud_fail(m, DSM_E_INVALID, "cloud kinds mask 0x%x", kinds_mask);
+    if (kinds_mask & ~((1u << DSM_CLOUD_KINDS) - 1u)) return fail(m, DSM_E_INVALID, "cloud kinds mask 0x%x", kinds_mask);
     if (!kinds_mask || !fn) {
         release_publisher(m);
         return DSM_OK;

@@ -3,32 +3,19 @@
 // (dsm_node::render_runs).  A translation unit of its own, like the grid's.
 #include "dsm_surfel_map_node.h"
 
-#include <cstdarg>
-#include <cstdio>
-
 namespace {
 
 using namespace dsm_node;
 
-int field_fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    m->err = buf;
-    return code;
-}
-
 int field(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, int32_t max_dist, uint32_t flags, const dsm_field_planes *planes, int on_device,
           int32_t *n_surfels) {
     if (!m || !spec || !planes || !n_surfels) return DSM_E_INVALID;
-    if (!m->last.valid) return field_fail(m, DSM_E_STATE, "no frame fused yet");
+    if (!m->last.valid) return fail(m, DSM_E_STATE, "no frame fused yet");
     int select = DSM_CLOUD_SELECT_NONE;
     std::vector<int32_t> begin, count;
-    if (!render_runs(m, kind, select, begin, count)) return field_fail(m, DSM_E_INVALID, "field kind %d", kind);
+    if (!render_runs(m, kind, select, begin, count)) return fail(m, DSM_E_INVALID, "field kind %d", kind);
     const int rc = dsm_field_compose(m->engine, select, (int32_t)begin.size(), begin.data(), count.data(), spec, max_dist, flags, planes, on_device, n_surfels);
-    return rc ? field_fail(m, rc, "dsm_field_compose: %s", dsm_last_error(m->engine)) : DSM_OK;
+    return rc ? fail(m, rc, "dsm_field_compose: %s", dsm_last_error(m->engine)) : DSM_OK;
 }
 
 } // namespace

@@ -4,32 +4,19 @@
 // the renders.
 #include "dsm_surfel_map_node.h"
 
-#include <cstdarg>
-#include <cstdio>
-
 namespace {
 
 using namespace dsm_node;
 
-int grid_fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    m->err = buf;
-    return code;
-}
-
 int grid(dsm_surfel_map *m, int kind, const dsm_grid_spec *spec, uint32_t flags, const dsm_grid_planes *planes, int on_device, int32_t *n_surfels,
          int32_t *n_cells) {
     if (!m || !spec || !planes || !n_surfels || !n_cells) return DSM_E_INVALID;
-    if (!m->last.valid) return grid_fail(m, DSM_E_STATE, "no frame fused yet");
+    if (!m->last.valid) return fail(m, DSM_E_STATE, "no frame fused yet");
     int select = DSM_CLOUD_SELECT_NONE;
     std::vector<int32_t> begin, count;
-    if (!render_runs(m, kind, select, begin, count)) return grid_fail(m, DSM_E_INVALID, "grid kind %d", kind);
+    if (!render_runs(m, kind, select, begin, count)) return fail(m, DSM_E_INVALID, "grid kind %d", kind);
     const int rc = dsm_grid_compose(m->engine, select, (int32_t)begin.size(), begin.data(), count.data(), spec, flags, planes, on_device, n_surfels, n_cells);
-    return rc ? grid_fail(m, rc, "dsm_grid_compose: %s", dsm_last_error(m->engine)) : DSM_OK;
+    return rc ? fail(m, rc, "dsm_grid_compose: %s", dsm_last_error(m->engine)) : DSM_OK;
 }
 
 } // namespace

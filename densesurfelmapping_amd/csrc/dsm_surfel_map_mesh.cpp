@@ -5,33 +5,20 @@
 #include "dsm_surfel_map_node.h"
 #include "dsm_mesh_ply.h"
 
-#include <cstdarg>
 #include <cstdio>
 
 namespace {
 
 using namespace dsm_node;
 
-int mesh_fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    m->err = buf;
-    return code;
-}
-
-int mesh_engine_fail(dsm_surfel_map *m, int rc, const char *what) { return mesh_fail(m, rc, "%s: %s", what, dsm_last_error(m->engine)); }
-
 // the attached surfels, then the active ones with update_times >= 5 (:1240-1248)
 int build_mesh(dsm_surfel_map *m, int layout, void *dst, int on_device, int32_t cap, int32_t *n) {
-    if (!m->last.valid) return mesh_fail(m, DSM_E_STATE, "no frame fused yet");
+    if (!m->last.valid) return fail(m, DSM_E_STATE, "no frame fused yet");
     std::vector<int32_t> begin, count;
     attached_runs(m, begin, count);
     const int rc = dsm_mesh_compose(m->engine, DSM_CLOUD_SELECT_MATURE, (int32_t)begin.size(), begin.data(), count.data(), layout, dst, on_device,
                                     cap, n);
-    return rc ? mesh_engine_fail(m, rc, "dsm_mesh_compose") : DSM_OK;
+    return rc ? engine_fail(m, rc, "dsm_mesh_compose") : DSM_OK;
 }
 
 struct HostBlock { // page-locked: the device-to-host copy of a chunk is one DMA
@@ -66,7 +53,7 @@ int dsm_surfel_map_get_mesh_device(dsm_surfel_map *m, int vertex_layout, void *d
 
 int dsm_surfel_map_save_mesh_binary(dsm_surfel_map *m, const char *path) {
     if (!m || !path) return DSM_E_INVALID;
-    if (!m->last.valid) return mesh_fail(m, DSM_E_STATE, "no frame fused yet");
+    if (!m->last.valid) return fail(m, DSM_E_STATE, "no frame fused yet");
     std::vector<int32_t> begin, count;
     attached_runs(m, begin, count);
     int64_t n_attached = 0;
@@ -74,20 +61,20 @@ int dsm_surfel_map_save_mesh_binary(dsm_surfel_map *m, const char *path) {
     // how many active surfels are mature: a compose with no room returns the count and writes nothing
     int32_t n_active = 0;
     int rc = dsm_mesh_compose(m->engine, DSM_CLOUD_SELECT_MATURE, 0, nullptr, nullptr, DSM_MESH_VERTEX_XYZ_RGBA8, nullptr, 0, 0, &n_active);
-    if (rc && rc != DSM_E_CAPACITY) return mesh_engine_fail(m, rc, "dsm_mesh_compose");
+    if (rc && rc != DSM_E_CAPACITY) return engine_fail(m, rc, "dsm_mesh_compose");
     const int64_t n_surfels = n_attached + n_active;
-    if (n_surfels * 6 > INT32_MAX) return mesh_fail(m, DSM_E_INVALID, "%lld surfels: the PLY's int vertex_index cannot address them", (long long)n_surfels);
+    if (n_surfels * 6 > INT32_MAX) return fail(m, DSM_E_INVALID, "%lld surfels: the PLY's int vertex_index cannot address them", (long long)n_surfels);
     // one page-locked block: a chunk of the attached surfels, or the whole active part (the engine composes the map part in
     // one piece) -- no larger than either needs
     int64_t chunk_cap = n_attached < kChunkSurfels ? n_attached : kChunkSurfels;
     if (chunk_cap < n_active) chunk_cap = n_active;
     HostBlock block;
     if (chunk_cap > 0 && (rc = dsm_host_alloc(&block.p, (size_t)chunk_cap * 96)))
-        return mesh_fail(m, rc, "no page-locked memory for %lld surfels of vertices", (long long)chunk_cap);
+        return fail(m, rc, "no page-locked memory for %lld surfels of vertices", (long long)chunk_cap);
     // the file is opened only now: an engine or allocation failure above leaves the path untouched; a failure below removes it
     File file;
     file.f = std::fopen(path, "wb");
-    if (!file.f) return mesh_fail(m, DSM_E_INVALID, "cannot open %s", path);
+    if (!file.f) return fail(m, DSM_E_INVALID, "cannot open %s", path);
     struct Unlink {
         const char *path;
         bool keep = false;
@@ -105,7 +92,7 @@ int dsm_surfel_map_save_mesh_binary(dsm_surfel_map *m, const char *path) {
         int32_t got = 0;
         const int r = dsm_mesh_compose(m->engine, select, (int32_t)cb.size(), cb.data(), cc.data(), DSM_MESH_VERTEX_XYZ_RGBA8, block.p, 0,
                                        (int32_t)chunk_cap, &got);
-        if (r) return mesh_engine_fail(m, r, "dsm_mesh_compose");
+        if (r) return engine_fail(m, r, "dsm_mesh_compose");
         ok = ok && dsm_mesh_ply::write_vertices(file.f, block.p, (size_t)got * 6, scratch);
         cb.clear();
         cc.clear();
@@ -136,7 +123,7 @@ int dsm_surfel_map_save_mesh_binary(dsm_surfel_map *m, const char *path) {
     std::FILE *f = file.f;
     file.f = nullptr;
     ok = (std::fclose(f) == 0) && ok;
-    if (!ok) return mesh_fail(m, DSM_E_INVALID, "write to %s failed", path);
+    if (!ok) return fail(m, DSM_E_INVALID, "write to %s failed", path);
     partial.keep = true;
     return DSM_OK;
 }

@@ -1,4 +1,4 @@
-// dsm_surfel_map_node.h -- the state of the node (include/dsm_surfel_map.h), shared by its two translation units:
+// dsm_surfel_map_node.h -- the state of the node (include/dsm_surfel_map.h), shared by its eight translation units:
 // dsm_surfel_map.cpp (the host logic of class SurfelMap), dsm_surfel_map_clouds.cpp (the point-cloud publications),
 // dsm_surfel_map_mesh.cpp, dsm_surfel_map_render.cpp and dsm_surfel_map_align.cpp (the mesh, the rendered images, the alignment),
 // dsm_surfel_map_grid.cpp, dsm_surfel_map_field.cpp and dsm_surfel_map_space.cpp (the voxel grid, its distance field, free space).
@@ -8,7 +8,9 @@
 #include "../../include/dsm_surfel_map.h"
 
 #include <algorithm>
+#include <cstdarg>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <list>
 #include <set>
@@ -156,6 +158,20 @@ struct dsm_surfel_map {
 };
 
 namespace dsm_node {
+
+// the node's last error (dsm_surfel_map_last_error) and the code to return with it; m may be null
+inline int fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (m) m->err = buf;
+    return code;
+}
+
+// an engine call failed with rc: its name and the engine's own text
+inline int engine_fail(dsm_surfel_map *m, int rc, const char *what) { return fail(m, rc, "%s: %s", what, dsm_last_error(m->engine)); }
 
 // SurfelMap::get_driftfree_poses (:1643-1673): breadth-first over linked_pose_index, root first,
 // driftfree_range - 1 levels, each pose once in discovery order

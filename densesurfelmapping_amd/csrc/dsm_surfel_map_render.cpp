@@ -4,30 +4,17 @@
 // publish_neighbor_pointcloud's breadth-first order), then the map part.  A translation unit of its own, like the clouds and the mesh.
 #include "dsm_surfel_map_node.h"
 
-#include <cstdarg>
-#include <cstdio>
-
 namespace {
 
 using namespace dsm_node;
 
-int render_fail(dsm_surfel_map *m, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    m->err = buf;
-    return code;
-}
-
 int render(dsm_surfel_map *m, int kind, const dsm_render_camera *camera, const float *pose16, uint32_t flags, const dsm_render_planes *planes,
            int on_device, int32_t *n_surfels) {
     if (!m || !planes || !n_surfels) return DSM_E_INVALID;
-    if (!m->last.valid) return render_fail(m, DSM_E_STATE, "no frame fused yet");
+    if (!m->last.valid) return fail(m, DSM_E_STATE, "no frame fused yet");
     int select = DSM_CLOUD_SELECT_NONE;
     std::vector<int32_t> begin, count;
-    if (!render_runs(m, kind, select, begin, count)) return render_fail(m, DSM_E_INVALID, "render kind %d", kind);
+    if (!render_runs(m, kind, select, begin, count)) return fail(m, DSM_E_INVALID, "render kind %d", kind);
     dsm_render_camera own;
     if (!camera) { // the node's camera
         own.width = m->cfg.cam_width;
@@ -42,7 +29,7 @@ int render(dsm_surfel_map *m, int kind, const dsm_render_camera *camera, const f
     }
     const int rc = dsm_render_compose(m->engine, select, (int32_t)begin.size(), begin.data(), count.data(), camera, pose16 ? pose16 : m->last.pose16,
                                       nullptr, flags, planes, on_device, n_surfels);
-    return rc ? render_fail(m, rc, "dsm_render_compose: %s", dsm_last_error(m->engine)) : DSM_OK;
+    return rc ? fail(m, rc, "dsm_render_compose: %s", dsm_last_error(m->engine)) : DSM_OK;
 }
 
 } // namespace
